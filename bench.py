@@ -4,11 +4,17 @@ configs[3] / configs[4] at N>1) = image encoder -> 134 217 728 occupancy queries
 seeded random-init weights; `value` is queries per second over the whole job.
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
+A plain run sets up, warms up, times the --steps steps and prints the line (value, ms_per_step, roofline of the timed launches).
+`--full` adds, at N=1, every other measurement and check: the extras below (`--no-extras` drops them) and the CPU baseline
+(`--no-cpu-baseline` drops it).  `--dump-outputs DIR` writes the meshes the last timed step returned to DIR/*.npy (dump_outputs):
+the inputs are seeded, so two builds can be compared output for output.
+
 `--precision bf16` (default: what BASELINE configs[2] names) | `fp16` (configs[4]) | `fp32` (the parity-grade sweep:
-column kernel v11, split-f16 operands, logits within 1e-4 of the reference).  At N=1 the line also carries
+column kernel v11, split-f16 operands, logits within 1e-4 of the reference).  With --full at N=1 the line also carries
 `config.fp32_mode` - the same step timed in fp32 - and `config.precision_acceptance` - what the reduced precisions do to
 the field and the meshes at full size against the fp32 sweep (tools/precision_report.py; asserted in
 tests/test_gpu_precision.py).
@@ -24,7 +30,7 @@ N > 1, default `--mode both`: BOTH configurations north_star names, in one invoc
     config names, every rank runs the whole reconstruction, no data-path collective; its own value (N x 512^3 per max-over-ranks
     step), ms_per_step and stage_ms.
 `--mode slab` / `--mode replicas` run one of them as the headline (replicas then in --precision; the workload string says
-configs[4] only when that is fp16).  Rank 0 prints ONE JSON line.  The CPU baseline leg (rank 0, N=1 only) times the oracle - test infrastructure, the
+configs[4] only when that is fp16).  Rank 0 prints ONE JSON line.  The CPU baseline leg (rank 0, N=1, --full only) times the oracle - test infrastructure, the
 checker, never the thing measured - on a bounded sample of the same grid.
 """
 import argparse
@@ -47,6 +53,7 @@ PEAK_MFMA = 2.5e15              # dense bf16 / f16, MI355X_MICROARCH.md
 RES = 512
 IMG = 512
 REF_LOOP_PASSES = 7   # timed passes of the reference-loop leg (40 chunks each): median reported, min / max beside it
+DUMP_ROWS = 1 << 19   # --dump-outputs: rows kept per mesh array (a 512^3 step's meshes hold ~22 M vertices / 44 M faces): <= 48 MiB in all
 
 
 def main():
@@ -56,8 +63,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"])
     ap.add_argument("--resolution", type=int, default=RES)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip config.fp32_mode and config.precision_acceptance (N=1)")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: also run the CPU baseline and the extras (other precisions, kernels, loops and checks) after the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the meshes the last timed step returned (rank 0) to DIR/<name>.npy, float32 / float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip config.fp32_mode, config.precision_acceptance and the other extras")
     ap.add_argument("--mode", default="both", choices=["both", "replicas", "slab"],
                     help="N>1 only: slab = one subject split into x-slabs (strong scaling, configs[3]); replicas = one subject per GPU "
                          "(weak, configs[4]); both (default) = slab as the headline + the fp16 replicas leg in config.replicas")
@@ -67,6 +78,9 @@ def main():
     ap.add_argument("--image", default="noise", choices=["smooth", "noise"],
                     help="synthetic input: white noise x mask (SURVEY 8d, default) or band-limited; with random-init weights both give a noise-like field")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    want_extras = args.full and not args.no_extras
 
     import torch.distributed as dist
     from surs_amd import _lib, dist as sdist, mesh_util, model, options, train_util, weights
@@ -112,13 +126,14 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def run(o, steps, warmup, net=net, slab=slab):
-        """warmup untimed steps, then `steps` timed ones between barriers; -> (seconds, per-stage ms, mesh sizes, kernel timing)."""
+    def run(o, steps, warmup, net=net, slab=slab, keep=None):
+        """warmup untimed steps, then `steps` timed ones between barriers; -> (seconds, per-stage ms, mesh sizes, kernel timing).
+        keep: a dict that receives the meshes the last timed step returned (keep["mesh"])."""
         stage_ms = {"encoder": 0.0, "query": 0.0, "exchange": 0.0, "mesh": 0.0}
         last = {}
         image = image_one if (slab or world == 1) else image_own
 
-        def step(timed):
+        def step(timed, keep=None):
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
             ev[0].record()
             if slab:   # super_res on this rank's image strip, feature_lr all-gathered, filter_hr on the strip (dist.encode_sharded)
@@ -140,6 +155,8 @@ def main():
                     m = mesh_util.meshes_from_volumes(net, [vh, vl], mat, want_normals=False)   # gen_mesh keeps vertices and faces only
             if m is not None:
                 last["verts_hr"], last["faces_hr"], last["verts_lr"], last["faces_lr"] = len(m[0]), len(m[1]), len(m[4]), len(m[5])
+            if keep is not None:
+                keep["mesh"] = m
             ev[3].record()
             if timed:
                 torch.cuda.synchronize()
@@ -153,8 +170,8 @@ def main():
         lib.surs_profile_enable(1)
         barrier()
         t0 = time.perf_counter()
-        for _ in range(steps):
-            step(True)
+        for i in range(steps):
+            step(True, keep if i == steps - 1 else None)
         barrier()
         dt = time.perf_counter() - t0
         launches, kms, kpts, ktiles, ksteps = C.c_double(0), C.c_double(0), C.c_double(0), C.c_double(0), C.c_double(0)
@@ -218,7 +235,11 @@ def main():
                 pass
         return r
 
-    dt, stage_ms, last, (k_avg_ms, k_pts, k_ks) = run(opt, args.steps, args.warmup)
+    kept = {}
+    dt, stage_ms, last, (k_avg_ms, k_pts, k_ks) = run(opt, args.steps, args.warmup, keep=kept)
+    if args.dump_outputs and rank == 0:   # before anything else runs: the meshes are views of buffers the next reconstruction reuses
+        dump_outputs(args.dump_outputs, kept["mesh"])
+    del kept
     kver_head = int(last.pop("column_kernel", (0, None))[0] or 0)
 
     replicas = None
@@ -239,7 +260,7 @@ def main():
         del net16
 
     extras = {}
-    if world == 1 and not args.no_extras and args.precision != "fp32":
+    if world == 1 and want_extras and args.precision != "fp32":
         # the same step in the parity-grade precision: fp32-grade column kernel AND fp32-grade encoder (a network object of its own:
         # --precision bf16 runs the encoder's 3x3 convolutions on one f16 product per MAC)
         o32 = options.BaseOptions().parse(flags + ["--precision", "fp32"])
@@ -253,7 +274,7 @@ def main():
         extras["fp32_mode"] = {"dtype": "fp32", "value": float(R) ** 3 * 2 / d32, "unit": "queries/s", "ms_per_step": d32 / 2 * 1e3,
                                "steps": 2, "warmup": 2, "stage_ms": st32, "mesh": last32, "roofline": roofline("fp32", k32, p32, ks32, kv32),
                                "tolerance": "logits within 1e-4 of the reference's fp32 path (tests/test_gpu_query.py, test_gpu_model.py)"}
-    if world == 1 and not args.no_extras:
+    if world == 1 and want_extras:
         # The restated column kernels' cost depends on the weights and features (how many layer-0 channels change LeakyReLU branch
         # inside a z tile).  (1) dense_floor: the same step on the dense-layer-1 kernels (v3 / v5) - the data-independent guarantee,
         # and what the host falls back to above 400 listed channels per tile.  (2) listed_sensitivity: the sweep alone with layer 0's
@@ -305,7 +326,7 @@ def main():
         except Exception as e:
             lib.surs_set_grid_kernel(0)
             extras["dense_floor"] = {"error": repr(e)}
-    if world == 1 and not args.no_extras:
+    if world == 1 and want_extras:
         # a run of subjects (apps/eval_SuRS.py:74-80) - per subject: decoded 8-bit pixels -> img_LR -> encoder ->
         # reconstruction (no OBJ files).  sequential = host normalise + upload + gen_mesh's order; pipelined = device input stage,
         # next subject's decode / upload / encoder under the current sweep (train_util.gen_mesh_pipelined)
@@ -347,7 +368,7 @@ def main():
                                                   "the GPU busy in both, the pipeline hides the input stage and the host gaps"}
         except Exception as e:
             extras["subject_pipeline"] = {"error": repr(e)}
-    if world == 1 and not args.no_extras:
+    if world == 1 and want_extras:
         # (a) "drops in unchanged": the reference's own sweep loop (lib/sdf.py:32-45 batch_eval over lib/mesh_util.py:20-28 eval_func)
         # around the facade - 50 000 points per call, query_mr + query_sr + get_preds()[0][0].detach().cpu().numpy() - timed on
         # 40 chunks of a 512^3 grid's points; (b) gen_mesh's DEFAULT sweep (use_octree=True, lib/train_util.py:53,73) at 512^3 in the
@@ -453,7 +474,7 @@ def main():
                 extras["octree_mode"]["octree_sweep_precision_opt_in"] = res["octree_sweep_precision"]
         except Exception as e:
             extras["octree_mode"] = {"error": repr(e)}
-    if world == 1 and not args.no_extras and R == RES:
+    if world == 1 and want_extras and R == RES:
         try:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import precision_report as pr
@@ -516,11 +537,26 @@ def main():
             out["config"]["replicas"] = replicas
         out["config"].update(extras)
         out["config"].update(flat_scalars(stage_ms, extras, args.precision))
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(net, sd, R, b_min, b_max)
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()
+
+
+def dump_outputs(path, mesh):
+    """What a caller of the timed path receives - world-space vertices and faces of the high- and low-resolution meshes - as
+    path/<name>.npy: vertices float32 (float64 if they come so), faces float64 (exact for every vertex id).  An array of more than
+    DUMP_ROWS rows keeps DUMP_ROWS evenly spaced rows (the same rows for the same row count); path/<name>_rows_colsum.npy holds
+    the whole array's row count and float64 column sums."""
+    if mesh is None:
+        raise RuntimeError("--dump-outputs: the last timed step returned no meshes")
+    os.makedirs(path, exist_ok=True)
+    for name, a in zip(("verts_hr", "faces_hr", "verts_lr", "faces_lr"), (mesh[0], mesh[1], mesh[4], mesh[5])):
+        a = a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        rows = np.arange(DUMP_ROWS, dtype=np.int64) * (len(a) - 1) // (DUMP_ROWS - 1) if len(a) > DUMP_ROWS else slice(None)
+        np.save(os.path.join(path, name + ".npy"), a[rows].astype(np.float32 if a.dtype == np.float32 else np.float64))
+        np.save(os.path.join(path, name + "_rows_colsum.npy"), np.concatenate([[float(len(a))], a.sum(axis=0, dtype=np.float64)]))
 
 
 def flat_scalars(stage_ms, extras, precision):

@@ -274,3 +274,27 @@ def test_mlp_blob_fragment_images_and_bias_split():
     want = w1[32 * T:32 * T + 32, 16 * s_:16 * s_ + 16].reshape(32, 2, 8).transpose(1, 0, 2)
     assert np.array_equal(got, want)
     assert np.array_equal(img3[0, s_, T], rnd(np.ascontiguousarray(want)))
+
+
+def test_bench_dump_outputs_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: an array of more than DUMP_ROWS rows keeps DUMP_ROWS evenly spaced rows (the first and the last
+    among them), float32 stays float32, everything else - the int32 faces included - is written exactly as float64, the whole
+    array's row count and column sums lie beside it; at most 64 MiB in all; a step without meshes is an error."""
+    import bench
+    assert 4 * bench.DUMP_ROWS * 3 * 8 <= 64 << 20
+    monkeypatch.setattr(bench, "DUMP_ROWS", 5)
+    rng = np.random.default_rng(0)
+    vh, fh = rng.standard_normal((101, 3)), rng.integers(0, 101, (203, 3), dtype=np.int32)
+    vl, fl = rng.standard_normal((4, 3)).astype(np.float32), rng.integers(0, 4, (3, 3), dtype=np.int32)
+    bench.dump_outputs(str(tmp_path), (vh, fh, None, None, vl, fl, None, None))
+    keys = ("verts_hr", "faces_hr", "verts_lr", "faces_lr")
+    assert sorted(os.listdir(tmp_path)) == sorted(k + s for k in keys for s in (".npy", "_rows_colsum.npy"))
+    got = {k: np.load(tmp_path / (k + ".npy")) for k in keys}
+    assert got["verts_hr"].dtype == np.float64 and np.array_equal(got["verts_hr"], vh[[0, 25, 50, 75, 100]])
+    assert got["faces_hr"].dtype == np.float64 and np.array_equal(got["faces_hr"], fh[[0, 50, 101, 151, 202]])
+    assert got["verts_lr"].dtype == np.float32 and np.array_equal(got["verts_lr"], vl)
+    assert got["faces_lr"].dtype == np.float64 and np.array_equal(got["faces_lr"], fl)
+    s = np.load(tmp_path / "faces_hr_rows_colsum.npy")
+    assert s[0] == 203 and np.array_equal(s[1:], fh.sum(axis=0, dtype=np.float64))
+    with pytest.raises(RuntimeError):
+        bench.dump_outputs(str(tmp_path / "none"), None)

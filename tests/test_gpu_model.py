@@ -605,13 +605,13 @@ def test_streamed_reconstruction_equals_one_piece(precision):
 
 
 def test_bench_contract_small():
-    """bench.py prints ONE JSON line with the driver's keys (reduced resolution here; the roofline / cpu_baseline objects
+    """bench.py --full prints ONE JSON line with the driver's keys (reduced resolution here; the roofline / cpu_baseline objects
     are part of the line) and the streamed reconstruction is what the timed steps run."""
     import json
     import subprocess
     import sys
     root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--resolution", "64", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--resolution", "64", "--steps", "2", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -632,6 +632,34 @@ def test_bench_contract_small():
     assert set(d["cpu_baseline"]) >= {"value", "unit", "cores", "kind", "sample"} and d["cpu_baseline"]["kind"] == "port"
     # (no ordering between the stage times here: at this size the mesh tail and the sweep are both ~1-3 ms)
     assert "workload" in d["config"] and set(d["config"]["stage_ms_rank0"]) == {"encoder", "query", "exchange", "mesh"}
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain bench.py run times --steps steps and nothing else (no CPU baseline, no extras), and --dump-outputs writes the meshes
+    of its last timed step: float arrays, the same bits from run to run (seeded inputs), the mesh sizes the line reports."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+    lines = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--resolution", "64", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append([l for l in r.stdout.splitlines() if l.strip()])
+        assert len(lines[-1]) == 1, lines[-1]
+    d = json.loads(lines[0][0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "bf16" and d["unit"] == "queries/s" and d["higher_is_better"] is True
+    assert abs(d["value"] - 64 ** 3 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    assert "cpu_baseline" not in d and "fp32_mode" not in d["config"] and "precision_acceptance" not in d["config"]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and len(names) == 8
+    for name in names:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+    for key in ("verts_hr", "faces_hr", "verts_lr", "faces_lr"):
+        assert np.load(tmp_path / "a" / (key + ".npy")).shape == (d["config"]["mesh"][key], 3)
+        assert np.load(tmp_path / "a" / (key + "_rows_colsum.npy"))[0] == d["config"]["mesh"][key]
 
 
 def test_streamed_reconstruction_full_size():

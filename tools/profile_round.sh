@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/prof
 rm -rf $O
 mkdir -p $O
-python3 bench.py > $O/bench_line.json 2> $O/bench.err
+python3 bench.py --full > $O/bench_line.json 2> $O/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- python3 bench.py --no-cpu-baseline --no-extras > $O/bench_profiled.json 2> $O/stats.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats32 -o bench -- python3 bench.py --no-cpu-baseline --no-extras --precision fp32 > $O/bench_profiled_fp32.json 2> $O/stats32.err
 for P in bf16 fp32; do
