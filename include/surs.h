@@ -295,6 +295,48 @@ int surs_query_points_hr(const float *points, int n, const float *calib, float z
                          int hl, int wl, const float *feat_hr, int hh, int wh, const void *mlp_blob, void *workspace,
                          size_t workspace_bytes, const float *p_lr, float *pred_hr, float *logit_hr, void *stream);
 
+/* ------------------------------------------------------------------ classifiers of any supported shape */
+
+/* One SurfaceClassifier as the reference builds it from --mlp_dim_*, --mlp_res_layers_* and --no_residual
+ * (lib/model/SuRSNet.py:67-78, lib/model/SurfaceClassifier.py:7-43): n_layers Conv1d layers of widths dims[0..n_layers];
+ * bit l of res_mask = layer l sees cat(y, feature) (zero under no_residual, SurfaceClassifier.py:57-66).  Supported:
+ * 1 <= n_layers <= 8, dims[0] = 321 (lr) / 322 (hr), dims[n_layers] = 1, hidden widths 1..2048, res_mask < 2^n_layers. */
+typedef struct SursMlpShape {
+    int n_layers;
+    int dims[9];
+    unsigned res_mask;
+} SursMlpShape;
+
+/* HOST: pack both classifiers (w[l] = Conv1d weight [out][in], b[l] = bias, l < n_layers) into the blob of the fused evaluator
+ * (csrc/surs_mlp_generic.h: per layer one f16 part, two f16 parts and three bf16 parts, zero-padded to the MFMA tile, fp32 bias).
+ * blob == NULL: returns the size in bytes.  Returns 0 for an unsupported pair (surs_last_error names the limit). */
+size_t surs_mlp_pack_generic(const SursMlpShape *lr, const float *const *w_lr, const float *const *b_lr, const SursMlpShape *hr,
+                             const float *const *w_hr, const float *const *b_hr, void *blob);
+
+/* HOST: how the fused evaluator runs this pair: *tile_points points per workgroup, *lds_bytes of LDS per workgroup, and (offsets,
+ * nullable: [2][8][4] = byte offsets of the one-part, two-part, three-part images and the bias of classifier m, layer l) the blob
+ * layout.  The fused kernel needs no device workspace. */
+int surs_mlp_generic_info(const SursMlpShape *lr, const SursMlpShape *hr, int *tile_points, int *lds_bytes,
+                          unsigned long long *offsets);
+
+/* query_mr + query_sr + get_preds (lib/model/SuRSNet.py:131-187) for classifiers of any supported shape, in ONE launch per call:
+ * projection, in-image mask, z_feat, bilinear gather, mlp_lr, masked sigmoid, mlp_hr, masked sigmoid per tile of points, the
+ * activations in LDS.  Arguments as surs_query_points, plus the shapes and the blob of surs_mlp_pack_generic.  p_lr non-NULL: the hr
+ * classifier alone, fed with p_lr [n] (query_sr on other points); pred_lr / logit_lr are then ignored.  Operand split as
+ * surs_query_points: surs_set_operand_split_local (1 = one f16 product, 2 = two f16 parts, 3 = three bf16 parts) or the process
+ * setting.  logit_* nullable (pre-sigmoid, pre-mask). */
+int surs_query_points_generic(const float *points, int n, const float *calib, float zmul, float zdiv, const float *feat_lr, int hl,
+                              int wl, const float *feat_hr, int hh, int wh, const SursMlpShape *lr, const SursMlpShape *hr,
+                              const void *blob, const float *p_lr, float *pred_hr, float *pred_lr, float *logit_hr,
+                              float *logit_lr, void *stream);
+
+/* The dense sweep (create_grid + eval_grid + eval_func, lib/sdf.py:4-52, lib/mesh_util.py:16-34) of grid slab [i0, i1) with the
+ * fused evaluator: voxel coordinates made in the kernel in float64 from `mat` (HOST, rows 0..2 of the grid matrix) and cast to
+ * float32, as create_grid does.  vol_hr / vol_lr [(i1-i0)][ry][rz]. */
+int surs_query_grid_generic(int i0, int i1, int ry, int rz, const double *mat, const float *calib, float zmul, float zdiv,
+                            const float *feat_lr, int hl, int wl, const float *feat_hr, int hh, int wh, const SursMlpShape *lr,
+                            const SursMlpShape *hr, const void *blob, float *vol_hr, float *vol_lr, void *stream);
+
 /* surs_query_points for point arrays that come as RUNS of equal (x, y): what the reference's dense sweep loop hands
  * query_mr / query_sr - 50 000 consecutive points of the flattened grid per call, z fastest (lib/sdf.py:32-45 batch_eval,
  * lib/mesh_util.py:20-28 eval_func) - i.e. ~ 98 columns of up to 512 points with one image position each.  Such a run is a column of

@@ -80,7 +80,13 @@ class McCounts(C.Structure):
     _fields_ = [("n_verts", C.c_int32), ("n_faces", C.c_int32), ("vmin", C.c_float), ("vmax", C.c_float)]
 
 
+class MlpShape(C.Structure):
+    """SursMlpShape of include/surs.h: one SurfaceClassifier's widths and skip layers."""
+    _fields_ = [("n_layers", C.c_int), ("dims", C.c_int * 9), ("res_mask", C.c_uint)]
+
+
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
+_shp = C.POINTER(MlpShape)
 _SIGS = {
     "surs_abi_version": (C.c_int, []),
     "surs_last_error": (C.c_char_p, []),
@@ -121,6 +127,11 @@ _SIGS = {
     "surs_encoder_filter_hr": (C.c_int, [C.POINTER(EncoderNet), _vp, _i, _i, _i, _vp, _vp]),
     "surs_encoder_forward": (C.c_int, [C.POINTER(EncoderNet), _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(EncoderStreams), _vp]),
     "surs_mlp_pack": (_sz, [_vp, _vp, _vp, _vp, _i, _vp]),
+    "surs_mlp_pack_generic": (_sz, [_shp, _vp, _vp, _shp, _vp, _vp, _vp]),
+    "surs_mlp_generic_info": (C.c_int, [_shp, _shp, C.POINTER(C.c_int), C.POINTER(C.c_int), _vp]),
+    "surs_query_points_generic": (C.c_int, [_vp, _i, _vp, _f, _f, _vp, _i, _i, _vp, _i, _i, _shp, _shp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                            _vp]),
+    "surs_query_grid_generic": (C.c_int, [_i, _i, _i, _i, _vp, _vp, _f, _f, _vp, _i, _i, _vp, _i, _i, _shp, _shp, _vp, _vp, _vp, _vp]),
     "surs_set_operand_split": (C.c_int, [_i]),
     "surs_set_operand_split_local": (C.c_int, [_i]),
     "surs_set_grid_kernel": (C.c_int, [_i]),

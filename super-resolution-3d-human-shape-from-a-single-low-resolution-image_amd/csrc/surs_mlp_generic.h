@@ -1,0 +1,107 @@
+// Blob layout of SurfaceClassifier pairs of any supported shape (surs_mlp_pack_generic, the fused kernel of surs_mlp_fused.inc).
+// The released shape keeps its own layout (surs_mlp_layout.h); this one is built from the runtime shape descriptors
+// SursMlpShape (include/surs.h), mirroring lib/model/SurfaceClassifier.py:7-43 and SuRSNet.py:67-78.
+//
+// Per classifier m (0 = lr, 1 = hr) and layer l, input = [ y (k1 = dims[l] rows) | feature (dims[0] rows, skip layers only) ]:
+//   k1pad = dims[l] padded to GEN_KT, k2pad = GEN_C0PAD for a skip layer (else 0), mpad = dims[l + 1] padded to GEN_KT
+//   (the output rows are the next layer's k rows: padding rows come out of the layer as exact zeros);
+//   w1  one f16 part                  [kt][tile][lane][8] u16
+//   w2  two f16 parts  (hi, lo)       [2][kt][tile][lane][8]
+//   w3  three bf16 parts (sum exact)  [3][kt][tile][lane][8]
+//   bias fp32 [mpad]
+// kt = k step of 32 over [k1pad | k2pad], tile = 16 output rows: the 512 halves of one (kt, tile) are the A fragments of one
+// v_mfma_f32_16x16x32_{f16,bf16} in lane order (lane l: row 16 tile + (l & 15), k = 32 kt + 8 (l >> 4) + j), so a wave-wide
+// 16-byte load is contiguous. Weights outside the reference tensor are zero.
+#pragma once
+#include <cstddef>
+#include <cstring>
+
+#include "../../include/surs.h"
+
+namespace surs {
+
+constexpr int GEN_MAX_LAYERS = 8;
+constexpr int GEN_MAX_WIDTH = 2048;
+constexpr int GEN_KT = 32;       // k per MFMA step (16x16x32)
+constexpr int GEN_MT = 16;       // output rows per MFMA tile
+constexpr int GEN_C0PAD = 352;   // 321 / 322 feature channels padded to GEN_KT
+
+struct GenLayer {
+    int m, mpad, k1, k1pad, k2pad, res;
+    unsigned long long w1, w2, w3, bias;   // byte offsets in the blob
+};
+
+struct GenLayout {
+    int n_layers[2];
+    int max_hidden;        // widest padded hidden layer output (the activation rows a tile keeps in LDS), >= GEN_KT
+    int reserved;
+    GenLayer layer[2][GEN_MAX_LAYERS];
+    unsigned long long total;
+};
+
+inline int gen_pad(int v, int a) { return (v + a - 1) / a * a; }
+
+// 0 if the pair is supported, otherwise a negative number naming the violated limit (gen_shape_error's message).
+inline int gen_shape_check(const SursMlpShape &s, int m) {
+    if (s.n_layers < 1 || s.n_layers > GEN_MAX_LAYERS) return -1;
+    if (s.dims[0] != (m == 0 ? 321 : 322)) return -2;
+    if (s.dims[s.n_layers] != 1) return -3;
+    for (int l = 1; l < s.n_layers; ++l)
+        if (s.dims[l] < 1 || s.dims[l] > GEN_MAX_WIDTH) return -4;
+    if (s.res_mask >> s.n_layers) return -5;
+    return 0;
+}
+
+inline const char *gen_shape_error(int code) {
+    switch (code) {
+    case -1: return "number of layers must be between 1 and 8";
+    case -2: return "input width must be 321 (lr) / 322 (hr)";
+    case -3: return "last width must be 1";
+    case -4: return "hidden widths must be between 1 and 2048";
+    case -5: return "skip layers must be in [0, number of layers)";
+    default: return "unsupported shape";
+    }
+}
+
+// Fills `out` for a supported pair; returns 0, or gen_shape_check's code of the first classifier that is not supported.
+inline int gen_layout(const SursMlpShape &lr, const SursMlpShape &hr, GenLayout &out) {
+    memset(&out, 0, sizeof(out));
+    const SursMlpShape *s[2] = {&lr, &hr};
+    unsigned long long off = 256;   // (room for a copy of the layout's first bytes; offsets stay 256-byte aligned)
+    out.max_hidden = GEN_KT;
+    for (int m = 0; m < 2; ++m) {
+        const int rc = gen_shape_check(*s[m], m);
+        if (rc) return rc;
+        out.n_layers[m] = s[m]->n_layers;
+        for (int l = 0; l < s[m]->n_layers; ++l) {
+            GenLayer &g = out.layer[m][l];
+            g.res = (s[m]->res_mask >> l) & 1u;
+            g.m = s[m]->dims[l + 1];
+            g.mpad = gen_pad(g.m, GEN_KT);
+            g.k1 = s[m]->dims[l];
+            g.k1pad = gen_pad(g.k1, GEN_KT);
+            g.k2pad = g.res ? GEN_C0PAD : 0;
+            const unsigned long long halves = (unsigned long long)(g.k1pad + g.k2pad) * g.mpad;
+            g.w1 = off;
+            off += (halves * 2 + 255) / 256 * 256;
+            g.w2 = off;
+            off += (halves * 4 + 255) / 256 * 256;
+            g.w3 = off;
+            off += (halves * 6 + 255) / 256 * 256;
+            g.bias = off;
+            off += ((unsigned long long)g.mpad * 4 + 255) / 256 * 256;
+            if (l + 1 < s[m]->n_layers && g.mpad > out.max_hidden) out.max_hidden = g.mpad;
+        }
+    }
+    out.total = off;
+    return 0;
+}
+
+// Index (in halves, inside one part) of weight (row o, input k of the concatenated [k1pad | k2pad] input) in the A-fragment image.
+inline size_t gen_frag_index(const GenLayer &g, int o, int k) {
+    const int kt = k / GEN_KT, kk = k % GEN_KT, tile = o / GEN_MT;
+    const int lane = (o % GEN_MT) + 16 * (kk / 8);
+    return (((size_t)kt * (g.mpad / GEN_MT) + tile) * 64 + lane) * 8 + (kk % 8);
+}
+
+}  // namespace surs

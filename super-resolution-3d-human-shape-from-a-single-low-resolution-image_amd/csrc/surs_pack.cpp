@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "surs_common.h"
+#include "surs_mlp_generic.h"
 #include "surs_mlp_layout.h"
 
 namespace surs {
@@ -36,6 +37,21 @@ static float f16_to_f32(uint16_t u) {
     _Float16 h;
     memcpy(&h, &u, 2);
     return (float)h;
+}
+
+// The operand splits of the kernels' SplitKind<NP> (surs_gemm.inc), on the host: two f16 parts (hi = f16(w), lo = f16(w - hi)) and
+// three bf16 parts (each the bf16 rounding of what the previous ones left: hi + mid + lo = w exactly).
+static void split2_f16(float w, uint16_t &hi, uint16_t &lo) {
+    hi = f32_to_f16(w);
+    lo = f32_to_f16(w - f16_to_f32(hi));
+}
+
+static void split3_bf16(float w, uint16_t (&p)[3]) {
+    float rest = w;
+    for (int part = 0; part < 3; ++part) {
+        p[part] = f32_to_bf16(rest);
+        rest -= bf16_to_f32(p[part]);
+    }
 }
 
 static const int kDims[2][6] = {{321, D1, D2, D3, D4, 1}, {322, D1, D2, D3, D4, 1}};
@@ -188,13 +204,10 @@ extern "C" size_t surs_mlp_pack(const float *const w_lr[5], const float *const b
             const size_t per_part = (size_t)kpad * M;
             for (int k = 0; k < kpad; ++k)
                 for (int o = 0; o < M; ++o) {
-                    float rest = wt[(size_t)k * M + o];
                     const size_t idx = ((((size_t)(k / 16) * (M / 32) + o / 32) * 2 + ((k >> 3) & 1)) * 32 + (o & 31)) * 8 + (k & 7);
-                    for (int part = 0; part < 3; ++part) {
-                        const uint16_t u = f32_to_bf16(rest);
-                        out[part * per_part + idx] = u;
-                        rest -= bf16_to_f32(u);
-                    }
+                    uint16_t u[3];
+                    split3_bf16(wt[(size_t)k * M + o], u);
+                    for (int part = 0; part < 3; ++part) out[part * per_part + idx] = u[part];
                 }
         };
         const int mout[4] = {D1, D2, D3, D4};
@@ -210,11 +223,8 @@ extern "C" size_t surs_mlp_pack(const float *const w_lr[5], const float *const b
             const size_t per_part = (size_t)kpad * M;
             for (int k = 0; k < kpad; ++k)
                 for (int o = 0; o < M; ++o) {
-                    const float w = wt[(size_t)k * M + o];
                     const size_t idx = ((((size_t)(k / 16) * (M / 32) + o / 32) * 2 + ((k >> 3) & 1)) * 32 + (o & 31)) * 8 + (k & 7);
-                    const uint16_t hi = f32_to_f16(w);
-                    out[idx] = hi;
-                    out[per_part + idx] = f32_to_f16(w - f16_to_f32(hi));
+                    split2_f16(wt[(size_t)k * M + o], out[idx], out[per_part + idx]);
                 }
         };
         const int mout[4] = {D1, D2, D3, D4};
@@ -287,6 +297,48 @@ extern "C" size_t surs_mlp_pack(const float *const w_lr[5], const float *const b
                 }
     }
     return off;
+}
+
+// Classifiers of any supported shape (csrc/surs_mlp_generic.h): per layer the A-fragment images of the fused evaluator in its three
+// operand forms, zero-padded to the MFMA tile in k and m; a skip layer's feature columns are the k segment behind y's.
+extern "C" size_t surs_mlp_pack_generic(const SursMlpShape *lr, const float *const *w_lr, const float *const *b_lr, const SursMlpShape *hr,
+                                        const float *const *w_hr, const float *const *b_hr, void *blob) {
+    if (!lr || !hr) {
+        fail(SURS_E_INVALID, "null shape");
+        return 0;
+    }
+    GenLayout lay;
+    const int rc = gen_layout(*lr, *hr, lay);
+    if (rc) {
+        fail(SURS_E_INVALID, "unsupported SurfaceClassifier shape (%s): %s", rc == gen_shape_check(*lr, 0) ? "lr" : "hr", gen_shape_error(rc));
+        return 0;
+    }
+    if (!blob) return (size_t)lay.total;
+    char *base = (char *)blob;
+    memset(base, 0, (size_t)lay.total);
+    const SursMlpShape *s[2] = {lr, hr};
+    const float *const *W[2] = {w_lr, w_hr};
+    const float *const *B[2] = {b_lr, b_hr};
+    for (int m = 0; m < 2; ++m)
+        for (int l = 0; l < lay.n_layers[m]; ++l) {
+            const GenLayer &g = lay.layer[m][l];
+            const int c0 = s[m]->dims[0], kin = g.k1 + (g.res ? c0 : 0);   // Conv1d in_channels
+            const size_t per_part = (size_t)(g.k1pad + g.k2pad) * g.mpad;
+            uint16_t *w1 = (uint16_t *)(base + g.w1), *w2 = (uint16_t *)(base + g.w2), *w3 = (uint16_t *)(base + g.w3);
+            for (int o = 0; o < g.m; ++o)
+                for (int k = 0; k < kin; ++k) {
+                    // reference weight row o: [ y part (k1) | feature part (c0) ]; in the image the feature part starts at k1pad
+                    const float w = W[m][l][(size_t)o * kin + k];
+                    const size_t idx = gen_frag_index(g, o, k < g.k1 ? k : g.k1pad + (k - g.k1));
+                    w1[idx] = f32_to_f16(w);
+                    split2_f16(w, w2[idx], w2[per_part + idx]);
+                    uint16_t u[3];
+                    split3_bf16(w, u);
+                    for (int part = 0; part < 3; ++part) w3[part * per_part + idx] = u[part];
+                }
+            memcpy(base + g.bias, B[m][l], (size_t)g.m * 4);
+        }
+    return (size_t)lay.total;
 }
 
 extern "C" size_t surs_conv_pack_weights(const float *w, int cout, int cin, int ksize, float *out) {

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "surs_common.h"
+#include "surs_mlp_generic.h"
 #include "surs_mlp_layout.h"
 
 namespace surs {
@@ -88,6 +89,52 @@ __device__ __forceinline__ void make_point(const PointSource &s, long long t, fl
     }
 }
 
+// orthogonal / perspective projection (lib/geometry.py:15-48) with calib rows 0..2, and the in-image mask of SuRSNet.py:137
+__device__ __forceinline__ void project_point(const PointSource &s, float px, float py, float pz, float &X, float &Y, float &Z) {
+    const float *c = s.calib;
+    X = c[3] + ((c[0] * px + c[1] * py) + c[2] * pz);
+    Y = c[7] + ((c[4] * px + c[5] * py) + c[6] * pz);
+    Z = c[11] + ((c[8] * px + c[9] * py) + c[10] * pz);
+    if (s.persp) {
+        X = X / Z;
+        Y = Y / Z;
+    }
+}
+
+__device__ __forceinline__ float in_image(float X, float Y) {
+    return (X >= -1.0f && X <= 1.0f && Y >= -1.0f && Y <= 1.0f) ? 1.0f : 0.0f;
+}
+
+// grid_sample's bilinear taps (align_corners=True, zeros padding, lib/geometry.py:4-12) of image position (u, v) on an H x W map:
+// pixel indices nw, ne, sw, se (clamped into the map: a tap outside it is loaded from a valid address and weighted with zero -
+// the same sum) and their weights
+__device__ __forceinline__ void bilinear_taps(float u, float v, int H, int W, long long (&pix)[4], float (&w)[4]) {
+    const float ix = ((u + 1.0f) / 2.0f) * (float)(W - 1);
+    const float iy = ((v + 1.0f) / 2.0f) * (float)(H - 1);
+    const float fx = floorf(ix), fy = floorf(iy);
+    const int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
+    const bool vx0 = x0 >= 0 && x0 < W, vx1 = x1 >= 0 && x1 < W, vy0 = y0 >= 0 && y0 < H, vy1 = y1 >= 0 && y1 < H;
+    w[0] = (vy0 && vx0) ? ((float)x1 - ix) * ((float)y1 - iy) : 0.0f;
+    w[1] = (vy0 && vx1) ? (ix - (float)x0) * ((float)y1 - iy) : 0.0f;
+    w[2] = (vy1 && vx0) ? ((float)x1 - ix) * (iy - (float)y0) : 0.0f;
+    w[3] = (vy1 && vx1) ? (ix - (float)x0) * (iy - (float)y0) : 0.0f;
+    const int cx0 = min(max(x0, 0), W - 1), cx1 = min(max(x1, 0), W - 1);
+    const int cy0 = min(max(y0, 0), H - 1), cy1 = min(max(y1, 0), H - 1);
+    pix[0] = (long long)cy0 * W + cx0;
+    pix[1] = (long long)cy0 * W + cx1;
+    pix[2] = (long long)cy1 * W + cx0;
+    pix[3] = (long long)cy1 * W + cx1;
+}
+
+__device__ __forceinline__ float tap_sum(const float (&t)[4], const float (&w)[4]) {
+    float a = 0.0f;   // nw, ne, sw, se in this order, as grid_sample accumulates them
+    a += t[0] * w[0];
+    a += t[1] * w[1];
+    a += t[2] * w[2];
+    a += t[3] * w[3];
+    return a;
+}
+
 // ------------------------------------------------------------------------------------------------
 // split-bf16 operands: x = a + b + c exactly (three bf16 parts of an fp32 value, 24 significant bits), so six bf16 MFMA
 // partial products reproduce the fp32 product sum at 2.7x the fp32 matrix rate (conv_x3_kernel in surs_encoder.hip).
@@ -137,15 +184,9 @@ __global__ __launch_bounds__(256) void gather_kernel(PointSource src, long long 
         if (t < n) {
             float px, py, pz;
             make_point(src, t, px, py, pz);
-            const float *c = src.calib;
-            X = c[3] + ((c[0] * px + c[1] * py) + c[2] * pz);
-            Y = c[7] + ((c[4] * px + c[5] * py) + c[6] * pz);
-            const float Z = c[11] + ((c[8] * px + c[9] * py) + c[10] * pz);
-            if (src.persp) {
-                X = X / Z;
-                Y = Y / Z;
-            }
-            const float in = (X >= -1.0f && X <= 1.0f && Y >= -1.0f && Y <= 1.0f) ? 1.0f : 0.0f;
+            float Z;
+            project_point(src, px, py, pz, X, Y, Z);
+            const float in = in_image(X, Y);
             if (lead) {
                 mask[t] = in;
                 if (zproj) zproj[t] = Z;
@@ -182,33 +223,14 @@ __global__ __launch_bounds__(256) void gather_kernel(PointSource src, long long 
 #pragma unroll
             for (int u4 = 0; u4 < 8; ++u4) {
                 const int p = wave * 16 + q0 + u4;
-                const float u = sx[p], v = sy[p];
-                const float ix = ((u + 1.0f) / 2.0f) * (float)(W - 1);
-                const float iy = ((v + 1.0f) / 2.0f) * (float)(H - 1);
-                const float fx = floorf(ix), fy = floorf(iy);
-                const int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
-                const bool vx0 = x0 >= 0 && x0 < W, vx1 = x1 >= 0 && x1 < W, vy0 = y0 >= 0 && y0 < H, vy1 = y1 >= 0 && y1 < H;
-                w[u4][0] = (vy0 && vx0) ? ((float)x1 - ix) * ((float)y1 - iy) : 0.0f;
-                w[u4][1] = (vy0 && vx1) ? (ix - (float)x0) * ((float)y1 - iy) : 0.0f;
-                w[u4][2] = (vy1 && vx0) ? ((float)x1 - ix) * (iy - (float)y0) : 0.0f;
-                w[u4][3] = (vy1 && vx1) ? (ix - (float)x0) * (iy - (float)y0) : 0.0f;
-                const int cx0 = min(max(x0, 0), W - 1), cx1 = min(max(x1, 0), W - 1);
-                const int cy0 = min(max(y0, 0), H - 1), cy1 = min(max(y1, 0), H - 1);
+                long long pix[4];
+                bilinear_taps(sx[p], sy[p], H, W, pix, w[u4]);
                 const long long ch = c0 + lane;
-                t[u4][0] = feat[((long long)cy0 * W + cx0) * C + ch];
-                t[u4][1] = feat[((long long)cy0 * W + cx1) * C + ch];
-                t[u4][2] = feat[((long long)cy1 * W + cx0) * C + ch];
-                t[u4][3] = feat[((long long)cy1 * W + cx1) * C + ch];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) t[u4][q] = feat[pix[q] * C + ch];
             }
 #pragma unroll
-            for (int u4 = 0; u4 < 8; ++u4) {
-                float a = 0.0f;   // nw, ne, sw, se in this order, as grid_sample accumulates them
-                a += t[u4][0] * w[u4][0];
-                a += t[u4][1] * w[u4][1];
-                a += t[u4][2] * w[u4][2];
-                a += t[u4][3] * w[u4][3];
-                tile[lane][wave * 16 + q0 + u4] = a;
-            }
+            for (int u4 = 0; u4 < 8; ++u4) tile[lane][wave * 16 + q0 + u4] = tap_sum(t[u4], w[u4]);
         }
         __syncthreads();
         const int cbase = is_hr ? C_LR : chunk * 64;
@@ -2310,3 +2332,5 @@ extern "C" int surs_query_points_columns(const float *points, long long ld, int 
     *columns = (int)ncols;
     return 0;
 }
+
+#include "surs_mlp_fused.inc"

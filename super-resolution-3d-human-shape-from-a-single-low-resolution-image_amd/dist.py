@@ -427,6 +427,8 @@ def reconstruction_sharded_once(opt, net, calib_tensor, resolution, b_min, b_max
     fl, fh = net.features()
     zmul, zdiv = net._zscale()
     prec = "fp32x" if wide else getattr(opt, "precision", "fp32")
+    if net.generic_mlp() is not None:
+        raise NotImplementedError("slab / sharded sweeps: classifiers of the released shape only")
     blob = net._mlp_blob()
     ws = net._workspace()
     dev = blob.device

@@ -18,8 +18,61 @@ from . import native, settings
 from .sdf import create_grid
 
 
+GENERIC_SLAB_POINTS = 1 << 21   # voxels per launch of the fused evaluator's dense sweep (whole axis-0 planes)
+
+
+def _no_generic_views(net):
+    if net.generic_mlp() is not None:
+        raise NotImplementedError("classifiers of a shape other than the released one: single-view orthogonal models only")
+
+
+def eval_volumes_generic(opt, net, calib_tensor, resolution, b_min, b_max, transform=None, i0=0, i1=None, precision=None,
+                         features=None):
+    """eval_volumes for classifiers of any supported shape: the fused evaluator (surs_query_grid_generic) over grid slab [i0, i1),
+    GENERIC_SLAB_POINTS voxels per launch; --precision bf16 | fp16: one f16 product per MAC, fp32: fp32-grade."""
+    R = int(resolution)
+    _, mat = create_grid(R, R, R, b_min, b_max, transform=transform)
+    i1 = R if i1 is None else i1
+    calib = calib_tensor[0].detach().to("cpu", torch.float32).numpy().reshape(-1)[:12]
+    fl, fh = features if features is not None else net.features()
+    zmul, zdiv = net._zscale()
+    g = net.generic_mlp()
+    prec = precision or getattr(opt, "precision", "fp32")
+    vh = torch.empty((i1 - i0, R, R), dtype=torch.float32, device=g.blob.device)
+    vl = torch.empty_like(vh)
+    planes = max(1, GENERIC_SLAB_POINTS // (R * R))
+    with native.reduced_point_operands(prec in ("bf16", "fp16")):
+        for a in range(i0, i1, planes):
+            b = min(i1, a + planes)
+            native.query_grid_generic(a, b, R, R, mat[:3].reshape(-1), calib, zmul, zdiv, fl, fh, g, vh[a - i0:b - i0], vl[a - i0:b - i0])
+    return vh, vl, mat
+
+
+def eval_volumes_octree_generic(opt, net, calib_tensor, resolution, b_min, b_max, transform=None, init_resolution=64, features=None):
+    """eval_volumes_octree for classifiers of any supported shape: the device level walk of native.octree_volumes with the fused
+    evaluator on each level's lattice points (fp32-grade, as the released shape's octree levels)."""
+    R = int(resolution)
+    _, mat = create_grid(R, R, R, b_min, b_max, transform=transform)
+    calib = calib_tensor[0].detach().to("cpu", torch.float32).numpy().reshape(-1)[:12]
+    fl, fh = features if features is not None else net.features()
+    zmul, zdiv = net._zscale()
+    g = net.generic_mlp()
+    dev = g.blob.device
+    M = torch.from_numpy(np.asarray(mat, np.float64)).to(dev)
+
+    def evaluate(idx):
+        return native.query_points_generic(_grid_points(M, idx, R).contiguous(), calib, zmul, zdiv, fl, fh, g)
+
+    vh, vl = native.octree_volumes(R, mat[:3].reshape(-1), None, 0.0, 1.0, None, None, None, net._workspace(), opt.threshold,
+                                   init_resolution, evaluate=evaluate, device=dev)
+    return vh, vl, mat
+
+
 def eval_volumes(opt, net, calib_tensor, resolution, b_min, b_max, transform=None, i0=0, i1=None, precision=None, features=None):
     """Dense occupancy volumes of grid slab [i0, i1) as float32 device tensors (vol_hr, vol_lr), and the grid matrix."""
+    if net.generic_mlp() is not None:
+        return eval_volumes_generic(opt, net, calib_tensor, resolution, b_min, b_max, transform, i0, i1,
+                                    None if precision == "fp32x" else precision, features)
     _, mat = create_grid(resolution, resolution, resolution, b_min, b_max, transform=transform)
     i1 = resolution if i1 is None else i1
     calib = calib_tensor[0].detach().to("cpu", torch.float32).numpy().reshape(-1)[:12]
@@ -52,6 +105,7 @@ def eval_volumes_views(opt, net, calib_tensor, resolution, b_min, b_max, transfo
     One library call (surs_query_grid_views: the voxels generated in the gather, the feature maps laid out once); loop=True - and the
     retry on three bf16 parts after an f16 overflow - walks the batches through the facade as the reference does (same kernels, same bits:
     tests/test_gpu_model.py)."""
+    _no_generic_views(net)
     _, mat = create_grid(resolution, resolution, resolution, b_min, b_max, transform=transform)
     dev = net._device()
     R = int(resolution)
@@ -90,6 +144,7 @@ def eval_volumes_octree_views(opt, net, calib_tensor, resolution, b_min, b_max, 
     """eval_grid_octree for num_views > 1 / the perspective projection: the same level walk on the device (selection,
     scatter and cell pass are the single-view kernels - they only see the two fields), the lattice points evaluated by
     eval_func's multi-view recipe (lib/mesh_util.py:20-28: points repeated per view, query_mr + query_sr, view 0 kept)."""
+    _no_generic_views(net)
     R = int(resolution)
     _, mat = create_grid(R, R, R, b_min, b_max, transform=transform)
     dev = net._device()
@@ -110,6 +165,8 @@ def eval_volumes_octree_views(opt, net, calib_tensor, resolution, b_min, b_max, 
 
 def eval_volumes_octree(opt, net, calib_tensor, resolution, b_min, b_max, transform=None, init_resolution=64, features=None):
     """eval_grid_octree: float64 device volumes (sdf_hr, sdf_lr) and the grid matrix."""
+    if net.generic_mlp() is not None:
+        return eval_volumes_octree_generic(opt, net, calib_tensor, resolution, b_min, b_max, transform, init_resolution, features)
     _, mat = create_grid(resolution, resolution, resolution, b_min, b_max, transform=transform)
     calib = calib_tensor[0].detach().to("cpu", torch.float32).numpy().reshape(-1)[:12]
     fl, fh = features if features is not None else net.features()
@@ -187,11 +244,12 @@ def reconstruction_streamed(opt, net, calib_tensor, resolution, b_min, b_max, tr
     (whole axis-0 planes) per launch; after every launch the cell layers that have become final are extracted
     (surs_mc_lewiner_range: Lewiner's sweep has axis 0 outermost, so their vertex / face numbers are final too) and their
     vertices and faces travel to the host under the next launches.  Same outputs as eval_volumes + meshes_from_volumes.
-    Returns None if it cannot run (first extraction of this workspace: no buffer sizes yet; multi-view; octree).
+    Returns None if it cannot run (first extraction of this workspace: no buffer sizes yet; multi-view; octree; classifiers of
+    a shape other than the released one - the dense branch of reconstruction() takes those).
     features: (Img feat_lr, Img feat_hr) instead of the model's current ones; after_enqueue: called once the whole sweep is
     enqueued and before the host starts driving the extraction (gen_mesh_pipelined enqueues the next subject's encoder there)."""
     ws = net._workspace()
-    if ws.mc_capacity.get(0) is None or ws.mc_capacity.get(1) is None or net.num_views != 1:
+    if ws.mc_capacity.get(0) is None or ws.mc_capacity.get(1) is None or net.num_views != 1 or net.generic_mlp() is not None:
         return None
     R = int(resolution)
     _, mat = create_grid(R, R, R, b_min, b_max, transform=transform)

@@ -55,6 +55,7 @@ class SuRSNet:
         self._sd = OrderedDict((k, torch.from_numpy(v)) for k, v in weights.synthetic_state_dict(opt, seed=0).items())
         self._enc = None
         self._blob = None
+        self._generic = None
         self._ws = None
         self.im_feat_list_lr = []
         self.im_feat_list_hr = []
@@ -134,9 +135,22 @@ class SuRSNet:
 
     def _mlp_blob(self):
         if self._blob is None:
-            self._blob, self._core_dtype = native.pack_mlp({k: v.numpy() for k, v in self._sd.items() if k.startswith("mlp_")},
-                                                           self.precision, self._device())
+            sd = {k: v.numpy() for k, v in self._sd.items() if k.startswith("mlp_")}
+            shapes = native.mlp_shapes(sd, self.opt)
+            if native.is_default_mlp(shapes):
+                self._generic = None
+                self._blob, self._core_dtype = native.pack_mlp(sd, self.precision, self._device())
+            else:
+                # any other --mlp_dim_* / --mlp_res_layers_* / --no_residual: the fused evaluator (surs_query_points_generic)
+                self._generic = native.pack_mlp_generic(sd, self._device(), shapes)
+                self._blob = self._generic.blob
+                self._core_dtype = native.DTYPES["bf16" if self.precision == "fp32" else self.precision]
         return self._blob
+
+    def generic_mlp(self):
+        """The packed classifiers (native.GenericMlp) when their shape is not the released one, else None."""
+        self._mlp_blob()
+        return self._generic
 
     def _workspace(self):
         if self._ws is None:
@@ -289,6 +303,26 @@ class SuRSNet:
         dev = self._device()
         zmul, zdiv = self._zscale()
         V = self.num_views
+        g = self.generic_mlp()
+        if g is not None and not (V == 1 and self.projection_mode == "orthogonal"):
+            raise NotImplementedError("classifiers of a shape other than the released one: single-view orthogonal models only")
+        if g is not None:
+            # the fused evaluator, one launch per image of the batch; --precision bf16 | fp16: one f16 product per MAC
+            B = points.shape[0]
+            if calibs.shape[0] != B:
+                raise ValueError("points [%d,3,N] and calibs [%d,4,4] disagree" % (B, calibs.shape[0]))
+            cal = self._calib_rows(calibs, transforms)
+            outs = []
+            for b in range(B):
+                pts = points[b].to(dev, torch.float32).contiguous()
+                pl = None if p_lr is None else p_lr[b].to(dev, torch.float32).reshape(-1).contiguous()
+                run = lambda: native.query_points_generic(pts, cal[b], zmul, zdiv, *self.features(b), g, p_lr=pl)
+                with native.reduced_point_operands(self.precision in ("bf16", "fp16")):
+                    first = run()
+                outs.append(self._finite_or_wide(run, b, first=first))
+            if B == 1:
+                return outs[0][0].view(1, 1, -1), outs[0][1].view(1, 1, -1)
+            return torch.stack([o[0] for o in outs]).view(B, 1, -1), torch.stack([o[1] for o in outs]).view(B, 1, -1)
         if V == 1 and self.projection_mode == "orthogonal":
             # a batch of B subjects (one image each): image b's features serve points[b] (geometry.index pairs them the same way)
             B = points.shape[0]

@@ -331,8 +331,8 @@ def pack_mlp(sd, dtype, device):
         for l, s in enumerate(shapes):
             got = tuple(np.asarray(sd[prefix + "conv%d.weight" % l]).shape[:2])
             if got != s:
-                raise ValueError("unsupported SurfaceClassifier shape %s%d: %s (the kernels are built for the "
-                                 "reference's default mlp_dim / res_layers)" % (prefix, l, got))
+                raise ValueError("SurfaceClassifier shape %s%d: %s is not the released shape these kernels are built for: "
+                                 "pack it with pack_mlp_generic (mlp_shapes gives the supported limits)" % (prefix, l, got))
     wl, bl = arrs("mlp_lr.")
     wh, bh = arrs("mlp_hr.")
     code = DTYPES[dtype] if isinstance(dtype, str) else dtype
@@ -341,6 +341,156 @@ def pack_mlp(sd, dtype, device):
     host = np.zeros(n, np.uint8)
     lib().surs_mlp_pack(wl, bl, wh, bh, core, host.ctypes.data_as(C.c_void_p))
     return torch.from_numpy(host).to(device), core
+
+
+DEFAULT_MLP_SHAPES = (((321, 1024, 512, 256, 128, 1), (2, 3, 4)), ((322, 1024, 512, 256, 128, 1), (2, 3, 4)))
+MLP_MAX_LAYERS, MLP_MAX_WIDTH = 8, 2048
+
+
+def mlp_shapes(sd, opt=None):
+    """((dims_lr, res_lr), (dims_hr, res_hr)) of the two SurfaceClassifiers in state dict `sd`, derived from the weight tensors
+    (lib/model/SurfaceClassifier.py:7-43: layer l sees dims[l] channels, plus dims[0] when l is a skip layer) and cross-checked
+    against opt's --mlp_dim_* / --mlp_res_layers_* / --no_residual when opt is given.  Raises ValueError naming the limit for
+    anything the evaluators do not support: 1..8 layers, input width 321 (lr) / 322 (hr) - fixed by the encoder -, last width 1,
+    hidden widths 1..2048, skip layers in [0, L)."""
+    out = []
+    for m, (prefix, c0) in enumerate((("mlp_lr.", 321), ("mlp_hr.", 322))):
+        L = 0
+        while prefix + "conv%d.weight" % L in sd:
+            L += 1
+        if not 1 <= L <= MLP_MAX_LAYERS:
+            raise ValueError("%s: %d layers; the number of layers must be between 1 and %d" % (prefix[:-1], L, MLP_MAX_LAYERS))
+        dims, res = [], []
+        for l in range(L):
+            w = np.asarray(sd[prefix + "conv%d.weight" % l])
+            cout, cin = int(w.shape[0]), int(w.shape[1])
+            if l == 0:
+                if cin not in (c0, 2 * c0):
+                    raise ValueError("%s: input width %d; it must be %d (256 + 64 + z%s), or %d with a skip at layer 0"
+                                     % (prefix[:-1], cin, c0, "" if m == 0 else " + p_lr", 2 * c0))
+                dims.append(c0)
+            if cin - dims[l] == c0:
+                res.append(l)
+            elif cin != dims[l]:
+                raise ValueError("%s.conv%d: %d input channels fit neither %d nor %d + %d" % (prefix[:-1], l, cin, dims[l], dims[l], c0))
+            dims.append(cout)
+        if dims[-1] != 1:
+            raise ValueError("%s: last width %d; it must be 1" % (prefix[:-1], dims[-1]))
+        for d in dims[1:-1]:
+            if not 1 <= d <= MLP_MAX_WIDTH:
+                raise ValueError("%s: hidden width %d; hidden widths must be between 1 and %d" % (prefix[:-1], d, MLP_MAX_WIDTH))
+        if opt is not None:
+            want_dims = [int(v) for v in (opt.mlp_dim_lr if m == 0 else opt.mlp_dim_hr)]
+            want_res = [] if opt.no_residual else sorted(set(int(v) for v in (opt.mlp_res_layers_lr if m == 0 else opt.mlp_res_layers_hr)))
+            if any(r < 0 or r >= len(want_dims) - 1 for r in want_res):
+                raise ValueError("%s: skip layers %s; they must be in [0, %d)" % (prefix[:-1], want_res, len(want_dims) - 1))
+            if want_dims != dims or want_res != res:
+                raise ValueError("%s: the weights describe dims %s, skips %s; the options say dims %s, skips %s"
+                                 % (prefix[:-1], dims, res, want_dims, want_res))
+        out.append((tuple(dims), tuple(res)))
+    return tuple(out)
+
+
+def is_default_mlp(shapes):
+    return tuple(shapes) == DEFAULT_MLP_SHAPES
+
+
+class GenericMlp:
+    """A classifier pair of any supported shape packed for the fused evaluator (surs_mlp_pack_generic): device blob + shapes."""
+
+    def __init__(self, blob, shapes):
+        self.blob, self.shapes = blob, shapes
+        self.lr, self.hr = (_shape_struct(*s) for s in shapes)
+
+    def info(self):
+        return mlp_generic_info(self.shapes)
+
+
+def mlp_generic_info(shapes):
+    """(points per tile, LDS bytes per workgroup, blob offsets [2,8,4] of the one-, two-, three-part images and the bias of each
+    layer) of surs_mlp_generic_info: how the fused evaluator runs this pair (host only)."""
+    lr, hr = (_shape_struct(*s) for s in shapes)
+    tp, lds = C.c_int(0), C.c_int(0)
+    off = np.zeros((2, 8, 4), np.uint64)
+    check(lib().surs_mlp_generic_info(C.byref(lr), C.byref(hr), C.byref(tp), C.byref(lds), off.ctypes.data_as(C.c_void_p)))
+    return tp.value, lds.value, off
+
+
+def _shape_struct(dims, res):
+    s = _lib.MlpShape()
+    s.n_layers = len(dims) - 1
+    for i, d in enumerate(dims):
+        s.dims[i] = int(d)
+    s.res_mask = sum(1 << int(r) for r in res)
+    return s
+
+
+def pack_mlp_generic_host(sd, shapes=None):
+    """surs_mlp_pack_generic into a numpy uint8 array: (host blob, shapes)."""
+    shapes = mlp_shapes(sd) if shapes is None else shapes
+    keep, args = [], []
+    for m, prefix in enumerate(("mlp_lr.", "mlp_hr.")):
+        L = len(shapes[m][0]) - 1
+        ws, bs = (C.c_void_p * L)(), (C.c_void_p * L)()
+        for l in range(L):
+            w = np.ascontiguousarray(np.asarray(sd[prefix + "conv%d.weight" % l], np.float32).reshape(shapes[m][0][l + 1], -1))
+            b = np.ascontiguousarray(np.asarray(sd[prefix + "conv%d.bias" % l], np.float32))
+            keep.extend([w, b])
+            ws[l], bs[l] = w.ctypes.data, b.ctypes.data
+        args.append((_shape_struct(*shapes[m]), ws, bs))
+    (sl, wl, bl), (sh, wh, bh) = args
+    n = lib().surs_mlp_pack_generic(C.byref(sl), wl, bl, C.byref(sh), wh, bh, None)
+    if n == 0:
+        raise ValueError(lib().surs_last_error().decode())
+    host = np.zeros(n, np.uint8)
+    lib().surs_mlp_pack_generic(C.byref(sl), wl, bl, C.byref(sh), wh, bh, host.ctypes.data_as(C.c_void_p))
+    return host, shapes
+
+
+def pack_mlp_generic(sd, device, shapes=None):
+    """Pack mlp_lr / mlp_hr of any supported shape for the fused evaluator: a GenericMlp on `device`."""
+    host, shapes = pack_mlp_generic_host(sd, shapes)
+    return GenericMlp(torch.from_numpy(host).to(device), shapes)
+
+
+def query_points_generic(points, calib, zmul, zdiv, feat_lr, feat_hr, g, p_lr=None, want_logits=False):
+    """surs_query_points_generic: both classifiers of GenericMlp g on points [3,N] in one launch (p_lr [N] given: the hr classifier
+    alone).  Returns (pred_hr, pred_lr[, logit_hr, logit_lr]); with p_lr, pred_lr is p_lr and logit_lr None."""
+    points = _f32c(points)
+    n = points.shape[1]
+    dev = points.device
+    phr = torch.empty(n, dtype=torch.float32, device=dev)
+    if p_lr is not None:
+        p_lr = _f32c(p_lr.reshape(-1))
+        assert p_lr.numel() == n
+        plr = p_lr
+    else:
+        plr = torch.empty(n, dtype=torch.float32, device=dev)
+    lg = [torch.empty(n, dtype=torch.float32, device=dev) if want_logits else None for _ in range(2)]
+    if p_lr is not None:
+        lg[1] = None
+    cal = (C.c_float * 12)(*[float(v) for v in calib])
+    assert feat_lr.ld == feat_lr.c == 256 and feat_hr.ld == feat_hr.c == 64
+    check(lib().surs_query_points_generic(_ptr(points), n, cal, float(zmul), float(zdiv), feat_lr.ptr(), feat_lr.h, feat_lr.w,
+                                          feat_hr.ptr(), feat_hr.h, feat_hr.w, C.byref(g.lr), C.byref(g.hr), _ptr(g.blob), _ptr(p_lr),
+                                          _ptr(phr), None if p_lr is not None else _ptr(plr), _ptr(lg[0]), _ptr(lg[1]), _stream()))
+    return (phr, plr, lg[0], lg[1]) if want_logits else (phr, plr)
+
+
+def query_grid_generic(i0, i1, ry, rz, mat, calib, zmul, zdiv, feat_lr, feat_hr, g, vol_hr=None, vol_lr=None):
+    """surs_query_grid_generic: the dense sweep of grid slab [i0, i1) with the fused evaluator.  Returns (vol_hr, vol_lr) float32
+    device tensors [(i1-i0), ry, rz]."""
+    dev = g.blob.device
+    if vol_hr is None:
+        vol_hr = torch.empty((i1 - i0, ry, rz), dtype=torch.float32, device=dev)
+        vol_lr = torch.empty_like(vol_hr)
+    m = (C.c_double * 12)(*[float(v) for v in np.asarray(mat, np.float64).reshape(-1)[:12]])
+    cal = (C.c_float * 12)(*[float(v) for v in calib])
+    assert feat_lr.ld == feat_lr.c == 256 and feat_hr.ld == feat_hr.c == 64
+    check(lib().surs_query_grid_generic(i0, i1, ry, rz, m, cal, float(zmul), float(zdiv), feat_lr.ptr(), feat_lr.h, feat_lr.w,
+                                        feat_hr.ptr(), feat_hr.h, feat_hr.w, C.byref(g.lr), C.byref(g.hr), _ptr(g.blob), _ptr(vol_hr),
+                                        _ptr(vol_lr), _stream()))
+    return vol_hr, vol_lr
 
 
 class Workspace:
