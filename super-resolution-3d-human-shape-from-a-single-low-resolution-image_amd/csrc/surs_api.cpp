@@ -33,10 +33,7 @@ struct OptionRow {
 };
 // (order = enum Opt of surs_common.h)
 const OptionRow kOptions[surs::OPT_COUNT] = {
-    {"gemm_x3", "SURS_GEMM_X3", 1, 0, 0, "0: the point path's layer GEMMs on the fp32 MFMA kernel (A/B)"},
-    {"gemm_big", "SURS_GEMM_BIG", 1, 0, 0, "0: the 128 x 128 layer kernel for every layer (A/B)"},
     {"split_parts", "SURS_SPLIT", 2, 'b', 3, "operand parts of the fp32-grade GEMMs: 2 (f16 x 2) or 3 (bf16 x 3; env: bf16x3)"},
-    {"gemm_waves", "SURS_GEMM_WAVES", 8, 0, 0, "waves per workgroup of the 256-point layer kernel: 8 or 16"},
     {"grid_f32_columns", "SURS_GRID_F32", 1, 'g', 0, "0 (env: gemm): the fp32 sweep on the per-point layer kernels"},
     {"grid_kernel", "SURS_GRID_KERNEL", 0, 0, 0, "reduced-precision column kernel: 0 (default 12), 3, 10, 12"},
     {"grid_f32_kernel", "SURS_GRID_F32_KERNEL", 0, 0, 0, "fp32-grade column kernel: 0 (default 11), 5, 11"},
@@ -46,7 +43,6 @@ const OptionRow kOptions[surs::OPT_COUNT] = {
     {"mc_emit_reclassify", "SURS_MC_EMIT_RECLASSIFY", 0, 0, 0, "1: marching cubes' emit pass classifies again (tests)"},
     {"point_runs_speculate", "SURS_POINT_RUNS_SPECULATE", 1, 0, 0, "0: surs_query_points_columns reads the run count before it launches"},
     {"conv_trace", "SURS_CONV_TRACE", 0, 0, 0, "diagnostic builds (-DSURS_CONV_TRACE): print the 3x3 kernel's phase stamps"},
-    {"gemm_trace", "SURS_GEMM_TRACE", 0, 0, 0, "diagnostic builds: print the layer GEMM's stamps"},
     {"v3_trace", "SURS_V3_TRACE", 0, 0, 0, "diagnostic builds (-DSURS_V3_TRACE): print the column kernels' stamps"},
     {"conv_tall_min_wg", "SURS_CONV_TALL_MIN_WG", 256, 0, 0, "workgroups from which a stride-1 3x3 convolution takes the 8-row tile instead of 4 rows (0: never; same bits)"},
     {"conv_wide_min_wg", "SURS_CONV_WIDE_MIN_WG", 512, 0, 0, "workgroups (of 64 channels) from which such a launch takes 8 rows x 64 channels (part of the bits: another order of sums; 0: never)"},

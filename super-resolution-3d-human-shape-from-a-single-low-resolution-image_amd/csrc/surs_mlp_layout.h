@@ -61,7 +61,7 @@ struct MlpBlobHeader {
     uint32_t total_bytes;
     uint32_t core16;  // the same cores as A fragments of the 16x16x32 shape (column kernel v4), same size
     uint32_t b1frag;  // layer-1 biases as 32x32x16 A fragments [2 MLPs][16 row tiles][64 lanes][8] (see B1FRAG_SCALE)
-    // fp32 path on the bf16 matrix pipe (gemm_x3_kernel): the k-major matrices wt[m][l] and wc again, every element as
+    // fp32 path on the bf16 matrix pipe (gemm_x3g_kernel, three parts): the k-major matrices wt[m][l] and wc again, every element as
     // three bf16 parts (hi + mid + lo = the fp32 value exactly), [3 parts][Kpad / 16][M][16] uint16
     uint32_t wt3[2][4];
     uint32_t wc3;

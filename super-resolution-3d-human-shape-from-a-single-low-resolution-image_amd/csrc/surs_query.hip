@@ -9,8 +9,8 @@
 //   create_grid / eval_grid / eval_func   lib/sdf.py:4-52, lib/mesh_util.py:16-34   (grid entry point)
 //
 // Two arithmetic modes:
-//   fp32  (parity mode, any points): gather kernel -> channel-major feature matrix F[336][N]; each MLP layer is
-//         one launch of a 128x128x16 LDS-tiled GEMM on v_mfma_f32_32x32x2_f32 (exact fp32 fmaf chains) with the
+//   fp32  (parity mode, any points): gather kernel -> F[336][N] and its split image; each hidden MLP layer is one
+//         launch of the layer kernel (surs_gemm.inc: 256x256 tiles, operands as two f16 or three bf16 parts) with the
 //         skip-concat done as a second K segment instead of a materialised torch.cat.
 //   bf16/f16 (grid mode): all voxels of a (i,j) column share their 320 gathered features, so the feature part of
 //         layers 0,2,3,4 is a per-column constant (computed in fp32 by the same GEMM, 0.1 % of the work) and
@@ -375,13 +375,12 @@ __global__ __launch_bounds__(256) void mlp_last_views_kernel(const float *__rest
 // host orchestration of the fp32 path
 // ------------------------------------------------------------------------------------------------
 struct Fp32Workspace {
-    float *F, *Y0, *Y1, *Y2, *Y3, *mask;
-    unsigned short *Fs, *Y0s, *Y1s, *Y2s;   // split images (split-bf16 layer kernels); they overlay Y0..Y2
-    long long np;  // padded point count (multiple of 128)
+    float *F, *Y3, *mask;
+    unsigned short *Fs, *Y0s, *Y1s, *Y2s;   // split images of F and of the hidden activations of layers 0-2
+    long long np;  // padded point count (multiple of 256)
 };
 
-// F, Y3 and the mask in fp32; the hidden activations either as split images (6 bytes per value, with the split image of
-// F) or - SURS_GEMM_X3=0 - as fp32 in the same region
+// F, Y3 and the mask in fp32; the split images of F and of the hidden activations (up to three parts: 6 bytes per value)
 static size_t fp32_ws_bytes(long long np) {
     return (size_t)np * ((C0PAD + D4 + 1) * sizeof(float) + (size_t)(C0PAD + D1 + D2 + D3) * 6) + 4096;
 }
@@ -393,9 +392,6 @@ static Fp32Workspace carve_fp32(void *ws, long long np) {
     w.F = p; p += (size_t)C0PAD * np;
     w.Y3 = p; p += (size_t)D4 * np;
     w.mask = p; p += np;
-    w.Y0 = p;
-    w.Y1 = w.Y0 + (size_t)D1 * np;
-    w.Y2 = w.Y1 + (size_t)D2 * np;
     unsigned short *q = (unsigned short *)p;
     w.Fs = q; q += (size_t)3 * C0PAD * np;
     w.Y0s = q; q += (size_t)3 * D1 * np;
@@ -404,44 +400,25 @@ static Fp32Workspace carve_fp32(void *ws, long long np) {
     return w;
 }
 
-// SURS_GEMM_X3=0 in the environment keeps the fp32 MFMA kernel (A/B comparisons)
-static bool gemm_use_x3() { return option(OPT_GEMM_X3) != 0; }
-
-// SURS_GEMM_BIG=0 keeps the 128 x 128 layer kernel for every layer (A/B comparisons)
-static bool gemm_use_big() { return option(OPT_GEMM_BIG) != 0; }
-
-static int launch_gemm(hipStream_t st, bool transposed, const float *Wt, const void *W3, int M, const float *X1, int K1,
-                       long long ld1, const float *X2, int K2, long long ld2, const float *bias, int act, float *Y,
-                       long long ldy, long long np) {
-    const int nblocks = (int)(np / 128);
-    dim3 grid(gemm_grid(M / 128, nblocks));
-    if (W3 && gemm_use_x3()) {
-        const unsigned short *w3 = (const unsigned short *)W3;
-        if (transposed)
-            hipLaunchKernelGGL(gemm_x3_kernel<true>, grid, dim3(256), 0, st, w3, M, K1 + K2, X1, K1, ld1, X2, K2, ld2, bias, act, Y, ldy, nblocks);
-        else
-            hipLaunchKernelGGL(gemm_x3_kernel<false>, grid, dim3(256), 0, st, w3, M, K1 + K2, X1, K1, ld1, X2, K2, ld2, bias, act, Y, ldy, nblocks);
-    } else if (transposed)
-        hipLaunchKernelGGL(gemm_f32_kernel<true>, grid, dim3(256), 0, st, Wt, M, X1, K1, ld1, X2, K2, ld2, bias, act, Y, ldy, nblocks);
-    else
-        hipLaunchKernelGGL(gemm_f32_kernel<false>, grid, dim3(256), 0, st, Wt, M, X1, K1, ld1, X2, K2, ld2, bias, act, Y, ldy, nblocks);
-    SURS_LAUNCH_CHECK();
-    return 0;
-}
-
-// Operand split of the 256-point layer kernels (SplitKind): two f16 parts (default: three products per MAC, 4 bytes per value;
-// |x| < 65504) or, with SURS_SPLIT=bf16x3, three bf16 parts (six products, 6 bytes, fp32's exponent range).  The older layer
-// kernels (SURS_GEMM_BIG=0 / SURS_GEMM_X3=0) only know the bf16 form.
+// Operand split of the layer kernel (SplitKind): two f16 parts (default: three products per MAC, 4 bytes per value;
+// |x| < 65504) or, with SURS_SPLIT=bf16x3, three bf16 parts (six products, 6 bytes, fp32's exponent range).
 static int g_split_override = 0;   // surs_set_operand_split (process-wide)
 static thread_local int t_split_call = 0;   // SursGridOptions::operand_parts of the surs_query_grid_opt call running on this thread
 static int split_parts() {
     const int v = option(OPT_SPLIT_PARTS) == 3 ? 3 : 2;
     // (a thread's 1 = the one-product point path, run_points_fp32 only: everything else that asks here stays fp32-grade)
-    const int want = t_split_call > 1 ? t_split_call : (g_split_override ? g_split_override : v);
-    return (gemm_use_x3() && gemm_use_big()) ? want : 3;
+    return t_split_call > 1 ? t_split_call : (g_split_override ? g_split_override : v);
 }
 
-// the 256-point layer kernels need more than 64 KB of dynamic LDS
+// f(NP) with NP = parts as a compile-time constant, for a kernel instantiated for the listed splits only: parts picks the
+// first equal one, the last one takes any other value
+template <int NP, int... More, class F> static void with_parts(int parts, F &&f) {
+    if constexpr (sizeof...(More) == 0) f(std::integral_constant<int, NP>());
+    else if (parts == NP) f(std::integral_constant<int, NP>());
+    else with_parts<More...>(parts, f);
+}
+
+// the layer kernels need more than 64 KB of dynamic LDS
 static int g3_set_attributes() {
     static DeviceOnce attr;
     if (attr.first()) {
@@ -450,7 +427,6 @@ static int g3_set_attributes() {
         SURS_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_x3g_kernel<8, 128, G3_F32, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, g3_lds_bytes(128, 2)));
         SURS_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_x3g_kernel<8, 128, G3_F32_T, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, g3_lds_bytes(128, 2)));
         SURS_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_x3g_kernel<8, 256, G3_SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, g3_lds_bytes(256)));
-        SURS_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_x3g_kernel<16, 256, G3_SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, g3_lds_bytes(256)));
         SURS_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_x3g_kernel<8, 256, G3_F32>, hipFuncAttributeMaxDynamicSharedMemorySize, g3_lds_bytes(256)));
         SURS_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_x3g_kernel<8, 128, G3_F32>, hipFuncAttributeMaxDynamicSharedMemorySize, g3_lds_bytes(128)));
         SURS_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_x3g_kernel<8, 128, G3_F32_T>, hipFuncAttributeMaxDynamicSharedMemorySize, g3_lds_bytes(128)));
@@ -464,86 +440,34 @@ static int g3_set_attributes() {
     return 0;
 }
 
-static int launch_gemm_s(hipStream_t st, const void *W3, int M, const unsigned short *X1s, int K1, const unsigned short *X2s,
-                         int K2, const float *bias, float *Y, unsigned short *Ys, long long np, int parts = 3) {
-    SplitSeg s1 = {X1s, (long long)K1 * np, K1 / 16}, s2 = {X2s, (long long)K2 * np, K2 / 16};
-    const int nblocks = (int)(np / 128);
-    dim3 grid(gemm_grid(M / 128, nblocks));
-    const unsigned short *w3 = (const unsigned short *)W3;
-    if (parts == 2) {   // two f16 parts: the 256-point kernels only
-        SURS_REQUIRE(np % 256 == 0 && (M % 256 == 0 || !Ys), "f16 x 2 layer kernels need 256-point tiles");
-        int rca = g3_set_attributes();
-        if (rca) return rca;
-        const int nb256 = (int)(np / 256);
-        const long long yp = (long long)M * np;
-        if (Ys)
-            hipLaunchKernelGGL((gemm_x3g_kernel<8, 256, G3_SPLIT, 2>), dim3(gemm_grid(M / 256, nb256)), dim3(512), g3_lds_bytes(256, 2), st,
-                               w3, M, K1 + K2, s1, s2, np, bias, (float *)nullptr, 0LL, Ys, yp, nb256);
-        else if (M % 256 == 0)
-            hipLaunchKernelGGL((gemm_x3g_kernel<8, 256, G3_F32, 2>), dim3(gemm_grid(M / 256, nb256)), dim3(512), g3_lds_bytes(256, 2), st,
-                               w3, M, K1 + K2, s1, s2, np, bias, Y, np, (unsigned short *)nullptr, 0LL, nb256);
-        else
-            hipLaunchKernelGGL((gemm_x3g_kernel<8, 128, G3_F32, 2>), dim3(gemm_grid(M / 128, nb256)), dim3(512), g3_lds_bytes(128, 2), st,
-                               w3, M, K1 + K2, s1, s2, np, bias, Y, np, (unsigned short *)nullptr, 0LL, nb256);
-        SURS_LAUNCH_CHECK();
-        return 0;
-    }
-    if (parts == 1) {   // ONE f16 part per operand (11 significant bits: the reduced-precision point path), same kernels and tiles
-        SURS_REQUIRE(np % 256 == 0 && (M % 256 == 0 || !Ys), "the one-part layer kernels need 256-point tiles");
-        int rca = g3_set_attributes();
-        if (rca) return rca;
-        const int nb256 = (int)(np / 256);
-        const long long yp = (long long)M * np;
-        if (Ys)
-            hipLaunchKernelGGL((gemm_x3g_kernel<8, 256, G3_SPLIT, 1>), dim3(gemm_grid(M / 256, nb256)), dim3(512), g3_lds_bytes(256, 1), st,
-                               w3, M, K1 + K2, s1, s2, np, bias, (float *)nullptr, 0LL, Ys, yp, nb256);
-        else if (M % 256 == 0)
-            hipLaunchKernelGGL((gemm_x3g_kernel<8, 256, G3_F32, 1>), dim3(gemm_grid(M / 256, nb256)), dim3(512), g3_lds_bytes(256, 1), st,
-                               w3, M, K1 + K2, s1, s2, np, bias, Y, np, (unsigned short *)nullptr, 0LL, nb256);
-        else
-            hipLaunchKernelGGL((gemm_x3g_kernel<8, 128, G3_F32, 1>), dim3(gemm_grid(M / 128, nb256)), dim3(512), g3_lds_bytes(128, 1), st,
-                               w3, M, K1 + K2, s1, s2, np, bias, Y, np, (unsigned short *)nullptr, 0LL, nb256);
-        SURS_LAUNCH_CHECK();
-        return 0;
-    }
-    if (np % 256 == 0 && gemm_use_big() && (M % 256 == 0 || !Ys)) {
-        // 256-point tiles: 256 rows per workgroup where M allows, else 128 (fp32 output only: the last hidden layer)
-        int rca = g3_set_attributes();
-        if (rca) return rca;
-        const int nb256 = (int)(np / 256);
-        const int nw = option(OPT_GEMM_WAVES);
-        const long long yp = (long long)M * np;
-        if (Ys && nw == 16)
-            hipLaunchKernelGGL((gemm_x3g_kernel<16, 256, G3_SPLIT>), dim3(gemm_grid(M / 256, nb256)), dim3(1024), g3_lds_bytes(256), st, w3, M,
-                               K1 + K2, s1, s2, np, bias, (float *)nullptr, 0LL, Ys, yp, nb256);
-        else if (Ys)
-            hipLaunchKernelGGL((gemm_x3g_kernel<8, 256, G3_SPLIT>), dim3(gemm_grid(M / 256, nb256)), dim3(512), g3_lds_bytes(256), st, w3, M,
-                               K1 + K2, s1, s2, np, bias, (float *)nullptr, 0LL, Ys, yp, nb256);
-        else if (M % 256 == 0)
-            hipLaunchKernelGGL((gemm_x3g_kernel<8, 256, G3_F32>), dim3(gemm_grid(M / 256, nb256)), dim3(512), g3_lds_bytes(256), st, w3, M,
-                               K1 + K2, s1, s2, np, bias, Y, np, (unsigned short *)nullptr, 0LL, nb256);
-        else
-            hipLaunchKernelGGL((gemm_x3g_kernel<8, 128, G3_F32>), dim3(gemm_grid(M / 128, nb256)), dim3(512), g3_lds_bytes(128), st, w3, M,
-                               K1 + K2, s1, s2, np, bias, Y, np, (unsigned short *)nullptr, 0LL, nb256);
-    } else if (Ys)
-        hipLaunchKernelGGL(gemm_x3s_kernel<true>, grid, dim3(256), 0, st, w3, M, K1 + K2, s1, s2, np, bias, 1, (float *)nullptr,
-                           0LL, Ys, (long long)M * np, nblocks);
-    else
-        hipLaunchKernelGGL(gemm_x3s_kernel<false>, grid, dim3(256), 0, st, w3, M, K1 + K2, s1, s2, np, bias, 1, Y, np,
-                           (unsigned short *)nullptr, 0LL, nblocks);
+// One layer on gemm_x3g_kernel, columns 0 .. n - 1 of split operands np columns wide: W (weight image of `parts` parts, M rows)
+// times segment s1, then s2.  out: G3_SPLIT -> Ys, the next layer's split image (parts M * np halfwords apart); G3_F32 ->
+// Y [M][np]; G3_F32_T -> Y [np][M] (bias only).  256 rows per workgroup where M allows, else 128 (fp32 outputs only).
+static int launch_layer(hipStream_t st, int parts, int out, const void *W, int M, SplitSeg s1, SplitSeg s2, long long np, long long n,
+                        const float *bias, float *Y, unsigned short *Ys) {
+    SURS_REQUIRE(parts >= 1 && parts <= 3, "layer kernel: 1, 2 or 3 operand parts");
+    SURS_REQUIRE(np % 256 == 0 && n % 256 == 0 && n <= np, "the layer kernel needs 256-point tiles");
+    SURS_REQUIRE(M % 256 == 0 || (out != G3_SPLIT && M % 128 == 0), "layer kernel rows: a multiple of 256 (of 128 for an fp32 output)");
+    SURS_REQUIRE(M % 256 == 0 || out != G3_F32_T || parts > 1, "no one-part layer kernel for a transposed output of 128-row tiles");
+    int rc = g3_set_attributes();
+    if (rc) return rc;
+    const int K = 16 * (s1.ktiles + s2.ktiles), nb = (int)(n / 256);
+    const long long ldy = out == G3_F32_T ? M : np;
+    with_parts<1, 2, 3>(parts, [&](auto NP) {
+        auto go = [&](auto BM, auto OUT) {
+            hipLaunchKernelGGL((gemm_x3g_kernel<8, BM, OUT, NP>), dim3(gemm_grid(M / BM, nb)), dim3(512), g3_lds_bytes(BM, NP), st,
+                               (const unsigned short *)W, M, K, s1, s2, np, bias, Y, ldy, Ys, (long long)M * np, nb);
+        };
+        using C256 = std::integral_constant<int, 256>;
+        using C128 = std::integral_constant<int, 128>;
+        if (out == G3_SPLIT) go(C256(), std::integral_constant<int, G3_SPLIT>());
+        else if (out == G3_F32) {
+            if (M % 256 == 0) go(C256(), std::integral_constant<int, G3_F32>());
+            else go(C128(), std::integral_constant<int, G3_F32>());
+        } else if (M % 256 == 0) go(C256(), std::integral_constant<int, G3_F32_T>());
+        else if constexpr (NP > 1) go(C128(), std::integral_constant<int, G3_F32_T>());
+    });
     SURS_LAUNCH_CHECK();
-#ifdef SURS_GEMM_TRACE
-    if (option(OPT_GEMM_TRACE)) {
-        unsigned long long t[64];
-        SURS_HIP_CHECK(hipStreamSynchronize(st));
-        SURS_HIP_CHECK(hipMemcpyFromSymbol(t, HIP_SYMBOL(g_gemm_trace), sizeof(t)));
-        fprintf(stderr, "gemm trace M=%d K=%d np=%lld (issue, mfma, store, barrier+):", M, K1 + K2, np);
-        for (int i = 0; i < 15; ++i)
-            fprintf(stderr, " [%llu %llu %llu %llu]", t[4 * i + 1] - t[4 * i], t[4 * i + 2] - t[4 * i + 1], t[4 * i + 3] - t[4 * i + 2],
-                    t[4 * i + 4] - t[4 * i + 3]);
-        fprintf(stderr, "\n");
-    }
-#endif
     return 0;
 }
 
@@ -553,68 +477,41 @@ static int run_points_fp32(hipStream_t st, const PointSource &src, long long n, 
                            const Fp32Workspace &w, float *pred_hr, float *pred_lr, float *logit_hr, float *logit_lr,
                            int parts = 0, const float *p_lr_in = nullptr) {
     const long long np = w.np;
-    const bool x3 = gemm_use_x3();
     // (the calling thread asked for the one-product point path - surs_set_operand_split_local(1): one f16 part per operand, the
     //  first plane of the two-part weight image; three times less matrix work than the fp32-grade path, 11 significant bits)
-    if (parts == 0) parts = (t_split_call == 1 && x3 && gemm_use_big()) ? 1 : split_parts();
-    unsigned short *Fs = x3 ? w.Fs : nullptr;
+    if (parts == 0) parts = t_split_call == 1 ? 1 : split_parts();
     const long long fs_part = (long long)C0PAD * np;
     // rows 322..335 of F meet zero weights and must be finite: the caller zeroes them once (zero_pad_rows; the split
     // image gets them from gather_kernel); rows < 322 are fully written for t < n; columns n..np-1 only feed outputs
     // that are never read
-    if (parts == 1)
-        hipLaunchKernelGGL(gather_kernel<1>, dim3((unsigned)ceil_div(n, 64)), dim3(256), 0, st, src, n, feat_lr, hl, wl, feat_hr,
-                           hh, wh, w.F, np, w.mask, (float *)nullptr, Fs, fs_part);
-    else if (parts == 2)
-        hipLaunchKernelGGL(gather_kernel<2>, dim3((unsigned)ceil_div(n, 64)), dim3(256), 0, st, src, n, feat_lr, hl, wl, feat_hr,
-                           hh, wh, w.F, np, w.mask, (float *)nullptr, Fs, fs_part);
-    else
-        hipLaunchKernelGGL(gather_kernel<3>, dim3((unsigned)ceil_div(n, 64)), dim3(256), 0, st, src, n, feat_lr, hl, wl, feat_hr,
-                           hh, wh, w.F, np, w.mask, (float *)nullptr, Fs, fs_part);
+    with_parts<1, 2, 3>(parts, [&](auto NP) {
+        hipLaunchKernelGGL(gather_kernel<NP>, dim3((unsigned)ceil_div(n, 64)), dim3(256), 0, st, src, n, feat_lr, hl, wl, feat_hr,
+                           hh, wh, w.F, np, w.mask, (float *)nullptr, w.Fs, fs_part);
+    });
     SURS_LAUNCH_CHECK();
     if (p_lr_in) {   // the hr classifier alone, on the caller's lr occupancies
-        if (parts == 1)
-            hipLaunchKernelGGL(patch_plr_kernel<1>, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, p_lr_in, np, n,
-                               w.F + (size_t)(C_G + 1) * np, Fs, fs_part);
-        else if (parts == 2)
-            hipLaunchKernelGGL(patch_plr_kernel<2>, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, p_lr_in, np, n,
-                               w.F + (size_t)(C_G + 1) * np, Fs, fs_part);
-        else
-            hipLaunchKernelGGL(patch_plr_kernel<3>, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, p_lr_in, np, n,
-                               w.F + (size_t)(C_G + 1) * np, Fs, fs_part);
+        with_parts<1, 2, 3>(parts, [&](auto NP) {
+            hipLaunchKernelGGL(patch_plr_kernel<NP>, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st, p_lr_in, np, n,
+                               w.F + (size_t)(C_G + 1) * np, w.Fs, fs_part);
+        });
         SURS_LAUNCH_CHECK();
     }
+    const SplitSeg none = {nullptr, 0, 0}, f = {w.Fs, fs_part, C0PAD / 16}, y0 = {w.Y0s, (long long)D1 * np, D1 / 16},
+                   y1 = {w.Y1s, (long long)D2 * np, D2 / 16}, y2 = {w.Y2s, (long long)D3 * np, D3 / 16};
     for (int m = p_lr_in ? 1 : 0; m < 2; ++m) {
-        auto WT = [&](int l) { return (const float *)(blob + h.wt[m][l]); };
-        auto W3 = [&](int l) { return (const void *)(blob + (parts <= 2 ? h.wt2[m][l] : h.wt3[m][l])); };   // (one part: the image's first plane, f16(w))
+        auto W = [&](int l) { return (const void *)(blob + (parts <= 2 ? h.wt2[m][l] : h.wt3[m][l])); };   // (one part: the image's first plane, f16(w))
         auto BI = [&](int l) { return (const float *)(blob + h.bias[m][l]); };
         int rc;
-        if (x3) {
-            if ((rc = launch_gemm_s(st, W3(0), D1, Fs, C0PAD, nullptr, 0, BI(0), nullptr, w.Y0s, np, parts))) return rc;
-            if ((rc = launch_gemm_s(st, W3(1), D2, w.Y0s, D1, nullptr, 0, BI(1), nullptr, w.Y1s, np, parts))) return rc;
-            if ((rc = launch_gemm_s(st, W3(2), D3, w.Y1s, D2, Fs, C0PAD, BI(2), nullptr, w.Y2s, np, parts))) return rc;
-            if ((rc = launch_gemm_s(st, W3(3), D4, w.Y2s, D3, Fs, C0PAD, BI(3), w.Y3, nullptr, np, parts))) return rc;
-        } else {
-            if ((rc = launch_gemm(st, false, WT(0), nullptr, D1, w.F, C0PAD, np, nullptr, 0, 0, BI(0), 1, w.Y0, np, np))) return rc;
-            if ((rc = launch_gemm(st, false, WT(1), nullptr, D2, w.Y0, D1, np, nullptr, 0, 0, BI(1), 1, w.Y1, np, np))) return rc;
-            if ((rc = launch_gemm(st, false, WT(2), nullptr, D3, w.Y1, D2, np, w.F, C0PAD, np, BI(2), 1, w.Y2, np, np))) return rc;
-            if ((rc = launch_gemm(st, false, WT(3), nullptr, D4, w.Y2, D3, np, w.F, C0PAD, np, BI(3), 1, w.Y3, np, np))) return rc;
-        }
-        if (parts == 1)
-            hipLaunchKernelGGL(mlp_last_kernel<1>, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st,
+        if ((rc = launch_layer(st, parts, G3_SPLIT, W(0), D1, f, none, np, np, BI(0), nullptr, w.Y0s))) return rc;
+        if ((rc = launch_layer(st, parts, G3_SPLIT, W(1), D2, y0, none, np, np, BI(1), nullptr, w.Y1s))) return rc;
+        if ((rc = launch_layer(st, parts, G3_SPLIT, W(2), D3, y1, f, np, np, BI(2), nullptr, w.Y2s))) return rc;
+        if ((rc = launch_layer(st, parts, G3_F32, W(3), D4, y2, f, np, np, BI(3), w.Y3, nullptr))) return rc;
+        with_parts<1, 2, 3>(parts, [&](auto NP) {
+            hipLaunchKernelGGL(mlp_last_kernel<NP>, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st,
                                (const float *)(blob + h.w4[m]), w.Y3, w.F, np, n, w.mask, m == 0 ? pred_lr : pred_hr,
                                m == 0 ? logit_lr : logit_hr, m == 0 ? w.F + (size_t)(C_G + 1) * np : (float *)nullptr,
-                               m == 0 ? Fs : (unsigned short *)nullptr, fs_part);
-        else if (parts == 2)
-            hipLaunchKernelGGL(mlp_last_kernel<2>, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st,
-                               (const float *)(blob + h.w4[m]), w.Y3, w.F, np, n, w.mask, m == 0 ? pred_lr : pred_hr,
-                               m == 0 ? logit_lr : logit_hr, m == 0 ? w.F + (size_t)(C_G + 1) * np : (float *)nullptr,
-                               m == 0 ? Fs : (unsigned short *)nullptr, fs_part);
-        else
-            hipLaunchKernelGGL(mlp_last_kernel<3>, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st,
-                               (const float *)(blob + h.w4[m]), w.Y3, w.F, np, n, w.mask, m == 0 ? pred_lr : pred_hr,
-                               m == 0 ? logit_lr : logit_hr, m == 0 ? w.F + (size_t)(C_G + 1) * np : (float *)nullptr,
-                               m == 0 ? Fs : (unsigned short *)nullptr, fs_part);
+                               m == 0 ? w.Fs : (unsigned short *)nullptr, fs_part);
+        });
         SURS_LAUNCH_CHECK();
     }
     return 0;
@@ -890,8 +787,8 @@ extern "C" int surs_query_points_hr(const float *points, int n, const float *cal
 // multi-view / perspective queries: SurfaceClassifier.py:70-76, train_util.py:40-51, geometry.py:34-48
 // ------------------------------------------------------------------------------------------------
 static size_t views_ws_bytes(long long np, int nviews) {
-    // per view: F (C0PAD rows), Y2 (D3 rows), mask; shared: Y0, Y1, Y3, mean F, mean Y2
-    // + the split images of the split-bf16 layer kernels: every view's F, Y0, Y1, the two means
+    // per view: F (C0PAD rows), Y2 (D3 rows), mask; shared: D1 + D2 rows (unused), Y3, mean F, mean Y2
+    // + the split images of the layer kernel: every view's F, Y0, Y1, the two means
     return ((size_t)nviews * (C0PAD + D3 + 1) + (D1 + D2 + D4 + C0PAD + D3)) * (size_t)np * sizeof(float) +
            ((size_t)nviews * C0PAD + D1 + D2 + D3 + C0PAD) * (size_t)np * 6 + 4096;
 }
@@ -913,13 +810,11 @@ static int run_points_views(hipStream_t st, const PointSource *srcs, int n, int 
     float *F = p;      p += (size_t)V * C0PAD * np;  // [V][C0PAD][np]
     float *Y2 = p;     p += (size_t)V * D3 * np;     // [V][D3][np]
     float *mask = p;   p += (size_t)V * np;          // [V][np]
-    float *Y0 = p;     p += (size_t)D1 * np;
-    float *Y1 = p;     p += (size_t)D2 * np;
+    p += (size_t)(D1 + D2) * np;                    // (unused)
     float *Y3 = p;     p += (size_t)D4 * np;
     float *Fm = p;     p += (size_t)C0PAD * np;
     float *Y2m = p;    p += (size_t)D3 * np;
     const long long fstride = (long long)C0PAD * np;
-    const bool x3 = gemm_use_x3();
     const int parts = split_parts();
     unsigned short *q = (unsigned short *)p;
     unsigned short *Fs = q;   q += (size_t)V * 3 * fstride;   // [V][parts][C0PAD/16][np][16] (sized for three parts)
@@ -932,34 +827,24 @@ static int run_points_views(hipStream_t st, const PointSource *srcs, int n, int 
         float *Fv = F + (size_t)v * fstride;
         SURS_HIP_CHECK(hipMemsetAsync(Fv + (size_t)(C_G + 2) * np, 0, (size_t)(C0PAD - C_G - 2) * np * sizeof(float), st));
         const PointSource &src = srcs[v];
-        unsigned short *Fsv = x3 ? Fs + (size_t)v * parts * fstride : (unsigned short *)nullptr;
-        if (parts == 2)
-            hipLaunchKernelGGL(gather_kernel<2>, dim3((unsigned)ceil_div(n, 64)), dim3(256), 0, st, src, (long long)n,
+        with_parts<2, 3>(parts, [&](auto NP) {
+            hipLaunchKernelGGL(gather_kernel<NP>, dim3((unsigned)ceil_div(n, 64)), dim3(256), 0, st, src, (long long)n,
                                feat_lr + (size_t)v * hl * wl * C_LR, hl, wl, feat_hr + (size_t)v * hh * wh * C_HR, hh, wh, Fv, np,
-                               mask + (size_t)v * np, (float *)nullptr, Fsv, fstride);
-        else
-            hipLaunchKernelGGL(gather_kernel<3>, dim3((unsigned)ceil_div(n, 64)), dim3(256), 0, st, src, (long long)n,
-                               feat_lr + (size_t)v * hl * wl * C_LR, hl, wl, feat_hr + (size_t)v * hh * wh * C_HR, hh, wh, Fv, np,
-                               mask + (size_t)v * np, (float *)nullptr, Fsv, fstride);
+                               mask + (size_t)v * np, (float *)nullptr, Fs + (size_t)v * parts * fstride, fstride);
+        });
         SURS_LAUNCH_CHECK();
     }
+    const SplitSeg none = {nullptr, 0, 0}, y0 = {Y0s, (long long)D1 * np, D1 / 16}, y1 = {Y1s, (long long)D2 * np, D2 / 16},
+                   y2m = {Y2ms, (long long)D3 * np, D3 / 16}, fm = {Fms, fstride, C0PAD / 16};
     for (int m = 0; m < 2; ++m) {
-        auto WT = [&](int l) { return (const float *)(blob + h.wt[m][l]); };
-        auto W3 = [&](int l) { return (const void *)(blob + (parts == 2 ? h.wt2[m][l] : h.wt3[m][l])); };
+        auto W = [&](int l) { return (const void *)(blob + (parts == 2 ? h.wt2[m][l] : h.wt3[m][l])); };
         auto BI = [&](int l) { return (const float *)(blob + h.bias[m][l]); };
         int rc;
-        for (int v = 0; v < V && x3; ++v) {   // split images between the layers, fp32 out of layer 2 for the mean
-            const unsigned short *Fsv = Fs + (size_t)v * parts * fstride;
-            if ((rc = launch_gemm_s(st, W3(0), D1, Fsv, C0PAD, nullptr, 0, BI(0), nullptr, Y0s, np, parts))) return rc;
-            if ((rc = launch_gemm_s(st, W3(1), D2, Y0s, D1, nullptr, 0, BI(1), nullptr, Y1s, np, parts))) return rc;
-            if ((rc = launch_gemm_s(st, W3(2), D3, Y1s, D2, Fsv, C0PAD, BI(2), Y2 + (size_t)v * D3 * np, nullptr, np, parts))) return rc;
-        }
-        for (int v = 0; v < V && !x3; ++v) {
-            const float *Fv = F + (size_t)v * fstride;
-            if ((rc = launch_gemm(st, false, WT(0), W3(0), D1, Fv, C0PAD, np, nullptr, 0, 0, BI(0), 1, Y0, np, np))) return rc;
-            if ((rc = launch_gemm(st, false, WT(1), W3(1), D2, Y0, D1, np, nullptr, 0, 0, BI(1), 1, Y1, np, np))) return rc;
-            if ((rc = launch_gemm(st, false, WT(2), W3(2), D3, Y1, D2, np, Fv, C0PAD, np, BI(2), 1, Y2 + (size_t)v * D3 * np, np, np)))
-                return rc;
+        for (int v = 0; v < V; ++v) {   // split images between the layers, fp32 out of layer 2 for the mean
+            const SplitSeg fv = {Fs + (size_t)v * parts * fstride, fstride, C0PAD / 16};
+            if ((rc = launch_layer(st, parts, G3_SPLIT, W(0), D1, fv, none, np, np, BI(0), nullptr, Y0s))) return rc;
+            if ((rc = launch_layer(st, parts, G3_SPLIT, W(1), D2, y0, none, np, np, BI(1), nullptr, Y1s))) return rc;
+            if ((rc = launch_layer(st, parts, G3_F32, W(2), D3, y1, fv, np, np, BI(2), Y2 + (size_t)v * D3 * np, nullptr))) return rc;
         }
         // the view mean after layer 2 (index len(filters) // 2) of both the activations and the input features
         const float inv = 1.0f / (float)V;
@@ -969,32 +854,20 @@ static int run_points_views(hipStream_t st, const PointSource *srcs, int n, int 
         hipLaunchKernelGGL(mean_views_kernel, dim3((unsigned)ceil_div(fstride, 256)), dim3(256), 0, st, F, fstride, V, fstride,
                            inv, Fm);
         SURS_LAUNCH_CHECK();
-        if (x3) {
-            if (parts == 2) {
-                hipLaunchKernelGGL(split_rows_kernel<2>, dim3((unsigned)ceil_div(np, 256), D3 / 16), dim3(256), 0, st, Y2m, np, D3 / 16,
-                                   Y2ms, (long long)D3 * np);
-                hipLaunchKernelGGL(split_rows_kernel<2>, dim3((unsigned)ceil_div(np, 256), C0PAD / 16), dim3(256), 0, st, Fm, np,
-                                   C0PAD / 16, Fms, fstride);
-            } else {
-                hipLaunchKernelGGL(split_rows_kernel<3>, dim3((unsigned)ceil_div(np, 256), D3 / 16), dim3(256), 0, st, Y2m, np, D3 / 16,
-                                   Y2ms, (long long)D3 * np);
-                hipLaunchKernelGGL(split_rows_kernel<3>, dim3((unsigned)ceil_div(np, 256), C0PAD / 16), dim3(256), 0, st, Fm, np,
-                                   C0PAD / 16, Fms, fstride);
-            }
-            SURS_LAUNCH_CHECK();
-            if ((rc = launch_gemm_s(st, W3(3), D4, Y2ms, D3, Fms, C0PAD, BI(3), Y3, nullptr, np, parts))) return rc;
-        } else if ((rc = launch_gemm(st, false, WT(3), W3(3), D4, Y2m, D3, np, Fm, C0PAD, np, BI(3), 1, Y3, np, np)))
-            return rc;
-        if (parts == 2)
-            hipLaunchKernelGGL(mlp_last_views_kernel<2>, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st,
+        with_parts<2, 3>(parts, [&](auto NP) {
+            hipLaunchKernelGGL(split_rows_kernel<NP>, dim3((unsigned)ceil_div(np, 256), D3 / 16), dim3(256), 0, st, Y2m, np, D3 / 16,
+                               Y2ms, (long long)D3 * np);
+            hipLaunchKernelGGL(split_rows_kernel<NP>, dim3((unsigned)ceil_div(np, 256), C0PAD / 16), dim3(256), 0, st, Fm, np,
+                               C0PAD / 16, Fms, fstride);
+        });
+        SURS_LAUNCH_CHECK();
+        if ((rc = launch_layer(st, parts, G3_F32, W(3), D4, y2m, fm, np, np, BI(3), Y3, nullptr))) return rc;
+        with_parts<2, 3>(parts, [&](auto NP) {
+            hipLaunchKernelGGL(mlp_last_views_kernel<NP>, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st,
                                (const float *)(blob + h.w4[m]), Y3, Fm, np, (long long)n, V, mask, m == 0 ? pred_lr : pred_hr,
                                m == 0 ? logit_lr : logit_hr, m == 0 ? F + (size_t)(C_G + 1) * np : (float *)nullptr, fstride,
-                               (m == 0 && x3) ? Fs : (unsigned short *)nullptr, fstride);
-        else
-            hipLaunchKernelGGL(mlp_last_views_kernel<3>, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, st,
-                               (const float *)(blob + h.w4[m]), Y3, Fm, np, (long long)n, V, mask, m == 0 ? pred_lr : pred_hr,
-                               m == 0 ? logit_lr : logit_hr, m == 0 ? F + (size_t)(C_G + 1) * np : (float *)nullptr, fstride,
-                               (m == 0 && x3) ? Fs : (unsigned short *)nullptr, fstride);
+                               m == 0 ? Fs : (unsigned short *)nullptr, fstride);
+        });
         SURS_LAUNCH_CHECK();
     }
     return 0;
@@ -1187,43 +1060,23 @@ static int grid_set_attributes() {
 }
 
 // Column constants of a batch of columns (src.mode = 2, src.base = first column): F = gathered features, cmask, and
-// CC[col][2944] = Wc^T F[:, col] + bc - the split-operand layer kernel in its transposed-output form on the split image of F
-// (SURS_GEMM_X3=0 / SURS_GEMM_BIG=0: the older kernels on the fp32 F).  Workspace carved by the caller (col_base_bytes).
+// CC[col][2944] = Wc^T F[:, col] + bc - the layer kernel in its transposed-output form on the split image of F.  Workspace
+// carved by the caller (col_base_bytes).
 static int column_constants(hipStream_t st, const PointSource &src, long long nc, long long ncp, const float *feat_lr, int hl, int wl,
                             const float *feat_hr, int hh, int wh, const char *blob, const MlpBlobHeader &h, float *F, float *CC,
                             float *cmask) {
-    int rc = 0;
-    const bool split = gemm_use_x3() && gemm_use_big();
     const int parts = split_parts();
     unsigned short *Fs = (unsigned short *)(cmask + COL_BATCH);
     const long long fs_part = (long long)C0PAD * COL_BATCH;
     const dim3 gg((unsigned)ceil_div(nc, 64), nc <= 4096 ? 5u : 1u);
-    if (parts == 2)
-        hipLaunchKernelGGL(gather_kernel<2>, gg, dim3(256), 0, st, src, nc, feat_lr, hl, wl,
-                           feat_hr, hh, wh, F, COL_BATCH, cmask, (float *)nullptr, split ? Fs : (unsigned short *)nullptr, fs_part);
-    else
-        hipLaunchKernelGGL(gather_kernel<3>, gg, dim3(256), 0, st, src, nc, feat_lr, hl, wl,
-                           feat_hr, hh, wh, F, COL_BATCH, cmask, (float *)nullptr, split ? Fs : (unsigned short *)nullptr, fs_part);
+    with_parts<2, 3>(parts, [&](auto NP) {
+        hipLaunchKernelGGL(gather_kernel<NP>, gg, dim3(256), 0, st, src, nc, feat_lr, hl, wl, feat_hr, hh, wh, F, COL_BATCH, cmask,
+                           (float *)nullptr, Fs, fs_part);
+    });
     SURS_LAUNCH_CHECK();
-    if (split) {
-        if ((rc = g3_set_attributes())) return rc;
-        SplitSeg s1 = {Fs, fs_part, C_G / 16}, s2 = {nullptr, 0, 0};
-        const int nb256 = (int)(ncp / 256);
-        if (parts == 2)
-            hipLaunchKernelGGL((gemm_x3g_kernel<8, 128, G3_F32_T, 2>), dim3(gemm_grid(CC_PAD / 128, nb256)), dim3(512), g3_lds_bytes(128, 2),
-                               st, (const unsigned short *)(blob + h.wc2), CC_PAD, C_G, s1, s2, COL_BATCH,
-                               (const float *)(blob + h.bc), CC, (long long)CC_PAD, (unsigned short *)nullptr, 0LL, nb256);
-        else
-            hipLaunchKernelGGL((gemm_x3g_kernel<8, 128, G3_F32_T>), dim3(gemm_grid(CC_PAD / 128, nb256)), dim3(512), g3_lds_bytes(128),
-                               st, (const unsigned short *)(blob + h.wc3), CC_PAD, C_G, s1, s2, COL_BATCH,
-                               (const float *)(blob + h.bc), CC, (long long)CC_PAD, (unsigned short *)nullptr, 0LL, nb256);
-        SURS_LAUNCH_CHECK();
-    } else {
-        rc = launch_gemm(st, true, (const float *)(blob + h.wc), blob + h.wc3, CC_PAD, F, C_G, COL_BATCH, nullptr, 0, 0,
-                         (const float *)(blob + h.bc), 0, CC, CC_PAD, ncp);
-        if (rc) return rc;
-    }
-    return 0;
+    const SplitSeg f = {Fs, fs_part, C_G / 16}, none = {nullptr, 0, 0};
+    return launch_layer(st, parts, G3_F32_T, blob + (parts == 2 ? h.wc2 : h.wc3), CC_PAD, f, none, COL_BATCH, ncp,
+                        (const float *)(blob + h.bc), CC, nullptr);
 }
 
 // One workgroup per column: how many layer-0 channels the restated column kernels (v7 / v8) would list per z tile - the
@@ -1402,7 +1255,6 @@ static int run_column_batch(const ColumnSweep &cs, const PointSource &src, long 
     a.zpts = cs.run_z;
     if (restated) {
         // the affine part of layer 1: R = W1 (g . [a0 | w0z | w0p]) for the batch's columns, on the layer GEMM kernel
-        if ((rc = g3_set_attributes())) return rc;
         char *v7 = (char *)workspace + col_base_bytes(COL_BATCH);
         unsigned short *g_lr = (unsigned short *)v7, *g_hr = g_lr + (size_t)COL_BATCH * 2 * D1 * 3;
         float *r_lr = (float *)(v7 + col_v7_image_bytes(COL_BATCH)), *r_hr = r_lr + (size_t)COL_BATCH * 2 * D2;
@@ -1421,15 +1273,10 @@ static int run_column_batch(const ColumnSweep &cs, const PointSource &src, long 
         // of the MFMA work, no measurable change of the bf16 sweep's error (SURS_R_PARTS=0: the split's parts there too)
         const int r_parts_env = option(OPT_R_PARTS);
         const int rparts = (dtype == SURS_BF16 && r_parts_env == 1) ? 1 : parts;
-        if (rparts == 1)
-            hipLaunchKernelGGL(colsum_prepare_kernel<1>, pg, dim3(256), 0, st, CC, (const float *)(blob + h.zvec), (int)ncp, a.zmid,
+        with_parts<1, 2, 3>(rparts, [&](auto NP) {
+            hipLaunchKernelGGL(colsum_prepare_kernel<NP>, pg, dim3(256), 0, st, CC, (const float *)(blob + h.zvec), (int)ncp, a.zmid,
                                g_lr, part_lr, g_hr, part_hr);
-        else if (rparts == 2)
-            hipLaunchKernelGGL(colsum_prepare_kernel<2>, pg, dim3(256), 0, st, CC, (const float *)(blob + h.zvec), (int)ncp, a.zmid,
-                               g_lr, part_lr, g_hr, part_hr);
-        else
-            hipLaunchKernelGGL(colsum_prepare_kernel<3>, pg, dim3(256), 0, st, CC, (const float *)(blob + h.zvec), (int)ncp, a.zmid,
-                               g_lr, part_lr, g_hr, part_hr);
+        });
         SURS_LAUNCH_CHECK();
         if (ncp <= 1024 && option(OPT_RVEC_SMALL)) {
             // small batches (the ~ 100 runs of a point-runs call, small slabs, coarse octree levels): both classifiers in one launch of
@@ -1446,31 +1293,19 @@ static int run_column_batch(const ColumnSweep &cs, const PointSource &src, long 
             }
             ra.wgs0 = (int)(ra.npm[0] / 64) * 4;
             const unsigned wgs = (unsigned)(ra.wgs0 + (ra.npm[1] / 64) * 4);
-            if (rparts == 1) hipLaunchKernelGGL(rvec_small_kernel<1>, dim3(wgs), dim3(256), 0, st, ra);
-            else if (rparts == 2) hipLaunchKernelGGL(rvec_small_kernel<2>, dim3(wgs), dim3(256), 0, st, ra);
-            else hipLaunchKernelGGL(rvec_small_kernel<3>, dim3(wgs), dim3(256), 0, st, ra);
+            with_parts<1, 2, 3>(rparts, [&](auto NP) { hipLaunchKernelGGL(rvec_small_kernel<NP>, dim3(wgs), dim3(256), 0, st, ra); });
             SURS_LAUNCH_CHECK();
-        } else
-        for (int m = 0; m < 2; ++m) {
-            const int nvec = m ? 3 : 2;
-            const long long npm = (long long)nvec * ncp;
-            SplitSeg s1 = {m ? g_hr : g_lr, m ? part_hr : part_lr, D1 / 16}, s2 = {nullptr, 0, 0};
-            const int nb256 = (int)(npm / 256);
-            float *R = m ? r_hr : r_lr;
-            // output R[column][vector][512] (transposed; the kernel swaps the MFMA operands so that its stores run along the rows)
-            if (rparts == 1)   // (the first part of the two-part weight image is f16(w))
-                hipLaunchKernelGGL((gemm_x3g_kernel<8, 256, G3_F32_T, 1>), dim3(gemm_grid(D2 / 256, nb256)), dim3(512), g3_lds_bytes(256, 1),
-                                   st, (const unsigned short *)(blob + h.wt2[m][1]), D2, D1, s1, s2, npm, (const float *)zero_bias, R,
-                                   (long long)D2, (unsigned short *)nullptr, 0LL, nb256);
-            else if (rparts == 2)
-                hipLaunchKernelGGL((gemm_x3g_kernel<8, 256, G3_F32_T, 2>), dim3(gemm_grid(D2 / 256, nb256)), dim3(512), g3_lds_bytes(256, 2),
-                                   st, (const unsigned short *)(blob + h.wt2[m][1]), D2, D1, s1, s2, npm, (const float *)zero_bias, R,
-                                   (long long)D2, (unsigned short *)nullptr, 0LL, nb256);
-            else
-                hipLaunchKernelGGL((gemm_x3g_kernel<8, 256, G3_F32_T>), dim3(gemm_grid(D2 / 256, nb256)), dim3(512), g3_lds_bytes(256),
-                                   st, (const unsigned short *)(blob + h.wt3[m][1]), D2, D1, s1, s2, npm, (const float *)zero_bias, R,
-                                   (long long)D2, (unsigned short *)nullptr, 0LL, nb256);
-            SURS_LAUNCH_CHECK();
+        } else {
+            // output R[column][vector][512] (transposed; the kernel swaps the MFMA operands so that its stores run along the rows);
+            // one part: the first plane of the two-part weight image is f16(w)
+            const SplitSeg none = {nullptr, 0, 0};
+            for (int m = 0; m < 2; ++m) {
+                const long long npm = (m ? 3LL : 2LL) * ncp;   // points = vectors x columns
+                const SplitSeg g = {m ? g_hr : g_lr, m ? part_hr : part_lr, D1 / 16};
+                if ((rc = launch_layer(st, rparts, G3_F32_T, blob + (rparts == 3 ? h.wt3[m][1] : h.wt2[m][1]), D2, g, none, npm, npm,
+                                       zero_bias, m ? r_hr : r_lr, nullptr)))
+                    return rc;
+            }
         }
         a.rvec_lr = r_lr;
         a.rvec_hr = r_hr;
@@ -1664,7 +1499,7 @@ static int query_grid_impl(int i0, int i1, int ry, int rz, const double *mat, co
     const bool columns = sweep_has_columns(mat, calib);
 
     if (dtype == SURS_F32 && !(columns && grid_f32_use_columns() && !force_gemm)) {
-        // general calibration: every voxel is its own point, the five layers are GEMMs on the split-bf16 layer kernels
+        // general calibration: every voxel is its own point, the five layers run on the layer kernel
         const long long total = (long long)(i1 - i0) * ry * rz;
         Fp32Workspace w = carve_fp32(workspace, GRID_BATCH);
         if ((rc = zero_pad_rows(st, w))) return rc;

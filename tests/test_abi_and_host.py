@@ -55,21 +55,22 @@ def test_switches_live_in_one_table():
         settings.get("SURS_NO_SUCH_SWITCH")
 
 
-def test_library_options_by_name():
-    """surs_set_option / surs_get_option / surs_option_name: no GPU needed."""
+def test_library_options_set_get_by_name():
+    """surs_set_option / surs_get_option / surs_option_name: no GPU needed.  The retired layer-kernel switches are unknown names."""
     from surs_amd import native
     opts = native.options()
     assert {"grid_kernel", "split_parts", "conv_tall_min_wg", "point_runs_speculate"} <= set(opts) and len(opts) >= 13
     assert opts["conv_tall_min_wg"][0] == int(__import__("os").environ.get("SURS_CONV_TALL_MIN_WG", 256))
-    old = native.get_option("gemm_waves")
-    native.set_option("gemm_waves", 16)
+    old = native.get_option("rvec_small")
+    native.set_option("rvec_small", 16)
     try:
-        assert native.get_option("gemm_waves") == 16 and native.get_option("SURS_GEMM_WAVES") == 16   # either spelling
+        assert native.get_option("rvec_small") == 16 and native.get_option("SURS_RVEC_SMALL") == 16   # either spelling
     finally:
-        native.set_option("gemm_waves", old)
+        native.set_option("rvec_small", old)
     from surs_amd._lib import SursError
-    with pytest.raises(SursError, match="unknown option"):
-        native.set_option("no_such_option", 1)
+    for name in ("no_such_option", "gemm_x3", "gemm_big", "gemm_waves", "gemm_trace"):
+        with pytest.raises(SursError, match="unknown option"):
+            native.set_option(name, 1)
 
 
 def test_conv_weight_packing_layout():

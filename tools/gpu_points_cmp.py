@@ -1,6 +1,7 @@
-"""Runs the fp32 point evaluator on fixed inputs and saves / compares the four outputs.  The layer-kernel generation is
-chosen by the environment (read once per process): SURS_GEMM_X3=0 (fp32 MFMA), SURS_GEMM_BIG=0 (128x128 split-bf16 kernel
-for every layer), SURS_GEMM_WAVES=16.  `python tools/gpu_points_cmp.py save|cmp file.npz`"""
+"""Runs the fp32 point evaluator on fixed inputs and saves / compares the four outputs and a small bf16 sweep.  The operand split
+is chosen by the environment (read once per process): SURS_SPLIT=bf16x3 for three bf16 parts, two f16 parts otherwise.  Pointed
+at two builds (SURS_LIB_PATH) with the same split, `cmp` shows whether they compute the same bits (equal=1 on every line).
+`python tools/gpu_points_cmp.py save|cmp file.npz`"""
 import os, sys
 import numpy as np, torch
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
