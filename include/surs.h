@@ -337,6 +337,32 @@ int surs_query_grid_generic(int i0, int i1, int ry, int rz, const double *mat, c
                             const float *feat_lr, int hl, int wl, const float *feat_hr, int hh, int wh, const SursMlpShape *lr,
                             const SursMlpShape *hr, const void *blob, float *vol_hr, float *vol_lr, void *stream);
 
+/* Multi-view query of one subject (num_views = V in [1, 64], orthogonal projection) for classifiers of any supported shape, in ONE
+ * launch per call (csrc/surs_mlp_fused_views.inc): lib/model/SurfaceClassifier.py:53-81 with num_views > 1 - layers 0 .. L/2 per
+ * view on that view's features, then the view mean ((sum in view order) * (1/V)) of layer L/2's outputs and of the input features,
+ * layers L/2 + 1 .. L-1 once per point (L = 1, 2: the mean of the logits) - and SuRSNet.py:131-187 (view v's prediction = in_img_v *
+ * sigmoid(logit); channel 321 of view v's hr input = view v's pred_lr).  points [V][3][n] (lib/train_util.py:40-51), calibs DEVICE
+ * [V][12] (rows 0..2 of each view's calibration), feat_lr [V][hl][wl][256], feat_hr [V][hh][wh][64]; pred_hr / pred_lr [V][n];
+ * logit_hr / logit_lr [n] nullable (what the sigmoid takes).  p_lr [V][n] non-NULL: the hr classifier alone (query_sr on other
+ * points), pred_lr / logit_lr ignored.  Operand split as surs_query_points_generic; V = 1 gives its bits. */
+int surs_query_points_generic_views(const float *points, int n, int num_views, const float *calibs, float zmul, float zdiv,
+                                    const float *feat_lr, int hl, int wl, const float *feat_hr, int hh, int wh, const SursMlpShape *lr,
+                                    const SursMlpShape *hr, const void *blob, const float *p_lr, float *pred_hr, float *pred_lr,
+                                    float *logit_hr, float *logit_lr, void *stream);
+
+/* The dense sweep of a multi-view model (eval_grid over eval_func, lib/sdf.py:32-52, lib/mesh_util.py:20-28: every grid point seen
+ * by every view, view 0's predictions kept) of grid slab [i0, i1) in one launch: voxels as surs_query_grid_generic, the other
+ * arguments as surs_query_points_generic_views; vol_hr / vol_lr [(i1-i0)][ry][rz] = view 0's rows. */
+int surs_query_grid_generic_views(int i0, int i1, int ry, int rz, const double *mat, int num_views, const float *calibs, float zmul,
+                                  float zdiv, const float *feat_lr, int hl, int wl, const float *feat_hr, int hh, int wh,
+                                  const SursMlpShape *lr, const SursMlpShape *hr, const void *blob, float *vol_hr, float *vol_lr,
+                                  void *stream);
+
+/* HOST: how the multi-view evaluator runs this pair for num_views views: *tile_points per workgroup and *lds_bytes of LDS per
+ * workgroup, or SURS_E_INVALID naming the limit (num_views outside [1, 64], an unsupported shape, a hidden layer wider than 1824:
+ * the tile keeps the features and their running view sum in LDS).  The multi-view entries need no device workspace. */
+int surs_mlp_generic_views_info(const SursMlpShape *lr, const SursMlpShape *hr, int num_views, int *tile_points, int *lds_bytes);
+
 /* surs_query_points for point arrays that come as RUNS of equal (x, y): what the reference's dense sweep loop hands
  * query_mr / query_sr - 50 000 consecutive points of the flattened grid per call, z fastest (lib/sdf.py:32-45 batch_eval,
  * lib/mesh_util.py:20-28 eval_func) - i.e. ~ 98 columns of up to 512 points with one image position each.  Such a run is a column of

@@ -132,6 +132,11 @@ _SIGS = {
     "surs_query_points_generic": (C.c_int, [_vp, _i, _vp, _f, _f, _vp, _i, _i, _vp, _i, _i, _shp, _shp, _vp, _vp, _vp, _vp, _vp, _vp,
                                             _vp]),
     "surs_query_grid_generic": (C.c_int, [_i, _i, _i, _i, _vp, _vp, _f, _f, _vp, _i, _i, _vp, _i, _i, _shp, _shp, _vp, _vp, _vp, _vp]),
+    "surs_mlp_generic_views_info": (C.c_int, [_shp, _shp, _i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "surs_query_points_generic_views": (C.c_int, [_vp, _i, _i, _vp, _f, _f, _vp, _i, _i, _vp, _i, _i, _shp, _shp, _vp, _vp, _vp, _vp,
+                                                  _vp, _vp, _vp]),
+    "surs_query_grid_generic_views": (C.c_int, [_i, _i, _i, _i, _vp, _i, _vp, _f, _f, _vp, _i, _i, _vp, _i, _i, _shp, _shp, _vp, _vp,
+                                                _vp, _vp]),
     "surs_set_operand_split": (C.c_int, [_i]),
     "surs_set_operand_split_local": (C.c_int, [_i]),
     "surs_set_grid_kernel": (C.c_int, [_i]),

@@ -55,14 +55,18 @@ template <> struct Mfma16<3> {
     static __device__ __forceinline__ f32x4 mfma(vec8 a, vec8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 };
 
-// One classifier on the tile: layers 0 .. L-1 (LeakyReLU(0.01) between them), the last layer's row 0 into slog[P].
-template <int NP, int PB>
-__device__ __forceinline__ void fused_classifier(const FusedArgs &a, int m, float *feat, float *act, float *slog, int lane, int wave) {
+// Layers l0 .. l1-1 of classifier m on the tile (LeakyReLU(0.01) between them), the last layer's row 0 into slog[P].  VIEWS
+// (surs_mlp_fused_views.inc): layer mv's outputs - after its LeakyReLU unless it is the last layer - are not stored but added to
+// vsum, the caller's running sum over the views (first: the first view, assigned); each wave owns the same output tiles for every
+// view, so the sum stays in registers.
+template <int NP, int PB, bool VIEWS>
+__device__ __forceinline__ void fused_layers(const FusedArgs &a, int m, int l0, int l1, float *feat, float *act, float *slog, int lane,
+                                             int wave, f32x4 (&vsum)[16 / PB][PB], int mv, bool first) {
     typedef Mfma16<NP> MF;
     typedef typename MF::vec8 vec8;
     constexpr int TPW = 16 / PB;
     const int L = a.lay.n_layers[m];
-    for (int l = 0; l < L; ++l) {
+    for (int l = l0; l < l1; ++l) {
         const GenLayer &g = a.lay.layer[m][l];
         const int mt = g.mpad / GEN_MT, k1t = g.k1pad / GEN_KT, kts = k1t + g.k2pad / GEN_KT;
         const unsigned short *wimg = (const unsigned short *)(a.blob + (NP == 1 ? g.w1 : (NP == 2 ? g.w2 : g.w3)));
@@ -132,13 +136,23 @@ __device__ __forceinline__ void fused_classifier(const FusedArgs &a, int m, floa
                         const float y = acc[i][pb][r] + bias[row0 + r];
                         v[r] = (last || y >= 0.0f) ? y : y * 0.01f;
                     }
-                    if (!last) *reinterpret_cast<f32x4 *>(act + pt * a.as + row0) = v;
+                    if (VIEWS && l == mv) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) vsum[i][pb][r] = first ? v[r] : vsum[i][pb][r] + v[r];
+                    } else if (!last) *reinterpret_cast<f32x4 *>(act + pt * a.as + row0) = v;
                     else if (row0 == 0) slog[pt] = v[0];
                 }
             }
         }
         __syncthreads();
     }
+}
+
+// One classifier on the tile: layers 0 .. L-1.
+template <int NP, int PB>
+__device__ __forceinline__ void fused_classifier(const FusedArgs &a, int m, float *feat, float *act, float *slog, int lane, int wave) {
+    f32x4 unused[16 / PB][PB];
+    fused_layers<NP, PB, false>(a, m, 0, a.lay.n_layers[m], feat, act, slog, lane, wave, unused, -1, false);
 }
 
 template <int NP, int PB>

@@ -2169,3 +2169,4 @@ extern "C" int surs_query_points_columns(const float *points, long long ld, int 
 }
 
 #include "surs_mlp_fused.inc"
+#include "surs_mlp_fused_views.inc"

@@ -427,9 +427,10 @@ def reconstruction_sharded_once(opt, net, calib_tensor, resolution, b_min, b_max
     fl, fh = net.features()
     zmul, zdiv = net._zscale()
     prec = "fp32x" if wide else getattr(opt, "precision", "fp32")
-    if net.generic_mlp() is not None:
-        raise NotImplementedError("slab / sharded sweeps: classifiers of the released shape only")
-    blob = net._mlp_blob()
+    g = net.generic_mlp()   # (classifiers of another shape: the fused evaluator sweeps the slab; the same on every rank)
+    if g is not None and (net.num_views != 1 or getattr(net, "projection_mode", "orthogonal") != "orthogonal"):
+        raise NotImplementedError("slab / sharded sweeps of classifiers of another shape: single-view orthogonal models only")
+    blob = net._mlp_blob() if g is None else g.blob
     ws = net._workspace()
     dev = blob.device
     vols = [torch.empty((nloc + (1 if halo else 0), R, R), dtype=torch.float32, device=dev) for _ in range(2)]
@@ -457,15 +458,30 @@ def reconstruction_sharded_once(opt, net, calib_tensor, resolution, b_min, b_max
     # 13-element status row of the counts exchange
     owner = next(r for r in range(world) if slab_range(R, r, world)[0] <= R // 2 < slab_range(R, r, world)[1])
     k, kern_err = 0.0, None
-    if rank == owner:
-        try:
-            k = float(native.grid_kernel_for(R, R, R, m12, calib, zmul, zdiv, fl, fh, blob, prec, ws))
-        except Exception as e:   # noqa: BLE001 - the others are waiting in the gather below: tell them
-            k, kern_err = -1.0, e
-    k = all_gather_rows([k], dev, group)[owner, 0]
+    if g is None:   # (classifiers of another shape have no column kernels: every rank skips the probe and its exchange alike)
+        if rank == owner:
+            try:
+                k = float(native.grid_kernel_for(R, R, R, m12, calib, zmul, zdiv, fl, fh, blob, prec, ws))
+            except Exception as e:   # noqa: BLE001 - the others are waiting in the gather below: tell them
+                k, kern_err = -1.0, e
+        k = all_gather_rows([k], dev, group)[owner, 0]
     if k < 0:
         raise kern_err or RuntimeError("the column-kernel probe failed on rank %d" % owner)
     kern = int(k)
+
+    def sweep_generic(a, b, vh=None, vl=None):   # planes [i0 + a, i0 + b) of classifiers of another shape, GENERIC_SLAB_POINTS per launch
+        if vh is None:
+            vh = torch.empty((b - a, R, R), dtype=torch.float32, device=dev)
+            vl = torch.empty_like(vh)
+        planes = max(1, mesh_util.GENERIC_SLAB_POINTS // (R * R))
+        with native.reduced_point_operands(prec in ("bf16", "fp16")):
+            for c in range(a, b, planes):
+                d = min(b, c + planes)
+                native.query_grid_generic(i0 + c, i0 + d, R, R, m12, calib, zmul, zdiv, fl, fh, g, vh[c - a:d - a], vl[c - a:d - a])
+        return vh, vl
+
+    if want_normals and g is not None:
+        return _reconstruction_sharded_with_normals(net, lambda: sweep_generic(0, nloc), mat, R, dst, group)
     if want_normals:
         def sweep_slab():
             try:
@@ -494,6 +510,14 @@ def reconstruction_sharded_once(opt, net, calib_tensor, resolution, b_min, b_max
         sweep = torch.cuda.current_stream(dev)
         done = []
         for a, b in sched:
+            if g is not None:
+                sweep_generic(a, b, vols[0][a:b], vols[1][a:b])
+                ev = torch.cuda.Event()
+                ev.record(sweep)
+                done.append((b, ev))
+                if ex is None:
+                    ex = halo_exchange()
+                continue
             try:
                 native.query_grid(i0 + a, i0 + b, R, R, m12, calib, zmul, zdiv, fl, fh, blob, prec, ws, vols[0][a:b], vols[1][a:b],
                                   kernel=kern)

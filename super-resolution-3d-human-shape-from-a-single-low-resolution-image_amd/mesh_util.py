@@ -22,8 +22,28 @@ GENERIC_SLAB_POINTS = 1 << 21   # voxels per launch of the fused evaluator's den
 
 
 def _no_generic_views(net):
-    if net.generic_mlp() is not None:
-        raise NotImplementedError("classifiers of a shape other than the released one: single-view orthogonal models only")
+    if net.generic_mlp() is not None and getattr(net, "projection_mode", "orthogonal") != "orthogonal":
+        raise NotImplementedError("classifiers of a shape other than the released one: orthogonal models only")
+
+
+def eval_volumes_generic_views(opt, net, calib_tensor, resolution, b_min, b_max, transform=None):
+    """eval_volumes_views for classifiers of any supported shape: the fused multi-view evaluator (surs_query_grid_generic_views)
+    over the whole grid, GENERIC_SLAB_POINTS voxels per launch, view 0's predictions kept; --precision bf16 | fp16: one f16
+    product per MAC, fp32: fp32-grade."""
+    R = int(resolution)
+    _, mat = create_grid(R, R, R, b_min, b_max, transform=transform)
+    fl, fh = net.views_features()
+    cal = net._views_calibs(net._calib_rows(calib_tensor, None), net._device())
+    zmul, zdiv = net._zscale()
+    g = net.generic_mlp()
+    vh = torch.empty((R, R, R), dtype=torch.float32, device=g.blob.device)
+    vl = torch.empty_like(vh)
+    planes = max(1, GENERIC_SLAB_POINTS // (R * R))
+    with native.reduced_point_operands(getattr(opt, "precision", "fp32") in ("bf16", "fp16")):
+        for a in range(0, R, planes):
+            b = min(R, a + planes)
+            native.query_grid_generic_views(a, b, R, R, mat[:3].reshape(-1), cal, zmul, zdiv, fl, fh, g, vh[a:b], vl[a:b])
+    return vh, vl, mat
 
 
 def eval_volumes_generic(opt, net, calib_tensor, resolution, b_min, b_max, transform=None, i0=0, i1=None, precision=None,
@@ -106,6 +126,8 @@ def eval_volumes_views(opt, net, calib_tensor, resolution, b_min, b_max, transfo
     retry on three bf16 parts after an f16 overflow - walks the batches through the facade as the reference does (same kernels, same bits:
     tests/test_gpu_model.py)."""
     _no_generic_views(net)
+    if net.generic_mlp() is not None and not loop:
+        return eval_volumes_generic_views(opt, net, calib_tensor, resolution, b_min, b_max, transform)
     _, mat = create_grid(resolution, resolution, resolution, b_min, b_max, transform=transform)
     dev = net._device()
     R = int(resolution)

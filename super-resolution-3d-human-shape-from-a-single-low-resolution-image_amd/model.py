@@ -244,9 +244,41 @@ class SuRSNet:
         self._feat_cache = (key, tl, th, out) if cacheable else None
         return out
 
+    def views_features(self):
+        """(feat_lr [V,hl,wl,256], feat_hr [V,hh,wh,64]) contiguous NHWC device tensors of every view: what the multi-view evaluator of
+        classifiers of any shape reads.  Cached as features() caches (same key rules, invalidate_feature_cache): the octree walk and
+        the reference's sweep loop ask for them once per batch."""
+        if not self.im_feat_list_lr or not self.im_feat_list_hr:
+            raise RuntimeError("filter_lr / filter_hr must run before a query")
+        tl, th = self.im_feat_list_lr[-1], self.im_feat_list_hr[0]
+        if tl.shape[0] != self.num_views or th.shape[0] != self.num_views:
+            raise RuntimeError("the encoder ran on %d views, num_views is %d" % (tl.shape[0], self.num_views))
+        cacheable = tl.is_cuda and th.is_cuda and not tl.is_inference() and not th.is_inference()
+        key = (tl.data_ptr(), th.data_ptr(), tuple(tl.shape), tuple(th.shape), tl.stride(), th.stride(),
+               tl._version if cacheable else None, th._version if cacheable else None)
+        hit = getattr(self, "_views_feat_cache", None)
+        if cacheable and hit is not None and hit[0] == key and hit[1] is tl and hit[2] is th:
+            return hit[3]
+        dev = self._device()
+        out = tl.to(dev, torch.float32).permute(0, 2, 3, 1).contiguous(), th.to(dev, torch.float32).permute(0, 2, 3, 1).contiguous()
+        self._views_feat_cache = (key, tl, th, out) if cacheable else None
+        return out
+
+    def _views_calibs(self, rows, dev):
+        """Host calibration rows [V,12] (_calib_rows' cached array) as a device tensor, copied once per rows array; one row serves
+        every view (gen_mesh's single diag(2, -2, 2, 1) calibration)."""
+        hit = getattr(self, "_views_cal_cache", None)
+        if hit is not None and hit[0] is rows:
+            return hit[1]
+        cal = np.ascontiguousarray(rows, np.float32)
+        cal = torch.from_numpy(np.repeat(cal, self.num_views, 0) if cal.shape[0] == 1 else cal).to(dev)
+        self._views_cal_cache = (rows, cal)
+        return cal
+
     def invalidate_feature_cache(self):
         """Forget the converted copy of hand-assigned feature maps (see features(): needed only after an edit no version counter sees)."""
         self._feat_cache = None
+        self._views_feat_cache = None
 
     # ------------------------------------------------------------------ query
     def _zscale(self):
@@ -304,8 +336,21 @@ class SuRSNet:
         zmul, zdiv = self._zscale()
         V = self.num_views
         g = self.generic_mlp()
-        if g is not None and not (V == 1 and self.projection_mode == "orthogonal"):
-            raise NotImplementedError("classifiers of a shape other than the released one: single-view orthogonal models only")
+        if g is not None and self.projection_mode != "orthogonal":
+            raise NotImplementedError("classifiers of a shape other than the released one: orthogonal models only")
+        if g is not None and V > 1:
+            # one subject seen by V views (SurfaceClassifier.py:70-76): the fused multi-view evaluator, one launch per call
+            if points.shape[0] != V or calibs.shape[0] not in (1, V):
+                raise NotImplementedError("one subject per call: points must be [num_views,3,N] and calibs [num_views,4,4] (or one "
+                                          "[1,4,4] for every view)")
+            pts = points.to(dev, torch.float32).contiguous()
+            cal = self._views_calibs(self._calib_rows(calibs, transforms), dev)
+            pl = None if p_lr is None else p_lr.to(dev, torch.float32).reshape(V, -1).contiguous()
+            run = lambda: native.query_points_generic_views(pts, cal, zmul, zdiv, *self.views_features(), g, p_lr=pl)
+            with native.reduced_point_operands(self.precision in ("bf16", "fp16")):
+                first = run()
+            phr, plr = self._finite_or_wide(run, first=first)
+            return phr.view(V, 1, -1), plr.view(V, 1, -1)
         if g is not None:
             # the fused evaluator, one launch per image of the batch; --precision bf16 | fp16: one f16 product per MAC
             B = points.shape[0]

@@ -493,6 +493,75 @@ def query_grid_generic(i0, i1, ry, rz, mat, calib, zmul, zdiv, feat_lr, feat_hr,
     return vol_hr, vol_lr
 
 
+def mlp_generic_views_info(shapes, num_views):
+    """(points per tile, LDS bytes per workgroup) of surs_mlp_generic_views_info: how the multi-view evaluator runs this pair for
+    num_views views (host only).  Raises ValueError with the library's message for what it refuses: num_views outside [1, 64], a
+    hidden layer wider than the multi-view limit."""
+    lr, hr = (_shape_struct(*s) for s in shapes)
+    tp, lds = C.c_int(0), C.c_int(0)
+    if lib().surs_mlp_generic_views_info(C.byref(lr), C.byref(hr), int(num_views), C.byref(tp), C.byref(lds)) != 0:
+        raise ValueError(lib().surs_last_error().decode())
+    return tp.value, lds.value
+
+
+def _device_calibs(calibs, dev):
+    """calibs [V,12] (host array, or a device tensor already) -> contiguous float32 device tensor [V,12]."""
+    if torch.is_tensor(calibs) and calibs.is_cuda:
+        return _f32c(calibs.reshape(calibs.shape[0], -1)[:, :12].contiguous())
+    cal = np.ascontiguousarray(np.asarray(calibs, np.float32).reshape(np.shape(calibs)[0], -1)[:, :12])
+    return torch.from_numpy(cal).to(dev)
+
+
+def query_points_generic_views(points, calibs, zmul, zdiv, feat_lr, feat_hr, g, p_lr=None, want_logits=False):
+    """surs_query_points_generic_views: both classifiers of GenericMlp g for one subject seen by V views, in one launch.  points
+    [V,3,N] f32 device tensor; calibs [V,12] (host rows or a device tensor); feat_lr [V,hl,wl,256] and feat_hr [V,hh,wh,64]
+    contiguous NHWC device tensors; p_lr [V,N] given: the hr classifier alone.  Returns (pred_hr [V,N], pred_lr [V,N][, logit_hr [N],
+    logit_lr [N]]); with p_lr, pred_lr is p_lr and logit_lr None."""
+    points = _f32c(points)
+    V, _, n = points.shape
+    mlp_generic_views_info(g.shapes, V)
+    dev = points.device
+    feat_lr, feat_hr = _f32c(feat_lr), _f32c(feat_hr)
+    assert feat_lr.shape[0] == V and feat_hr.shape[0] == V and feat_lr.shape[3] == 256 and feat_hr.shape[3] == 64
+    cal = _device_calibs(calibs, dev)
+    assert cal.shape == (V, 12)
+    phr = torch.empty((V, n), dtype=torch.float32, device=dev)
+    if p_lr is not None:
+        p_lr = _f32c(p_lr.reshape(V, n))
+        plr = p_lr
+    else:
+        plr = torch.empty_like(phr)
+    lg = [torch.empty(n, dtype=torch.float32, device=dev) if want_logits else None for _ in range(2)]
+    if p_lr is not None:
+        lg[1] = None
+    check(lib().surs_query_points_generic_views(_ptr(points), n, V, _ptr(cal), float(zmul), float(zdiv), _ptr(feat_lr), feat_lr.shape[1],
+                                                feat_lr.shape[2], _ptr(feat_hr), feat_hr.shape[1], feat_hr.shape[2], C.byref(g.lr),
+                                                C.byref(g.hr), _ptr(g.blob), _ptr(p_lr), _ptr(phr),
+                                                None if p_lr is not None else _ptr(plr), _ptr(lg[0]), _ptr(lg[1]), _stream()))
+    return (phr, plr, lg[0], lg[1]) if want_logits else (phr, plr)
+
+
+def query_grid_generic_views(i0, i1, ry, rz, mat, calibs, zmul, zdiv, feat_lr, feat_hr, g, vol_hr=None, vol_lr=None):
+    """surs_query_grid_generic_views: the dense sweep of grid slab [i0, i1) for a multi-view model with the fused evaluator - every
+    voxel seen by every view, view 0's predictions kept (lib/mesh_util.py:20-28).  calibs [V,12]; feat_lr [V,hl,wl,256], feat_hr
+    [V,hh,wh,64] contiguous NHWC device tensors.  Returns (vol_hr, vol_lr) float32 device tensors [(i1-i0), ry, rz]."""
+    feat_lr, feat_hr = _f32c(feat_lr), _f32c(feat_hr)
+    V = feat_lr.shape[0]
+    mlp_generic_views_info(g.shapes, V)
+    dev = g.blob.device
+    assert feat_hr.shape[0] == V and feat_lr.shape[3] == 256 and feat_hr.shape[3] == 64
+    cal = _device_calibs(calibs, dev)
+    assert cal.shape == (V, 12)
+    if vol_hr is None:
+        vol_hr = torch.empty((i1 - i0, ry, rz), dtype=torch.float32, device=dev)
+        vol_lr = torch.empty_like(vol_hr)
+    m = (C.c_double * 12)(*[float(v) for v in np.asarray(mat, np.float64).reshape(-1)[:12]])
+    check(lib().surs_query_grid_generic_views(i0, i1, ry, rz, m, V, _ptr(cal), float(zmul), float(zdiv), _ptr(feat_lr), feat_lr.shape[1],
+                                              feat_lr.shape[2], _ptr(feat_hr), feat_hr.shape[1], feat_hr.shape[2], C.byref(g.lr),
+                                              C.byref(g.hr), _ptr(g.blob), _ptr(vol_hr), _ptr(vol_lr), _stream()))
+    return vol_hr, vol_lr
+
+
 class Workspace:
     """Grow-only device scratch buffer; remembers mesh capacities between extractions."""
 

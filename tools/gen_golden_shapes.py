@@ -1,12 +1,14 @@
 """Golden vectors for SurfaceClassifier shapes other than the released one, from the upstream reference itself on CPU
 (tools/ref_harness.py, weights.synthetic_state_dict for each shape's flags).
 
-    python tools/gen_golden_shapes.py [query] [recon]
+    python tools/gen_golden_shapes.py [query] [recon] [views]
 
 query -> tests/golden/query_shapes.npz: one set of 7168 points (uniform in the box, on the image border, outside the image) and,
          per shape, pred_hr / pred_lr and the last convolution's logits (forward hooks); one query_sr-on-other-points case (B = 2).
 recon -> tests/golden/recon_shapes_r32.npz: the reference's dense (eval_grid) and octree (eval_grid_octree, init_resolution 8)
          occupancy fields at R = 32 for shape s1, encoder on weights.synthetic_image(64, seed=1).
+views -> tests/golden/query_shapes_views.npz, query_shapes_views4.npz, recon_shapes_views_r32.npz: the same shapes (and l2) with
+         --num_views 2 (4 for s1 and deep), per-view features and calibrations (gen_views).
 """
 import os
 import sys
@@ -147,6 +149,106 @@ def gen_recon():
                         octree_hr=oh.astype(np.float32), octree_lr=ol.astype(np.float32), threshold=np.array(opt_ref.threshold),
                         init_resolution=np.array(8))
     print("recon_shapes_r32.npz: %d bytes" % os.path.getsize(os.path.join(GOLD, "recon_shapes_r32.npz")))
+
+
+L2 = _dims("lr", [321, 64, 1]) + _dims("hr", [322, 64, 1]) + _res("lr", [1]) + _res("hr", [1])   # a skip at the merge layer, mean of the logits
+VIEW_SHAPES = dict(SHAPES, l2=L2)
+VIEW_COUNTS = {"s1": (2, 4), "deep": (2, 4)}   # every other shape: V = 2
+
+
+def views_calibs(V):
+    """[V,4,4] orthogonal calibrations rotated about y (as gen_golden.gen_views builds them): x' = 2 (cos a x + sin a z) moves
+    points of shape_points() in and out of the views' images."""
+    return np.stack([np.array([[2.0 * np.cos(a), 0, 2.0 * np.sin(a), 0.02 * v], [0, -2.0, 0, -0.01 * v],
+                               [-2.0 * np.sin(a), 0, 2.0 * np.cos(a), 0], [0, 0, 0, 1]], np.float32)
+                     for v, a in enumerate(np.linspace(0.0, 0.6, V))])
+
+
+def views_features(V):
+    """per-view feature maps: synth_features(seed=10 + v) stacked -> ([V,256,32,32], [V,64,128,128])"""
+    f = [synth_features(seed=10 + v) for v in range(V)]
+    return np.stack([a for a, _ in f]), np.stack([b for _, b in f])
+
+
+def make_views_net(extra, V):
+    net = rh.build_net(rh.parse_opt(FLAGS + extra + ["--num_views", str(V)]))
+    sd = weights.synthetic_state_dict(options.BaseOptions().parse(FLAGS + extra), seed=0)
+    net.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in sd.items()}, strict=True)
+    fl, fh = views_features(V)
+    net.im_feat_list_lr = [torch.from_numpy(fl)]
+    net.im_feat_list_hr = [torch.from_numpy(fh)]
+    return net
+
+
+def gen_views():
+    """views -> tests/golden/query_shapes_views.npz (V = 2, every shape), query_shapes_views4.npz (V = 4: s1, deep; the query_sr on
+    other points case, s1, V = 2) and recon_shapes_views_r32.npz (dense and octree fields, s1, V = 2): the reference's own multi-view
+    path (SurfaceClassifier.py:70-76, train_util.reshape_sample_tensor), per-view features synth_features(seed=10 + v), calibrations
+    views_calibs(V).  pred_hr / pred_lr [V,N]; logits (the last convolution's single row per point) where the merge layer is not the
+    last one."""
+    ns = rh.load_reference()
+    pts = shape_points()
+    out2, out4 = {"points": pts}, {}
+    for name, extra in VIEW_SHAPES.items():
+        for V in VIEW_COUNTS.get(name, (2,)):
+            net = make_views_net(extra, V)
+            cap = {}
+            hooks = [getattr(net, m)._modules["conv%d" % (len(getattr(net, m).filters) - 1)].register_forward_hook(
+                lambda mod, i, o, key=m: cap.__setitem__(key, o.detach().clone())) for m in ("mlp_lr", "mlp_hr")]
+            samples = ns.train_util.reshape_sample_tensor(torch.from_numpy(pts[None].copy()), V)
+            c = torch.from_numpy(views_calibs(V))
+            with torch.no_grad(), rh.quiet():
+                net.query_mr(samples, c)
+                net.query_sr(samples, c)
+                phr, plr = net.get_preds()
+            for h in hooks:
+                h.remove()
+            assert tuple(phr.shape) == (V, 1, pts.shape[1])
+            out = out2 if V == 2 else out4
+            key = "%s_v%d_" % (name, V)
+            out.update({key + "pred_hr": phr[:, 0].numpy(), key + "pred_lr": plr[:, 0].numpy()})
+            for m, tag in (("mlp_lr", "lr"), ("mlp_hr", "hr")):
+                if cap[m].shape[0] == 1:   # (merge layer = last layer: the last convolution yields one row per view)
+                    out[key + "logit_" + tag] = cap[m][0, 0].numpy()
+            print("%-6s V=%d zeros per view %s" % (name, V, [round(float((phr[v] == 0).float().mean()), 3) for v in range(V)]))
+    # query_sr on points other than query_mr's: s1, V = 2
+    V, n = 2, 4099
+    net = make_views_net(S1, V)
+    c = torch.from_numpy(views_calibs(V))
+    pts_mr = weights.synthetic_points(n, seed=11)
+    pts_sr = weights.synthetic_points(n, seed=13)
+    with torch.no_grad(), rh.quiet():
+        net.query_mr(ns.train_util.reshape_sample_tensor(torch.from_numpy(pts_mr[None].copy()), V), c)
+        net.query_sr(ns.train_util.reshape_sample_tensor(torch.from_numpy(pts_sr[None].copy()), V), c)
+        phr, plr = net.get_preds()
+    out4.update(sr_points_mr=pts_mr, sr_points_sr=pts_sr, sr_pred_hr=phr[:, 0].numpy(), sr_pred_lr=plr[:, 0].numpy())
+    for fname, out in (("query_shapes_views.npz", out2), ("query_shapes_views4.npz", out4)):
+        np.savez_compressed(os.path.join(GOLD, fname), **out)
+        print("%s: %d bytes" % (fname, os.path.getsize(os.path.join(GOLD, fname))))
+    # R = 32 dense and octree fields, s1, V = 2: eval_func's multi-view recipe (lib/mesh_util.py:20-28), view 0's predictions
+    net = make_views_net(S1, V)
+    opt_ref = rh.parse_opt(FLAGS + S1 + ["--num_views", str(V)])
+    R = 32
+    coords, mat = ns.sdf.create_grid(R, R, R, np.array([-0.5] * 3), np.array([0.5] * 3))
+
+    def eval_func(points):
+        samples = torch.from_numpy(np.repeat(np.expand_dims(points, axis=0), V, axis=0)).float()
+        net.query_mr(samples, c)
+        net.query_sr(samples, c)
+        phr, plr = net.get_preds()
+        return phr[0][0].detach().numpy(), plr[0][0].detach().numpy()
+
+    with torch.no_grad(), rh.quiet():
+        dh, dl = ns.sdf.eval_grid(coords, eval_func, num_samples=50000)
+        oh, ol = ns.sdf.eval_grid_octree(types.SimpleNamespace(threshold=opt_ref.threshold), coords, eval_func, init_resolution=8,
+                                         num_samples=50000)
+    for k, v in (("dense hr", dh), ("dense lr", dl), ("octree hr", oh), ("octree lr", ol)):
+        print("%-9s range %.3f..%.3f, mean %.3f, > 0.5: %.3f" % (k, v.min(), v.max(), v.mean(), float((v > 0.5).mean())))
+    fname = "recon_shapes_views_r32.npz"
+    np.savez_compressed(os.path.join(GOLD, fname), dense_hr=dh.astype(np.float32), dense_lr=dl.astype(np.float32),
+                        octree_hr=oh.astype(np.float32), octree_lr=ol.astype(np.float32), threshold=np.array(opt_ref.threshold),
+                        init_resolution=np.array(8))
+    print("%s: %d bytes" % (fname, os.path.getsize(os.path.join(GOLD, fname))))
 
 
 if __name__ == "__main__":
