@@ -129,6 +129,17 @@ int surs_avgpool2(const float *x, int h, int w, int c, int x_ld, float *y, int y
 /* y = bicubic_x2(x) (+ addend, nullable, pitch add_ld): A=-0.75, border-clamped taps */
 int surs_bicubic_up2(const float *x, int h, int w, int c, int x_ld, int align_corners, const float *addend, int add_ld,
                      float *y, int y_ld, void *stream);
+/* y = bicubic(x) enlarged by the integer factor `scale` in SURS_SR_SCALE_MIN..SURS_SR_SCALE_MAX (+ addend, nullable, pitch add_ld): nn.Upsample(
+ * scale_factor = scale, mode = 'bicubic') with PyTorch's arithmetic - A = -0.75, border-clamped taps, the source coordinate
+ * (float)(1 / scale) * (dst + 0.5) - 0.5 as a separately rounded fp32 multiply and subtract (align_corners = 0) -, one output element
+ * per work item.  scale = 2 is surs_bicubic_up2 (the same kernels, the same bits); scale = 1 returns x. */
+enum { SURS_SR_SCALE_MIN = 1, SURS_SR_SCALE_MAX = 4 };
+int surs_bicubic_up(const float *x, int h, int w, int c, int x_ld, int scale, int align_corners, const float *addend, int add_ld,
+                    float *y, int y_ld, void *stream);
+/* surs_bicubic_up2 as 2 x 2 blocks of output pixels per work item (25 loads for four outputs instead of 64; the same bits): the form
+ * surs_bicubic_up2_gn runs, without its statistics.  c % 4 == 0, 16-byte aligned rows. */
+int surs_bicubic_up2_block(const float *x, int h, int w, int c, int x_ld, int align_corners, const float *addend, int add_ld, float *y,
+                           int y_ld, void *stream);
 /* y[2h+i][2w+j][c] = lrelu(x[h][w][4c+2i+j], slope)  (slope 1 = no activation) */
 int surs_pixel_shuffle2(const float *x, int h, int w, int c4, int x_ld, float slope, float *y, int y_ld, void *stream);
 /* y = a + b (+ c, nullable) */
@@ -182,6 +193,15 @@ int surs_conv2d_nhwc_gn_sum(int parts, const float *x, int h, int w, int cin, in
                             float eps, float *y, int cout, int y_ld, SursGnStats *gn_out, const float *residual, int res_ld, float *y2,
                             int y2_ld, double *gn_out2, int gn2_pitch, int gn2_g0, int gn2_cg, int *gn2_slots, void *stream);
 
+/* surs_conv2d_nhwc_gn_sum without statistics on either side - pre = relu(x * in_scale + in_shift) (BatchNorm in eval mode folded to
+ * constants; nullable: none), y = v (nullable), y2 = v + residual -: the same tiles, the same values, no sums formed or written. */
+int surs_conv2d_nhwc_sum(int parts, const float *x, int h, int w, int cin, int x_ld, const void *wsplit, const float *bias,
+                         const float *in_scale, const float *in_shift, float *y, int cout, int y_ld, const float *residual, int res_ld,
+                         float *y2, int y2_ld, void *stream);
+/* Calls so far, process-wide, into the entry points that compute or consume GroupNorm statistics (surs_groupnorm_coeffs*, surs_*_gn,
+ * surs_conv2d_nhwc_gn_sum): a BatchNorm encoder makes none. */
+long long surs_stats_calls(void);
+
 /* ------------------------------------------------------------------ the encoder as ONE call per network
  * SuRSNet.super_res / filter_hr / filter_lr (lib/model/SuRSNet.py:101-129) = SuRSSR_v3.forward (lib/model/SuRSSR_v3.py:143-181),
  * HGFilter.forward high_res (lib/model/HGFilters.py:179-181) and low_res (:183-206; ConvBlock :29-74, HourGlass :76-120), sequenced
@@ -192,6 +212,9 @@ int surs_conv2d_nhwc_gn_sum(int parts, const float *x, int h, int w, int cin, in
 enum { SURS_ENC_SEPARATE_SUM = 1 };  /* SursEncoderNet.flags: a ConvBlock's closing sum as a pass of its own (surs_add3_gn: the four-launch
                                          form of rounds 4 - 5, whose bits the host mirror's per-launch sequencing reproduces) instead of in
                                          the three convolutions' epilogues (surs_conv2d_nhwc_gn_sum: the default) */
+enum { SURS_ENC_EXTENDED = 2 };      /* SursEncoderNet.flags: the caller's struct has the fields behind `bn_end` (norm, sr_scale, bn_*) and
+                                         they are read; without it the net is GroupNorm, x2 - whatever lies behind bn_end */
+enum { SURS_NORM_GROUP = 0, SURS_NORM_BATCH = 1 };   /* SursEncoderNet.norm (--norm) */
 typedef struct SursConv {
     const void *w_split;    /* surs_conv_pack_weights_x2 image (3x3 and 1x1), or NULL: only the fp32 kernel applies */
     const float *w_packed;  /* surs_conv_pack_weights image (the fp32 MFMA / direct kernels: 3 -> 32 head, 32 -> 3 tail) */
@@ -200,6 +223,7 @@ typedef struct SursConv {
 } SursConv;
 typedef struct SursGroupNorm { const float *gamma, *beta; } SursGroupNorm;           /* GroupNorm(32, C), eps 1e-5 */
 typedef struct SursConvBlock { SursConv conv[3]; SursGroupNorm bn[3]; } SursConvBlock; /* ConvBlock with in_planes == out_planes */
+typedef struct SursBatchNorm { const float *scale, *shift; } SursBatchNorm;          /* BatchNorm2d in eval mode, folded: [C] each */
 typedef struct SursEncoderNet {
     int residual;           /* opt.residual: the ResBlocks of the super-resolution stages run */
     int n_block[3];         /* opt.n_block */
@@ -217,13 +241,27 @@ typedef struct SursEncoderNet {
     const SursConvBlock *top_m;   /* [num_stack] */
     const SursConv *conv_last, *l, *next;   /* [num_stack]; next[s] = bl{s} + al{s} o l{s} merged (W_bl + W_al W_l), unused for the last stack */
     const SursGroupNorm *bn_end;  /* [num_stack] */
+    /* ---- read only with SURS_ENC_EXTENDED in flags */
+    int norm;               /* SURS_NORM_GROUP: the SursGroupNorm fields above apply.  SURS_NORM_BATCH (--norm batch): nn.BatchNorm2d in EVAL
+                               mode at every norm site, folded by the caller to y = x * scale[c] + shift[c] (scale = weight / sqrt(running_var
+                               + 1e-5), shift = bias - running_mean * scale); the SursGroupNorm fields are not read, no statistics are computed */
+    int sr_scale;           /* --scale: the bicubic enlargement in front of the super-resolution net, SURS_SR_SCALE_MIN..MAX (0 = 2) */
+    /* SURS_NORM_BATCH: the folded coefficients per site, three per ConvBlock (bn1, bn2, bn3) in the order of the block arrays above */
+    const SursBatchNorm *bn_conv2;    /* [3] */
+    const SursBatchNorm *bn_hg;       /* [3 * num_stack * (3 * hg_depth + 1)] */
+    const SursBatchNorm *bn_top_m;    /* [3 * num_stack] */
+    const SursBatchNorm *bn_end_bn;   /* [num_stack] */
 } SursEncoderNet;
 /* Streams the caller lends for the low-resolution branch of hourglass level 1..4 (NULL entries / NULL struct: the branches run one
  * behind the other on `stream`).  The library never creates a stream (a new stream shifts the hardware-queue assignment of every later one). */
 typedef struct SursEncoderStreams { void *side[4]; } SursEncoderStreams;
-/* bytes of workspace the calls below need for an h x w input image (0: bad arguments) */
+/* bytes of workspace the calls below need for an h x w input image (0: bad arguments, a size the net cannot run included);
+ * _enlarged: for an enlarged image of eh x ew = sr_scale * (h x w) pixels (what a caller of surs_encoder_filter_lr alone knows:
+ * eh = 4 * feature_lr's height) */
 size_t surs_encoder_workspace_bytes(const SursEncoderNet *net, int h, int w);
-/* x [h][w][3] (pitch x_ld) -> feature_lr [h/2][w/2][256], feature_hr [2h][2w][64] and, if want_image, img_sr [2h][2w][3] (dense) */
+size_t surs_encoder_workspace_bytes_enlarged(const SursEncoderNet *net, int eh, int ew);
+/* x [h][w][3] (pitch x_ld) -> feature_lr [h/2][w/2][256], feature_hr [2h][2w][64] and, if want_image, img_sr [2h][2w][3] (dense).
+ * With net->sr_scale = s: feature_lr [sh/4][sw/4][256], feature_hr and img_sr [sh][sw]; s * h and s * w must be multiples of 8. */
 int surs_encoder_super_res(const SursEncoderNet *net, const float *x, int h, int w, int x_ld, int want_image, float *img_sr,
                            float *feature_lr, float *feature_hr, void *workspace, size_t workspace_bytes, void *stream);
 /* feature_lr [h][w][256] (pitch ld) -> outs[s] [h][w][last_ch] for every stack s with outs[s] != NULL (HOST array of num_stack device
@@ -233,7 +271,7 @@ int surs_encoder_filter_lr(const SursEncoderNet *net, const float *feature_lr, i
 /* feature_hr [h][w][64] (pitch ld) -> out [h][w][64] */
 int surs_encoder_filter_hr(const SursEncoderNet *net, const float *feature_hr, int h, int w, int ld, float *out, void *stream);
 /* the three in the order gen_mesh runs them (lib/train_util.py:57-59): image [h][w][3] -> feature_lr, feature_hr (kept: the caller's
- * buffers), im_feat_lr [h/2][w/2][last_ch] (last stack), im_feat_hr [2h][2w][64] */
+ * buffers), im_feat_lr [h/2][w/2][last_ch] (last stack), im_feat_hr [2h][2w][64]; with net->sr_scale = s: [sh/4][sw/4] and [sh][sw] */
 int surs_encoder_forward(const SursEncoderNet *net, const float *image, int h, int w, int x_ld, float *feature_lr, float *feature_hr,
                          float *im_feat_lr, float *im_feat_hr, void *workspace, size_t workspace_bytes,
                          const SursEncoderStreams *streams, void *stream);

@@ -51,6 +51,11 @@ class GroupNorm(C.Structure):
     _fields_ = [("gamma", C.c_void_p), ("beta", C.c_void_p)]
 
 
+class BatchNorm(C.Structure):
+    """SursBatchNorm of include/surs.h: BatchNorm2d in eval mode folded to y = x * scale + shift."""
+    _fields_ = [("scale", C.c_void_p), ("shift", C.c_void_p)]
+
+
 class ConvBlock(C.Structure):
     _fields_ = [("conv", Conv * 3), ("bn", GroupNorm * 3)]
 
@@ -64,7 +69,15 @@ class EncoderNet(C.Structure):
                 ("ups2", Conv), ("ups3", Conv), ("ups4", Conv), ("last0", Conv), ("last2", Conv),
                 ("body", C.POINTER(Conv)), ("conv5", Conv), ("conv2", ConvBlock), ("hg", C.POINTER(ConvBlock)),
                 ("top_m", C.POINTER(ConvBlock)), ("conv_last", C.POINTER(Conv)), ("l", C.POINTER(Conv)), ("next", C.POINTER(Conv)),
-                ("bn_end", C.POINTER(GroupNorm))]
+                ("bn_end", C.POINTER(GroupNorm)),
+                # read only with ENC_EXTENDED in flags: --norm, --scale and the folded BatchNorm coefficients per norm site
+                ("norm", C.c_int), ("sr_scale", C.c_int), ("bn_conv2", C.POINTER(BatchNorm)), ("bn_hg", C.POINTER(BatchNorm)),
+                ("bn_top_m", C.POINTER(BatchNorm)), ("bn_end_bn", C.POINTER(BatchNorm))]
+
+
+ENC_SEPARATE_SUM, ENC_EXTENDED = 1, 2     # SursEncoderNet.flags
+NORM_GROUP, NORM_BATCH = 0, 1             # SursEncoderNet.norm
+SR_SCALE_MIN, SR_SCALE_MAX = 1, 4         # SursEncoderNet.sr_scale / surs_bicubic_up
 
 
 class EncoderStreams(C.Structure):
@@ -103,6 +116,11 @@ _SIGS = {
     "surs_scale_shift_act": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp]),
     "surs_avgpool2": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "surs_bicubic_up2": (C.c_int, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
+    "surs_bicubic_up": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
+    "surs_bicubic_up2_block": (C.c_int, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
+    "surs_conv2d_nhwc_sum": (C.c_int, [_i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp]),
+    "surs_stats_calls": (C.c_longlong, []),
+    "surs_encoder_workspace_bytes_enlarged": (_sz, [C.POINTER(EncoderNet), _i, _i]),
     "surs_pixel_shuffle2": (C.c_int, [_vp, _i, _i, _i, _i, _f, _vp, _i, _vp]),
     "surs_add3": (C.c_int, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp]),
     "surs_image_prepare": (C.c_int, [_vp, _vp, _i, _i, _vp, _i, _vp]),

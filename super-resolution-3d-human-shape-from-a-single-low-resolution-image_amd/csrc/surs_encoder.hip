@@ -17,6 +17,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <utility>
@@ -1267,6 +1268,42 @@ __global__ void bicubic_up2_kernel(const float *__restrict__ x, int h, int w, in
     y[pix * y_ld + ch] = acc;
 }
 
+// Bicubic by an integer factor s (PyTorch's upsample_bicubic2d: A = -0.75, border-clamped taps), one output element per thread.  The
+// source coordinate is formed the way PyTorch forms it, in fp32 with a separately rounded multiply and subtract - (float)(1 / s) *
+// (dst + 0.5) - 0.5 -: for s = 3 that coordinate is not exactly periodic in dst, and weights taken from the exact phase dst mod s
+// differ from nn.Upsample's by 7e-6 of the range (64 -> 192), a contracted multiply-add by as much.
+__global__ void bicubic_up_kernel(const float *__restrict__ x, int h, int w, int c, int x_ld, int s, int align_corners,
+                                  const float *__restrict__ addend, int add_ld, float *__restrict__ y, int y_ld) {
+    const int ho = s * h, wo = s * w;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)ho * wo * c) return;
+    const int ch = (int)(i % c);
+    const size_t pix = i / c;
+    const int ox = (int)(pix % wo), oy = (int)(pix / wo);
+    const float sy = align_corners ? (ho > 1 ? (float)(h - 1) / (float)(ho - 1) : 0.f) : (float)(1.0 / (double)s);
+    const float sx = align_corners ? (wo > 1 ? (float)(w - 1) / (float)(wo - 1) : 0.f) : sy;
+    const float ry = align_corners ? __fmul_rn(sy, (float)oy) : __fsub_rn(__fmul_rn(sy, (float)oy + 0.5f), 0.5f);
+    const float rx = align_corners ? __fmul_rn(sx, (float)ox) : __fsub_rn(__fmul_rn(sx, (float)ox + 0.5f), 0.5f);
+    const int iy = (int)floorf(ry), ix = (int)floorf(rx);
+    float cy[4], cx[4];
+    cubic_coeffs(ry - (float)iy, cy);
+    cubic_coeffs(rx - (float)ix, cx);
+    float acc = 0.f;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const int yy = min(max(iy - 1 + a, 0), h - 1);
+        float r = 0.f;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int xx = min(max(ix - 1 + b, 0), w - 1);
+            r += cx[b] * x[((size_t)yy * w + xx) * x_ld + ch];
+        }
+        acc += cy[a] * r;
+    }
+    if (addend) acc = addend[pix * add_ld + ch] + acc;
+    y[pix * y_ld + ch] = acc;
+}
+
 __global__ void pixel_shuffle2_kernel(const float *__restrict__ x, int h, int w, int c4, int x_ld, float slope,
                                       float *__restrict__ y, int y_ld) {
     const int c = c4 / 4, ho = 2 * h, wo = 2 * w;
@@ -1567,6 +1604,74 @@ __global__ __launch_bounds__(BB_THREADS) void bicubic_block_stats_kernel(Bicubic
     }
 }
 
+// The block form without statistics (a BatchNorm encoder's hourglass: its normalisations are constants, nobody reads the sums): one
+// item per thread - the 2 x 2 output block of input pixel position i / (c / 4), channels 4 (i % (c / 4)) ..+ 4 -, the expressions of
+// bicubic_block_stats_kernel above, the same bits.  (A kernel of its own rather than a shared item function: with the item factored
+// out the statistics kernel's register allocation moved, and the released encoder's instructions are not to change.)
+__global__ __launch_bounds__(256) void bicubic_block_kernel(BicubicUp2Op op) {
+    const int h = op.h, w = op.w, ho = 2 * h, wo = 2 * w, c4 = op.c / 4;
+    const unsigned n = (unsigned)h * w * c4, i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float sy = op.align_corners ? (ho > 1 ? (float)(h - 1) / (float)(ho - 1) : 0.f) : 0.5f;
+    const float sx = op.align_corners ? (wo > 1 ? (float)(w - 1) / (float)(wo - 1) : 0.f) : 0.5f;
+    const unsigned blk = i / c4, q = i - blk * c4;
+    const int by = (int)(blk / w), bx = (int)(blk - (unsigned)by * w);
+    int iy[2], ix[2];
+    float cy[2][4], cx[2][4];
+#pragma unroll
+    for (int d = 0; d < 2; ++d) {
+        const int oy = 2 * by + d, ox = 2 * bx + d;
+        const float ry = op.align_corners ? sy * (float)oy : sy * ((float)oy + 0.5f) - 0.5f;
+        const float rx = op.align_corners ? sx * (float)ox : sx * ((float)ox + 0.5f) - 0.5f;
+        iy[d] = (int)floorf(ry);
+        ix[d] = (int)floorf(rx);
+        cubic_coeffs(ry - (float)iy[d], cy[d]);
+        cubic_coeffs(rx - (float)ix[d], cx[d]);
+    }
+    const int dy = iy[1] - iy[0], dx = ix[1] - ix[0];   // 0 or 1
+    // horizontal sums of the window's five rows for both output columns
+    f32x4 r[5][2];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const int yy = min(max(iy[0] - 1 + k, 0), h - 1);
+        const float *rowp = op.x + (size_t)yy * w * op.x_ld + 4 * q;
+        f32x4 v[5];
+#pragma unroll
+        for (int m = 0; m < 5; ++m) v[m] = *reinterpret_cast<const f32x4 *>(rowp + (size_t)min(max(ix[0] - 1 + m, 0), w - 1) * op.x_ld);
+        f32x4 r0 = {0.f, 0.f, 0.f, 0.f}, r1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const f32x4 u = dx ? v[b + 1] : v[b];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                r0[e] += cx[0][b] * v[b][e];
+                r1[e] += cx[1][b] * u[e];
+            }
+        }
+        r[k][0] = r0;
+        r[k][1] = r1;
+    }
+#pragma unroll
+    for (int d = 0; d < 2; ++d)        // output row 2 by + d: window rows a + (d ? dy : 0)
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {  // output column 2 bx + g
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                const f32x4 rr = (d && dy) ? r[a + 1][g] : r[a][g];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[e] += cy[d][a] * rr[e];
+            }
+            const size_t pix = (size_t)(2 * by + d) * wo + (2 * bx + g);
+            if (op.addend) {
+                const f32x4 ad = *reinterpret_cast<const f32x4 *>(op.addend + pix * op.add_ld + 4 * q);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[e] = ad[e] + acc[e];
+            }
+            *reinterpret_cast<f32x4 *>(op.y + pix * op.y_ld + 4 * q) = acc;
+        }
+}
+
 __global__ void nchw_to_nhwc_kernel(const float *__restrict__ x, int c, size_t hw, float *__restrict__ y, int y_ld) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= hw * c) return;
@@ -1655,6 +1760,11 @@ extern "C" int surs_conv2d_nhwc_x3(const float *x, int h, int w, int cin, int x_
     return launch_conv_x3<3, 1, 3>(a, (const unsigned short *)wsplit, as_stream(stream));
 }
 
+// Calls into the entry points that compute or consume GroupNorm statistics (process-wide): what a BatchNorm encoder must leave untouched.
+static std::atomic<long long> g_stats_calls{0};
+static void count_stats_call() { g_stats_calls.fetch_add(1, std::memory_order_relaxed); }
+extern "C" long long surs_stats_calls(void) { return g_stats_calls.load(std::memory_order_relaxed); }
+
 struct GnLink {   // GroupNorm(32) statistics handed from kernel to kernel (ConvArgs)
     const double *in; int in_slots; const float *gamma, *beta; float eps;
     double *out; int out_capacity; int *out_slots;
@@ -1683,6 +1793,7 @@ extern "C" int surs_conv2d_nhwc_gn(int parts, const float *x, int h, int w, int 
                                    float *y, int cout, int y_ld, int ksize, int stride, const double *gn_in, int gn_in_slots,
                                    const float *gamma, const float *beta, float eps, int act, float slope, const float *residual,
                                    int res_ld, double *gn_out, int gn_out_capacity, int *gn_out_slots, void *stream) {
+    count_stats_call();
     SURS_REQUIRE(parts == 1 || parts == 2, "one or two f16 parts");
     GnLink gn = {gn_in, gn_in_slots, gamma, beta, eps, gn_out, gn_out_capacity, gn_out_slots};
     return conv2d_split_f16(parts, x, h, w, cin, x_ld, wsplit, bias, y, cout, y_ld, ksize, stride, nullptr, nullptr, act, slope, residual,
@@ -1738,11 +1849,11 @@ static int conv2d_split_f16(int parts, const float *x, int h, int w, int cin, in
 }
 
 // One convolution of a ConvBlock (lib/model/HGFilters.py:57-73) with the block's closing sum in its epilogue: see include/surs.h.
-extern "C" int surs_conv2d_nhwc_gn_sum(int parts, const float *x, int h, int w, int cin, int x_ld, const void *wsplit, const float *bias,
-                                       const SursGnStats *gn_in, const float *in_scale, const float *in_shift, const float *gamma,
-                                       const float *beta, float eps, float *y, int cout, int y_ld, SursGnStats *gn_out,
-                                       const float *residual, int res_ld, float *y2, int y2_ld, double *gn_out2, int gn2_pitch, int gn2_g0,
-                                       int gn2_cg, int *gn2_slots, void *stream) {
+static int conv2d_sum(int parts, const float *x, int h, int w, int cin, int x_ld, const void *wsplit, const float *bias,
+                      const SursGnStats *gn_in, const float *in_scale, const float *in_shift, const float *gamma,
+                      const float *beta, float eps, float *y, int cout, int y_ld, SursGnStats *gn_out,
+                      const float *residual, int res_ld, float *y2, int y2_ld, double *gn_out2, int gn2_pitch, int gn2_g0,
+                      int gn2_cg, int *gn2_slots, void *stream) {
     SURS_REQUIRE(parts == 1 || parts == 2, "one or two f16 parts");
     SURS_REQUIRE(x && wsplit && y2 && residual, "null argument (the sum needs its second operand and its output)");
     SURS_REQUIRE(h > 0 && w > 0 && cin > 0 && cout > 0 && x_ld >= cin && y2_ld >= cout && (!y || y_ld >= cout), "bad sizes");
@@ -1791,6 +1902,25 @@ extern "C" int surs_conv2d_nhwc_gn_sum(int parts, const float *x, int h, int w, 
     return launch_conv_x3<3, 1, 2>(a, (const unsigned short *)wsplit, as_stream(stream));
 }
 
+extern "C" int surs_conv2d_nhwc_gn_sum(int parts, const float *x, int h, int w, int cin, int x_ld, const void *wsplit, const float *bias,
+                                       const SursGnStats *gn_in, const float *in_scale, const float *in_shift, const float *gamma,
+                                       const float *beta, float eps, float *y, int cout, int y_ld, SursGnStats *gn_out,
+                                       const float *residual, int res_ld, float *y2, int y2_ld, double *gn_out2, int gn2_pitch, int gn2_g0,
+                                       int gn2_cg, int *gn2_slots, void *stream) {
+    count_stats_call();
+    return conv2d_sum(parts, x, h, w, cin, x_ld, wsplit, bias, gn_in, in_scale, in_shift, gamma, beta, eps, y, cout, y_ld, gn_out, residual,
+                      res_ld, y2, y2_ld, gn_out2, gn2_pitch, gn2_g0, gn2_cg, gn2_slots, stream);
+}
+
+// The same convolution without any statistics (BatchNorm in eval mode: constant coefficients in, nothing to hand on): the kernel's
+// epilogue instantiation that stores the two outputs and sums nothing.
+extern "C" int surs_conv2d_nhwc_sum(int parts, const float *x, int h, int w, int cin, int x_ld, const void *wsplit, const float *bias,
+                                    const float *in_scale, const float *in_shift, float *y, int cout, int y_ld, const float *residual,
+                                    int res_ld, float *y2, int y2_ld, void *stream) {
+    return conv2d_sum(parts, x, h, w, cin, x_ld, wsplit, bias, nullptr, in_scale, in_shift, nullptr, nullptr, 0.0f, y, cout, y_ld, nullptr,
+                      residual, res_ld, y2, y2_ld, nullptr, 0, 0, 0, nullptr, stream);
+}
+
 extern "C" int surs_groupnorm_coeffs_ws(const float *x, int hw, int c, int x_ld, int groups, float eps, const float *gamma,
                                         const float *beta, float *scale, float *shift, void *scratch, void *stream);
 
@@ -1823,6 +1953,7 @@ extern "C" size_t surs_groupnorm_scratch_bytes(void) { return sizeof(double) * 6
 
 extern "C" int surs_groupnorm_coeffs_ws(const float *x, int hw, int c, int x_ld, int groups, float eps, const float *gamma,
                                         const float *beta, float *scale, float *shift, void *scratch, void *stream) {
+    count_stats_call();
     SURS_REQUIRE(x && gamma && beta && scale && shift && scratch, "null argument");
     SURS_REQUIRE(groups > 0 && groups <= 64 && c % groups == 0 && hw > 0, "bad GroupNorm shape");
     SURS_REQUIRE(c % 4 == 0 && x_ld % 4 == 0 && (reinterpret_cast<size_t>(x) & 15) == 0 && c <= 1024,
@@ -1896,6 +2027,29 @@ extern "C" int surs_bicubic_up2(const float *x, int h, int w, int c, int x_ld, i
     return 0;
 }
 
+extern "C" int surs_bicubic_up(const float *x, int h, int w, int c, int x_ld, int scale, int align_corners, const float *addend,
+                               int add_ld, float *y, int y_ld, void *stream) {
+    SURS_REQUIRE(scale >= SURS_SR_SCALE_MIN && scale <= SURS_SR_SCALE_MAX, "scale %d: the super-resolution factor must be an integer in 1..4", scale);
+    if (scale == 2) return surs_bicubic_up2(x, h, w, c, x_ld, align_corners, addend, add_ld, y, y_ld, stream);   // (the released factor: its kernels, its bits)
+    SURS_REQUIRE(x && y && h > 0 && w > 0 && c > 0 && x_ld >= c && y_ld >= c && (!addend || add_ld >= c), "bad argument");
+    SURS_REQUIRE((long long)scale * h * scale * w * c < (1ll << 40), "map too large");
+    hipLaunchKernelGGL(bicubic_up_kernel, dim3(blocks_for((size_t)scale * h * scale * w * c)), dim3(256), 0, as_stream(stream), x, h, w, c,
+                       x_ld, scale, align_corners, addend, add_ld, y, y_ld);
+    SURS_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int surs_bicubic_up2_block(const float *x, int h, int w, int c, int x_ld, int align_corners, const float *addend, int add_ld,
+                                      float *y, int y_ld, void *stream) {
+    SURS_REQUIRE(x && y && h > 0 && w > 0 && c > 0, "bad argument");
+    SURS_REQUIRE(c % 4 == 0 && vec4_fits(x, x_ld) && vec4_fits(y, y_ld) && (!addend || vec4_fits(addend, add_ld)) && x_ld >= c && y_ld >= c &&
+                 (long long)h * w * (c / 4) < (1ll << 32), "the block form needs 16-byte aligned rows");
+    hipLaunchKernelGGL(bicubic_block_kernel, dim3(blocks_for((size_t)h * w * (c / 4))), dim3(256), 0, as_stream(stream),
+                       BicubicUp2Op{x, h, w, c, x_ld, align_corners, addend, add_ld, y, y_ld});
+    SURS_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int surs_pixel_shuffle2(const float *x, int h, int w, int c4, int x_ld, float slope, float *y, int y_ld,
                                    void *stream) {
     SURS_REQUIRE(x && y && c4 % 4 == 0, "bad argument");
@@ -1943,6 +2097,7 @@ static int launch_vec4_stats(const Op &op, size_t items, int c, double *gn_out, 
 
 extern "C" int surs_avgpool2_gn(const float *x, int h, int w, int c, int x_ld, float *y, int y_ld, double *gn_out, int gn_out_capacity,
                                 int *gn_out_slots, void *stream) {
+    count_stats_call();
     SURS_REQUIRE(x && y && h >= 2 && w >= 2, "bad argument");
     SURS_REQUIRE(c % 4 == 0 && vec4_fits(x, x_ld) && vec4_fits(y, y_ld), "the statistics form needs 16-byte aligned rows");
     return launch_vec4_stats(AvgPool2Op{x, h, w, c, x_ld, y, y_ld}, (size_t)(h / 2) * (w / 2) * (c / 4), c, gn_out, gn_out_capacity,
@@ -1951,6 +2106,7 @@ extern "C" int surs_avgpool2_gn(const float *x, int h, int w, int c, int x_ld, f
 
 extern "C" int surs_bicubic_up2_gn(const float *x, int h, int w, int c, int x_ld, int align_corners, const float *addend, int add_ld,
                                    float *y, int y_ld, double *gn_out, int gn_out_capacity, int *gn_out_slots, void *stream) {
+    count_stats_call();
     SURS_REQUIRE(x && y && h > 0 && w > 0, "bad argument");
     SURS_REQUIRE(c % 4 == 0 && vec4_fits(x, x_ld) && vec4_fits(y, y_ld) && (!addend || vec4_fits(addend, add_ld)),
                  "the statistics form needs 16-byte aligned rows");
@@ -1976,6 +2132,7 @@ extern "C" int surs_bicubic_up2_gn(const float *x, int h, int w, int c, int x_ld
 
 extern "C" int surs_add3_gn(const float *a, int a_ld, const float *b, int b_ld, const float *c, int c_ld, int hw, int ch, float *y, int y_ld,
                             double *gn_out, int gn_out_capacity, int *gn_out_slots, void *stream) {
+    count_stats_call();
     SURS_REQUIRE(a && b && y && hw > 0, "bad argument");
     SURS_REQUIRE(ch % 4 == 0 && vec4_fits(a, a_ld) && vec4_fits(b, b_ld) && (!c || vec4_fits(c, c_ld)) && vec4_fits(y, y_ld),
                  "the statistics form needs 16-byte aligned rows");

@@ -53,6 +53,9 @@ struct Run {
     int parts;           // 2 (fp32-grade) or 1 (one f16 product per MAC in the 3x3 convolutions)
     bool dry;
     int rc = 0;
+    // --norm batch: every norm site is y = x * scale + shift with constant coefficients (SursEncoderNet.bn_*): no map carries
+    // statistics, no kernel computes any
+    bool bn() const { return (net->flags & SURS_ENC_EXTENDED) && net->norm == SURS_NORM_BATCH; }
 
     Map map(int h, int w, int c) {
         Map m;
@@ -68,6 +71,10 @@ struct Run {
 };
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<size_t>(p) & 15) == 0; }
+
+// --scale: the bicubic enlargement in front of the super-resolution net (2 for callers without the extended fields)
+inline int sr_scale(const SursEncoderNet *n) { return ((n->flags & SURS_ENC_EXTENDED) && n->sr_scale) ? n->sr_scale : 2; }
+inline int per_stack_blocks(const SursEncoderNet *n) { return 3 * n->hg_depth + 1; }
 
 // native.conv2d of encoder.py: the split-f16 kernels where they apply, the fp32 MFMA / direct kernels otherwise
 void conv(Run &r, const Map &x, const SursConv &cw, Map &out, int stride, int act, float slope, const Map *residual,
@@ -154,6 +161,19 @@ void bicubic_up2(Run &r, const Map &x, bool align_corners, const Map *addend, Ma
     out.set_stats(sb, slots);
 }
 
+// the statistics-free 2 x 2-block form (a BatchNorm hourglass's up1 + up2)
+void bicubic_up2_block(Run &r, const Map &x, bool align_corners, const Map *addend, Map &out) {
+    out.set_stats(nullptr, 0);
+    if (r.dry || r.rc) return;
+    r.fail(surs_bicubic_up2_block(x.p, x.h, x.w, x.c, x.ld, align_corners, addend ? addend->p : nullptr, addend ? addend->ld : 0, out.p, out.ld, r.st));
+}
+
+void bicubic_up(Run &r, const Map &x, int scale, Map &out) {
+    out.set_stats(nullptr, 0);
+    if (r.dry || r.rc) return;
+    r.fail(surs_bicubic_up(x.p, x.h, x.w, x.c, x.ld, scale, 0, nullptr, 0, out.p, out.ld, r.st));
+}
+
 void pixel_shuffle2(Run &r, const Map &x, float slope, Map &out) {
     out.set_stats(nullptr, 0);
     if (r.dry || r.rc) return;
@@ -164,16 +184,17 @@ constexpr int ACT = 1;
 constexpr float LRELU = 0.2f, RELU = 0.0f;
 
 // ---------------------------------------------------------------- SuRSSR_v3.forward (lib/model/SuRSSR_v3.py:143-181)
-void super_res(Run &r, const Map &x, bool want_image, float *img_sr, float *feature_lr, float *feature_hr) {
+// H2 x W2: the enlarged image (sr_scale times x; a dry run reads nothing else of x)
+void super_res(Run &r, const Map &x, int H2, int W2, bool want_image, float *img_sr, float *feature_lr, float *feature_hr) {
     const SursEncoderNet &n = *r.net;
-    const int H2 = 2 * x.h, W2 = 2 * x.w;
     Map fin = r.map(H2, W2, 64);               // cat(h, up3)
-    Map new3 = r.map(x.h, x.w, 128);           // cat(d1_f, up2)
+    Map new3 = r.map(H2 / 2, W2 / 2, 128);     // cat(d1_f, up2)
     Map new2;                                  // cat(d2_f, up1) -> feature_lr: the caller's buffer
-    new2.p = feature_lr; new2.h = x.h / 2; new2.w = x.w / 2; new2.c = new2.ld = 256;
-    Map new1 = r.map(x.h / 4, x.w / 4, 512);   // cat(d3_f, bo)
+    new2.p = feature_lr; new2.h = H2 / 4; new2.w = W2 / 4; new2.c = new2.ld = 256;
+    Map new1 = r.map(H2 / 8, W2 / 8, 512);     // cat(d3_f, bo)
     Map up = r.map(H2, W2, 3);
-    bicubic_up2(r, x, false, nullptr, up, false);
+    if (sr_scale(&n) == 2) bicubic_up2(r, x, false, nullptr, up, false);
+    else bicubic_up(r, x, sr_scale(&n), up);
     Map h = fin.slice(0, 32);
     conv(r, up, n.head, h, 1, ACT, LRELU, nullptr);
 
@@ -236,6 +257,16 @@ void super_res(Run &r, const Map &x, bool want_image, float *img_sr, float *feat
 // SURS_ENC_SEPARATE_SUM (net->flags): the four-launch form of rounds 4 - 5 (convolutions into the slices, then surs_add3_gn), whose
 // bits encoder.py's sequencing reproduces.  A first block (x without statistics) takes GroupNorm coefficients from
 // surs_groupnorm_coeffs' two launches in front of its first convolution (in front of all three in the separate-sum form).
+// The folded BatchNorm coefficients (bn1, bn2, bn3) of a ConvBlock of the net, by the array the block lives in; null: GroupNorm.
+const SursBatchNorm *batchnorm_of(const Run &r, const SursConvBlock *b) {
+    const SursEncoderNet &n = *r.net;
+    if (!r.bn()) return nullptr;
+    if (b == &n.conv2) return n.bn_conv2;
+    const ptrdiff_t nhg = (ptrdiff_t)n.num_stack * per_stack_blocks(&n);
+    if (b >= n.hg && b < n.hg + nhg) return n.bn_hg + 3 * (b - n.hg);
+    return n.bn_top_m + 3 * (b - n.top_m);
+}
+
 Map conv_block(Run &r, const SursConvBlock &b, const Map &x, bool want_stats) {
     const int c = x.c;
     Map out = r.map(x.h, x.w, c);
@@ -254,6 +285,29 @@ Map conv_block(Run &r, const SursConvBlock &b, const Map &x, bool want_stats) {
     //  of a 512 x 512 image's hourglass; smaller ones take the separate sum)
     const bool sum_in_conv = fused && !(r.net->flags & SURS_ENC_SEPARATE_SUM) && b.conv[0].ksize == 3 && b.conv[1].ksize == 3 &&
                              b.conv[2].ksize == 3 && x.w % 32 == 0 && x.h % 8 == 0 && c % 256 == 0;
+    if (const SursBatchNorm *bn = batchnorm_of(r, &b)) {
+        // BatchNorm in eval mode: the three normalisations are the caller's constants in the convolutions' staging, the same launches
+        // without a statistics epilogue, buffer or fold
+        out.set_stats(nullptr, 0);
+        if (sum_in_conv) {
+            Map raw1 = r.map(x.h, x.w, c / 2), raw2 = r.map(x.h, x.w, c / 4);
+            if (r.dry || r.rc) return out;
+            r.fail(surs_conv2d_nhwc_sum(r.parts, x.p, x.h, x.w, c, x.ld, b.conv[0].w_split, b.conv[0].bias, bn[0].scale, bn[0].shift, raw1.p, c / 2,
+                                        raw1.ld, x.p, x.ld, o1.p, out.ld, r.st));
+            if (!r.rc)
+                r.fail(surs_conv2d_nhwc_sum(r.parts, raw1.p, x.h, x.w, c / 2, raw1.ld, b.conv[1].w_split, b.conv[1].bias, bn[1].scale, bn[1].shift,
+                                            raw2.p, c / 4, raw2.ld, x.p + c / 2, x.ld, o2.p, out.ld, r.st));
+            if (!r.rc)
+                r.fail(surs_conv2d_nhwc_sum(r.parts, raw2.p, x.h, x.w, c / 4, raw2.ld, b.conv[2].w_split, b.conv[2].bias, bn[2].scale, bn[2].shift,
+                                            nullptr, c / 4, 0, x.p + 3 * c / 4, x.ld, o3.p, out.ld, r.st));
+            return out;
+        }
+        const Map ins[3] = {x, o1, o2};
+        Map outs[3] = {o1, o2, o3};
+        for (int k = 0; k < 3; ++k) conv(r, ins[k], b.conv[k], outs[k], 1, 0, 0.0f, nullptr, bn[k].scale, bn[k].shift);
+        add3(r, out, x, out, false);
+        return out;
+    }
     if (sum_in_conv) {
         const int cap = ((x.w + 31) / 32) * ((x.h + 3) / 4), cg = c / 32;
         Map raw1 = r.map(x.h, x.w, c / 2), raw2 = r.map(x.h, x.w, c / 4);
@@ -334,7 +388,7 @@ Map hourglass(Run &r, const SursConvBlock *blocks, int depth, const Map &x, cons
     struct Fwd {
         Run &r; Level *lv; const SursEncoderStreams *ss; int *ev;
         Map low_branch(int level, const Map &inp) {
-            Map pooled = avgpool2(r, inp, true);
+            Map pooled = avgpool2(r, inp, !r.bn());
             Map low1 = conv_block(r, *lv[level].b2, pooled, true);
             Map low2;
             if (level > 1) low2 = run(level - 1, low1);
@@ -365,7 +419,8 @@ Map hourglass(Run &r, const SursConvBlock *blocks, int depth, const Map &x, cons
                 low3 = low_branch(level, inp);
             }
             Map out = r.map(2 * low3.h, 2 * low3.w, low3.c);
-            bicubic_up2(r, low3, true, &up1, out, true);   // up1 + up2
+            if (r.bn()) bicubic_up2_block(r, low3, true, &up1, out);
+            else bicubic_up2(r, low3, true, &up1, out, true);   // up1 + up2
             return out;
         }
     } f{r, lv, ss, &ev};
@@ -378,9 +433,7 @@ Map hourglass(Run &r, const SursConvBlock *blocks, int depth, const Map &x, cons
 // (`next`, packed by the caller: W = W_bl + W_al W_l) with the sum in its epilogue.
 void filter_lr(Run &r, const Map &feature_lr, float *const *outs, const SursEncoderStreams *ss, Arena *arenas /* [2] */) {
     const SursEncoderNet &n = *r.net;
-    int per_stack = 0;
-    for (int l = n.hg_depth; l >= 1; --l) per_stack += 3;
-    per_stack += 1;   // b2_plus_1
+    const int per_stack = per_stack_blocks(&n);   // three per level + b2_plus_1
     r.a = &arenas[1];
     Map previous = conv_block(r, n.conv2, feature_lr, true);
     for (int s = 0; s < n.num_stack; ++s) {
@@ -390,6 +443,21 @@ void filter_lr(Run &r, const Map &feature_lr, float *const *outs, const SursEnco
         Map ll = conv_block(r, n.top_m[s], hg, false);
         const bool last = s == n.num_stack - 1;
         Map t = r.map(ll.h, ll.w, n.conv_last[s].cout);
+        if (r.bn()) {   // the same pointwise launches with bn_end's constants, no statistics
+            const SursBatchNorm &be = n.bn_end_bn[s];
+            conv(r, ll, n.conv_last[s], t, 1, 0, 0.0f, nullptr);
+            if (outs[s]) {
+                Map o;
+                o.p = outs[s]; o.h = t.h; o.w = t.w; o.c = o.ld = n.l[s].cout;
+                conv(r, t, n.l[s], o, 1, 0, 0.0f, nullptr, be.scale, be.shift);
+            }
+            if (!last) {
+                Map nx = r.map(t.h, t.w, n.next[s].cout);
+                conv(r, t, n.next[s], nx, 1, 0, 0.0f, &previous, be.scale, be.shift);
+                previous = nx;
+            }
+            continue;
+        }
         conv_gn(r, ll, n.conv_last[s], t, nullptr, true);
         if (outs[s]) {
             Map o;
@@ -408,8 +476,35 @@ int check_net(const SursEncoderNet *n) {
     SURS_REQUIRE(n, "null network");
     SURS_REQUIRE(n->num_stack >= 1 && n->num_stack <= 16 && n->hg_depth >= 1 && n->hg_depth <= 4, "1..16 stacks, hourglass depth 1..4");
     SURS_REQUIRE(n->parts == 1 || n->parts == 2, "parts: 2 (fp32-grade) or 1");
-    SURS_REQUIRE((n->flags & ~SURS_ENC_SEPARATE_SUM) == 0, "unknown flags");
+    SURS_REQUIRE((n->flags & ~(SURS_ENC_SEPARATE_SUM | SURS_ENC_EXTENDED)) == 0, "unknown flags");
     for (int i = 0; i < 3; ++i) SURS_REQUIRE(n->n_block[i] >= 0 && n->n_block[i] <= 64, "bad n_block");
+    if (!(n->flags & SURS_ENC_EXTENDED)) return 0;
+    SURS_REQUIRE(n->norm == SURS_NORM_GROUP || n->norm == SURS_NORM_BATCH, "norm %d: the supported values are 'group' and 'batch'", n->norm);
+    SURS_REQUIRE(n->sr_scale == 0 || (n->sr_scale >= SURS_SR_SCALE_MIN && n->sr_scale <= SURS_SR_SCALE_MAX),
+                 "scale %d: the super-resolution factor must be an integer in 1..4", n->sr_scale);
+    if (n->norm == SURS_NORM_BATCH) {
+        SURS_REQUIRE(n->bn_conv2 && n->bn_hg && n->bn_top_m && n->bn_end_bn && n->hg && n->top_m, "BatchNorm net: null coefficient array");
+        auto filled = [](const SursBatchNorm *a, int count) {
+            for (int i = 0; i < count; ++i)
+                if (!a[i].scale || !a[i].shift) return false;
+            return true;
+        };
+        SURS_REQUIRE(filled(n->bn_conv2, 3) && filled(n->bn_hg, 3 * n->num_stack * per_stack_blocks(n)) && filled(n->bn_top_m, 3 * n->num_stack) &&
+                     filled(n->bn_end_bn, n->num_stack), "BatchNorm net: a norm site without folded coefficients");
+    }
+    return 0;
+}
+
+// the size rule of the three stride-2 stages, on the enlarged image; factor 2: in its words of old, on the input
+int check_image_size(const SursEncoderNet *n, int h, int w) {
+    const int s = sr_scale(n);
+    if (s == 2) {
+        SURS_REQUIRE(h > 0 && w > 0 && h % 4 == 0 && w % 4 == 0, "input image height/width must be multiples of 4 (three stride-2 stages), got %dx%d", h, w);
+        return 0;
+    }
+    SURS_REQUIRE(h > 0 && w > 0 && (s * h) % 8 == 0 && (s * w) % 8 == 0,
+                 "input image %dx%d enlarged by the factor %d is %dx%d: the enlarged height/width must be multiples of 8 (three stride-2 stages)",
+                 h, w, s, s * h, s * w);
     return 0;
 }
 
@@ -421,30 +516,36 @@ Map input_map(const float *x, int h, int w, int c, int ld) {
 
 }  // namespace
 
-extern "C" size_t surs_encoder_workspace_bytes(const SursEncoderNet *net, int h, int w) {
-    if (!net || h <= 0 || w <= 0 || check_net(net)) return 0;
+extern "C" size_t surs_encoder_workspace_bytes_enlarged(const SursEncoderNet *net, int eh, int ew) {
+    if (!net || eh <= 0 || ew <= 0 || check_net(net)) return 0;
     // the stages run one after the other on one workspace: the largest of them; filter_lr = two arenas
     Arena a;
     a.dry = true;
     Run r{net, &a, nullptr, net->parts, true};
-    super_res(r, input_map(nullptr, h, w, 3, 3), true, nullptr, reinterpret_cast<float *>(4096), reinterpret_cast<float *>(4096));
+    super_res(r, input_map(nullptr, 0, 0, 3, 3), eh, ew, true, nullptr, reinterpret_cast<float *>(4096), reinterpret_cast<float *>(4096));
     const size_t sr = align_up(a.peak, 256);
     Arena ar[2];
     ar[0].dry = ar[1].dry = true;
     Run r2{net, &ar[0], nullptr, net->parts, true};
     float *outs[16];
     for (int s = 0; s < 16; ++s) outs[s] = reinterpret_cast<float *>(4096);
-    filter_lr(r2, input_map(reinterpret_cast<const float *>(4096), h / 2, w / 2, 256, 256), outs, nullptr, ar);
+    filter_lr(r2, input_map(reinterpret_cast<const float *>(4096), eh / 4, ew / 4, 256, 256), outs, nullptr, ar);
     const size_t half = align_up(ar[0].peak > ar[1].peak ? ar[0].peak : ar[1].peak, 256);
     return (sr > 2 * half ? sr : 2 * half) + 256;
+}
+
+extern "C" size_t surs_encoder_workspace_bytes(const SursEncoderNet *net, int h, int w) {
+    if (!net || h <= 0 || w <= 0 || check_net(net)) return 0;
+    return surs_encoder_workspace_bytes_enlarged(net, sr_scale(net) * h, sr_scale(net) * w);
 }
 
 extern "C" int surs_encoder_super_res(const SursEncoderNet *net, const float *x, int h, int w, int x_ld, int want_image, float *img_sr,
                                       float *feature_lr, float *feature_hr, void *workspace, size_t workspace_bytes, void *stream) {
     if (int rc = check_net(net)) return rc;
     SURS_REQUIRE(x && feature_lr && feature_hr && workspace && (!want_image || img_sr), "null argument");
-    SURS_REQUIRE(h > 0 && w > 0 && h % 4 == 0 && w % 4 == 0 && x_ld >= 3,
-                 "input image height/width must be multiples of 4 (three stride-2 stages), got %dx%d", h, w);
+    if (int rc = check_image_size(net, h, w)) return rc;
+    SURS_REQUIRE(x_ld >= 3, "input image: three channels");
+    const int eh = sr_scale(net) * h, ew = sr_scale(net) * w;
     Arena a;
     a.base = (char *)align_up((size_t)workspace, 256);
     a.cap = workspace_bytes - (size_t)(a.base - (char *)workspace);
@@ -452,11 +553,11 @@ extern "C" int surs_encoder_super_res(const SursEncoderNet *net, const float *x,
         Arena d;
         d.dry = true;
         Run rd{net, &d, nullptr, net->parts, true};
-        super_res(rd, input_map(nullptr, h, w, 3, 3), want_image != 0, nullptr, reinterpret_cast<float *>(4096), reinterpret_cast<float *>(4096));
+        super_res(rd, input_map(nullptr, h, w, 3, 3), eh, ew, want_image != 0, nullptr, reinterpret_cast<float *>(4096), reinterpret_cast<float *>(4096));
         SURS_REQUIRE(d.peak <= a.cap, "workspace too small: %zu bytes needed", d.peak + 256);
     }
     Run r{net, &a, as_stream(stream), net->parts, false};
-    super_res(r, input_map(x, h, w, 3, x_ld), want_image != 0, img_sr, feature_lr, feature_hr);
+    super_res(r, input_map(x, h, w, 3, x_ld), eh, ew, want_image != 0, img_sr, feature_lr, feature_hr);
     return r.rc;
 }
 
@@ -501,8 +602,9 @@ extern "C" int surs_encoder_forward(const SursEncoderNet *net, const float *imag
     SURS_REQUIRE(im_feat_lr && im_feat_hr, "null argument");
     int rc = surs_encoder_super_res(net, image, h, w, x_ld, 0, nullptr, feature_lr, feature_hr, workspace, workspace_bytes, stream);
     if (rc) return rc;
-    if ((rc = surs_encoder_filter_hr(net, feature_hr, 2 * h, 2 * w, 64, im_feat_hr, stream))) return rc;
+    const int eh = sr_scale(net) * h, ew = sr_scale(net) * w;
+    if ((rc = surs_encoder_filter_hr(net, feature_hr, eh, ew, 64, im_feat_hr, stream))) return rc;
     float *outs[16] = {};
     outs[net->num_stack - 1] = im_feat_lr;
-    return surs_encoder_filter_lr(net, feature_lr, h / 2, w / 2, 256, outs, workspace, workspace_bytes, streams, stream);
+    return surs_encoder_filter_lr(net, feature_lr, eh / 4, ew / 4, 256, outs, workspace, workspace_bytes, streams, stream);
 }

@@ -293,8 +293,13 @@ def encode_sharded(net, images, calib_tensor, resolution, b_min, b_max, transfor
 
     Leaves net.im_feat_list_lr / im_feat_list_hr as the replicated encoder would, except that im_feat_hr holds zeros outside the
     rank's strip.  Falls back to the replicated encoder (returns False) for one rank, several views, a general calibration, or a
-    width the ranks cannot share in even strips."""
+    width the ranks cannot share in even strips.  A --norm batch encoder shards like a GroupNorm one (filter_lr replicated, its
+    normalisations constants).  --scale other than 2: ValueError - the strip and halo arithmetic (input columns = feature_lr columns
+    x 2) is written for the released factor; run the replicated encoder on every rank, the sharded sweep takes its features."""
     from . import encoder, native
+    if int(getattr(net.opt, "scale", 2)) != 2:
+        raise ValueError("encode_sharded: the strip and halo arithmetic of the sharded super-resolution net is written for --scale 2, "
+                         "not %s: run the replicated encoder (super_res -> filter_hr -> filter_lr on every rank)" % (net.opt.scale,))
     from .model import _as_img, _as_nchw_view
     from .sdf import create_grid
     world, rank = _world(group)

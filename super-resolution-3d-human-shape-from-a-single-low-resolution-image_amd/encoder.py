@@ -13,22 +13,56 @@ import os
 
 import torch
 
-from . import native, settings
+from . import native, settings, weights
 from .native import Img
+
+SR_SCALES = (1, 2, 3, 4)   # --scale: the bicubic enlargement in front of the super-resolution net (SURS_SR_SCALE_MIN..MAX of surs.h)
+
+
+def check_scale(scale):
+    """--scale as the encoder runs it: an integer factor in 1..4 (1: no enlargement), else ValueError."""
+    if isinstance(scale, bool) or not isinstance(scale, (int, np.integer)) or scale not in SR_SCALES:
+        raise ValueError("--scale %s: the super-resolution factor must be an integer in 1..4" % (scale,))
+    return int(scale)
+
+
+def check_image_size(h, w, scale):
+    """The three stride-2 stages of the super-resolution net halve the ENLARGED image three times: scale * h and scale * w must be
+    multiples of 8 (for the released factor 2: the input's multiples of 4, in the words that rule has always had)."""
+    if scale == 2:
+        if h % 4 or w % 4:
+            raise ValueError("input image height/width must be multiples of 4 (three stride-2 stages), got %dx%d" % (h, w))
+    elif (scale * h) % 8 or (scale * w) % 8:
+        raise ValueError("input image %dx%d enlarged by the factor %d is %dx%d: the enlarged height/width must be multiples of 8 "
+                         "(three stride-2 stages)" % (h, w, scale, scale * h, scale * w))
+
+
+def check_feature_lr_size(h, w, hg_depth, scale):
+    """feature_lr (a quarter of the enlarged image) is halved hg_depth times by every hourglass."""
+    if h % (1 << hg_depth) or w % (1 << hg_depth):
+        if scale == 2:
+            raise ValueError("feature_lr size must be a multiple of 2^hg_depth")
+        raise ValueError("feature_lr size must be a multiple of 2^hg_depth = %d: got %dx%d, a quarter of the enlarged image of %dx%d "
+                         "(factor %d: an input image of %gx%g)" % (1 << hg_depth, h, w, 4 * h, 4 * w, scale, 4 * h / scale, 4 * w / scale))
 
 
 _weights_serial = iter(range(1, 1 << 62))
 
 
 class EncoderWeights:
-    """Device-side packed weights of every conv / GroupNorm that is live at eval time."""
+    """Device-side packed weights of every conv / GroupNorm that is live at eval time.  --norm batch: every norm site
+    is nn.BatchNorm2d in EVAL mode - the running statistics, whatever SuRSNet.train() says - folded here, in float64, to the constants
+    scale = weight / sqrt(running_var + 1e-5), shift = bias - running_mean * scale (self.bn); self.gn stays empty."""
 
     def __init__(self, sd, opt, device):
         self.serial = next(_weights_serial)   # the key of this object's captured graphs: never reused, unlike id()
         self.device = device
         self.conv = {}
         self.gn = {}
+        self.bn = {}
         self.opt = opt
+        self.norm = weights.check_norm(getattr(opt, "norm", "group"))
+        self.scale = check_scale(getattr(opt, "scale", 2))
         # --encoder_precision: "fp32" (= "auto", the default) = two f16 parts, three products per MAC: the parity-grade encoder, whatever
         # --precision says about the classifiers (BASELINE configs[2] / [4] name a bf16 / fp16 MLP, not a reduced encoder); "f16" = one
         # f16 product in the 3x3 convolutions (features within 1.8e-3 / 4e-4 of their range, 2 ms of 7 per 512^2 image): opt-in only.
@@ -47,6 +81,10 @@ class EncoderWeights:
                                                  reduced=self.reduced)
 
         def add_gn(name):
+            if self.norm == "batch":
+                sc, sh = weights.fold_batchnorm(*[get(name + "." + k) for k in ("weight", "bias", "running_mean", "running_var")])
+                self.bn[name] = (torch.from_numpy(sc).to(device), torch.from_numpy(sh).to(device))
+                return
             self.gn[name] = (torch.from_numpy(np.ascontiguousarray(get(name + ".weight"), np.float32)).to(device),
                              torch.from_numpy(np.ascontiguousarray(get(name + ".bias"), np.float32)).to(device))
 
@@ -113,11 +151,21 @@ class NativeNet:
             return _lib.Conv(w3.data_ptr() if w3 is not None else None, cw.w.data_ptr(), cw.b.data_ptr() if cw.b is not None else None,
                              cw.cin, cw.cout, cw.k, 0)
 
+        batch = W.norm == "batch"
+        bn_sites = {"conv2": [], "hg": [], "top_m": [], "end": []}   # the folded coefficients, in the order of the block arrays
+
         def gn(name):
+            if batch:
+                return _lib.GroupNorm()
             g, b = W.gn[name]
             return _lib.GroupNorm(g.data_ptr(), b.data_ptr())
 
-        def block(prefix):
+        def bn(kind, names):
+            if batch:
+                bn_sites[kind] += [_lib.BatchNorm(W.bn[k][0].data_ptr(), W.bn[k][1].data_ptr()) for k in names]
+
+        def block(prefix, kind="hg"):
+            bn(kind, [prefix + "bn%d" % i for i in (1, 2, 3)])
             return _lib.ConvBlock((_lib.Conv * 3)(*[conv(prefix + "conv%d" % i) for i in (1, 2, 3)]),
                                   (_lib.GroupNorm * 3)(*[gn(prefix + "bn%d" % i) for i in (1, 2, 3)]))
 
@@ -148,7 +196,7 @@ class NativeNet:
         n.body = array(_lib.Conv, body)
         n.conv5 = conv("image_filter_hr.conv5")
         L = "image_filter_lr."
-        n.conv2 = block(L + "conv2.")
+        n.conv2 = block(L + "conv2.", "conv2")
         hg = []
         for s in range(opt.num_stack_lr):
             def gen(level):
@@ -162,19 +210,28 @@ class NativeNet:
             gen(opt.hg_depth)
         n.hg = array(_lib.ConvBlock, hg)
         S_ = range(opt.num_stack_lr)
-        n.top_m = array(_lib.ConvBlock, [block(L + "top_m_%d." % s) for s in S_])
+        n.top_m = array(_lib.ConvBlock, [block(L + "top_m_%d." % s, "top_m") for s in S_])
         n.conv_last = array(_lib.Conv, [conv(L + "conv_last%d" % s) for s in S_])
         n.l = array(_lib.Conv, [conv(L + "l%d" % s) for s in S_])
         n.next = array(_lib.Conv, [conv(L + "next%d" % s) if s < opt.num_stack_lr - 1 else _lib.Conv() for s in S_])
         n.bn_end = array(_lib.GroupNorm, [gn(L + "bn_end%d" % s) for s in S_])
+        if batch or W.scale != 2:
+            # (the released configuration hands over the struct as it always was: flags without ENC_EXTENDED, the fields behind bn_end unread)
+            n.flags |= _lib.ENC_EXTENDED
+            n.norm, n.sr_scale = (_lib.NORM_BATCH if batch else _lib.NORM_GROUP), W.scale
+            bn("end", [L + "bn_end%d" % s for s in S_])
+            if batch:
+                n.bn_conv2, n.bn_hg = array(_lib.BatchNorm, bn_sites["conv2"]), array(_lib.BatchNorm, bn_sites["hg"])
+                n.bn_top_m, n.bn_end_bn = array(_lib.BatchNorm, bn_sites["top_m"]), array(_lib.BatchNorm, bn_sites["end"])
         self.net = n
         self.last_ch = W.conv[L + "l0"].cout
         self.ws = None
 
-    def workspace(self, h, w, device):
-        """The calls' workspace: one tensor per stream the encoder runs on (two encoders side by side - gen_mesh_pipelined - must not
-        share intermediates), grown on demand."""
-        need = native.lib().surs_encoder_workspace_bytes(C.byref(self.net), h, w)
+    def workspace(self, h, w, device, enlarged=False):
+        """The calls' workspace for an h x w input image (enlarged: for an enlarged image of h x w): one tensor per stream the encoder
+        runs on (two encoders side by side - gen_mesh_pipelined - must not share intermediates), grown on demand."""
+        query = native.lib().surs_encoder_workspace_bytes_enlarged if enlarged else native.lib().surs_encoder_workspace_bytes
+        need = query(C.byref(self.net), h, w)
         if need == 0:
             raise ValueError("surs_encoder_workspace_bytes refused a %dx%d image" % (h, w))
         if self.ws is None:
@@ -221,13 +278,13 @@ def _lent_streams(depth):
 
 def super_res_native(W, x, want_image=True):
     """super_res() as one library call (surs_encoder_super_res): same outputs, bit for bit."""
-    if x.h % 4 or x.w % 4:
-        raise ValueError("input image height/width must be multiples of 4 (three stride-2 stages), got %dx%d" % (x.h, x.w))
+    check_image_size(x.h, x.w, W.scale)
     nn, dev = _native_net(W), x.buf.device
     ws = nn.workspace(x.h, x.w, dev)
-    new2 = Img(x.h // 2, x.w // 2, 256, device=dev)
-    new_fin = Img(2 * x.h, 2 * x.w, 64, device=dev)
-    img_sr = Img(2 * x.h, 2 * x.w, 3, device=dev) if want_image else None
+    H2, W2 = W.scale * x.h, W.scale * x.w
+    new2 = Img(H2 // 4, W2 // 4, 256, device=dev)
+    new_fin = Img(H2, W2, 64, device=dev)
+    img_sr = Img(H2, W2, 3, device=dev) if want_image else None
     native.check(native.lib().surs_encoder_super_res(C.byref(nn.net), x.ptr(), x.h, x.w, x.ld, 1 if want_image else 0,
                                                      img_sr.ptr() if want_image else None, new2.ptr(), new_fin.ptr(), native._ptr(ws),
                                                      ws.numel(), native._stream()))
@@ -237,10 +294,9 @@ def super_res_native(W, x, want_image=True):
 def filter_lr_native(W, feature_lr, keep_all=False):
     """filter_lr() as one library call (surs_encoder_filter_lr)."""
     opt = W.opt
-    if feature_lr.h % (1 << opt.hg_depth) or feature_lr.w % (1 << opt.hg_depth):
-        raise ValueError("feature_lr size must be a multiple of 2^hg_depth")
+    check_feature_lr_size(feature_lr.h, feature_lr.w, opt.hg_depth, W.scale)
     nn, dev = _native_net(W), feature_lr.buf.device
-    ws = nn.workspace(2 * feature_lr.h, 2 * feature_lr.w, dev)
+    ws = nn.workspace(4 * feature_lr.h, 4 * feature_lr.w, dev, enlarged=True)
     S = opt.num_stack_lr
     outs = [Img(feature_lr.h, feature_lr.w, nn.last_ch, device=dev) if (keep_all or s == S - 1) else None for s in range(S)]
     ptrs = (C.c_void_p * S)(*[o.ptr() if o is not None else None for o in outs])
@@ -255,19 +311,19 @@ RELU = dict(act=1, slope=0.0)
 
 
 def super_res(W, x, want_image=True):
-    """x: Img [H,W,3].  Returns (img_SR [2H,2W,3], new2 = feature_lr [H/2,W/2,256], new_fin = feature_hr [2H,2W,64]).
+    """x: Img [H,W,3].  Returns (img_SR [2H,2W,3], new2 = feature_lr [H/2,W/2,256], new_fin = feature_hr [2H,2W,64]) - with --scale s:
+    [sH,sW,3], [sH/4,sW/4,256], [sH,sW,64].
     want_image=False: img_SR (two convolutions at 2H x 2W that nothing on the reconstruction path reads: lib/train_util.py:57 drops
     it) is not computed and None is returned in its place - for callers that do not hand it out."""
     opt, P, cv = W.opt, "super_resolution.", native.conv2d
-    if x.h % 4 or x.w % 4:
-        raise ValueError("input image height/width must be multiples of 4 (three stride-2 stages), got %dx%d" % (x.h, x.w))
+    check_image_size(x.h, x.w, W.scale)
     dev = x.buf.device
-    H2, W2 = 2 * x.h, 2 * x.w
+    H2, W2 = W.scale * x.h, W.scale * x.w
     fin = Img(H2, W2, 64, device=dev)             # cat(h, up3)
-    new3 = Img(x.h, x.w, 128, device=dev)          # cat(d1_f, up2)
-    new2 = Img(x.h // 2, x.w // 2, 256, device=dev)  # cat(d2_f, up1)   -> feature_lr
-    new1 = Img(x.h // 4, x.w // 4, 512, device=dev)  # cat(d3_f, bo)
-    up = native.bicubic_up2(x, False)
+    new3 = Img(H2 // 2, W2 // 2, 128, device=dev)    # cat(d1_f, up2)
+    new2 = Img(H2 // 4, W2 // 4, 256, device=dev)    # cat(d2_f, up1)   -> feature_lr
+    new1 = Img(H2 // 8, W2 // 8, 512, device=dev)    # cat(d3_f, bo)
+    up = native.bicubic_up2(x, False) if W.scale == 2 else native.bicubic_up(x, W.scale)
     h = cv(up, W.conv[P + "head.0"], out=fin.slice(0, 32), **LRELU)
 
     def stage(i, src, dst):
@@ -306,6 +362,9 @@ def super_res_strip(W, x, a, b, want_image=True):
     from the same inputs by the same instruction sequence as in super_res on the whole image: the strips are BIT-IDENTICAL to
     the corresponding columns of the full maps (tests/test_gpu_dist.py).  a, b even; what one rank of a sharded reconstruction
     computes (dist.encode_sharded)."""
+    if W.scale != 2:
+        raise ValueError("the strip and halo arithmetic of the sharded super-resolution net is written for --scale 2, not %d: run the "
+                         "replicated encoder (super_res -> filter_hr -> filter_lr on every rank)" % W.scale)
     wl = x.w // 2
     if a % 2 or b % 2 or not (0 <= a < b <= wl):
         raise ValueError("strip [%d, %d) of %d feature_lr columns: bounds must be even and inside the map" % (a, b, wl))
@@ -342,6 +401,11 @@ def conv_block(W, prefix, x, want_stats=False):
     out = Img(x.h, x.w, c, device=x.buf.device)
     o1, o2, o3 = out.slice(0, c // 2), out.slice(c // 2, c // 4), out.slice(3 * c // 4, c // 4)
     cw = [W.conv[prefix + "conv%d" % i] for i in (1, 2, 3)]
+    if W.norm == "batch":
+        # BatchNorm in eval mode: constants in each convolution's staging, no statistics in or out
+        for t, w, o, k in zip((x, o1, o2), cw, (o1, o2, o3), ("bn1", "bn2", "bn3")):
+            native.conv2d(t, w, out=o, in_scale=W.bn[prefix + k][0], in_shift=W.bn[prefix + k][1])
+        return native.add3(out, x, out=out)
     fused = native.fused_groupnorm() and c % 128 == 0 and all(native.conv_gn_eligible(t, w) for t, w in zip((x, o1, o2), cw))
     if fused and x.stats is not None:
         native.conv2d_gn(x, cw[0], o1, gn=W.gn[prefix + "bn1"], want_stats=True)
@@ -387,7 +451,10 @@ def hourglass(W, prefix, depth, x):
     fork = settings.get("SURS_ENC_STREAMS") != "0" and (
         cur0.cuda_stream == torch.cuda.default_stream(cur0.device).cuda_stream or torch.cuda.is_current_stream_capturing())
 
-    st = native.fused_groupnorm()   # every map a ConvBlock reads is written with its GroupNorm statistics (conv_block)
+    st = native.fused_groupnorm() and W.norm != "batch"   # every map a ConvBlock reads is written with its GroupNorm statistics (conv_block)
+    # (a BatchNorm hourglass: the 2 x 2-block bicubic kernel without its statistics)
+    up2 = (lambda low3, up1: native.bicubic_up2_block(low3, True, addend=up1)) if W.norm == "batch" else (
+        lambda low3, up1: native.bicubic_up2(low3, True, addend=up1, want_stats=st))
 
     capturing = torch.cuda.is_current_stream_capturing()
 
@@ -405,7 +472,7 @@ def hourglass(W, prefix, depth, x):
             low2 = fwd(level - 1, low1) if level > 1 else conv_block(W, prefix + "b2_plus_%d." % level, low1, want_stats=True)
             low3 = conv_block(W, prefix + "b3_%d." % level, low2)
             cur.wait_stream(side)
-            return native.bicubic_up2(low3, True, addend=up1, want_stats=st)
+            return up2(low3, up1)
 
         def low_branch():
             low1 = conv_block(W, prefix + "b2_%d." % level, native.avgpool2(inp, want_stats=st), want_stats=True)
@@ -421,21 +488,29 @@ def hourglass(W, prefix, depth, x):
         else:
             up1 = conv_block(W, prefix + "b1_%d." % level, inp)
             low3 = low_branch()
-        return native.bicubic_up2(low3, True, addend=up1, want_stats=st)   # up1 + up2
+        return up2(low3, up1)   # up1 + up2
     return fwd(depth, x)
 
 
 def filter_lr(W, feature_lr, keep_all=False):
     """Returns the list of stack outputs (only the last one unless keep_all, as SuRSNet.filter_lr does in eval)."""
     opt, P = W.opt, "image_filter_lr."
-    if feature_lr.h % (1 << opt.hg_depth) or feature_lr.w % (1 << opt.hg_depth):
-        raise ValueError("feature_lr size must be a multiple of 2^hg_depth")
+    check_feature_lr_size(feature_lr.h, feature_lr.w, opt.hg_depth, W.scale)
     previous = conv_block(W, P + "conv2.", feature_lr, want_stats=True)
     outs = []
     for i in range(opt.num_stack_lr):
         hg = hourglass(W, P + "m%d." % i, opt.hg_depth, previous)
         ll = conv_block(W, P + "top_m_%d." % i, hg)
         last = i == opt.num_stack_lr - 1
+        if W.norm == "batch":
+            # the same three pointwise launches with bn_end's constants
+            sc, sh = W.bn[P + "bn_end%d" % i]
+            t = native.conv2d(ll, W.conv[P + "conv_last%d" % i])
+            if last or keep_all:
+                outs.append(native.conv2d(t, W.conv[P + "l%d" % i], in_scale=sc, in_shift=sh))
+            if not last:
+                previous = native.conv2d(t, W.conv[P + "next%d" % i], in_scale=sc, in_shift=sh, residual=previous)
+            continue
         if native.fused_groupnorm() and all(native.conv_gn_eligible(ll, W.conv[P + k % i]) for k in ("conv_last%d", "l%d")):
             # the tail of a stack in two launches (three where the stack's output is wanted): conv_last leaves bn_end's statistics,
             # the pointwise convolutions behind it fold them; the next stack's input from the merged convolution, its sum with

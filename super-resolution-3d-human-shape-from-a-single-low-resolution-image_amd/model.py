@@ -6,8 +6,13 @@ SURVEY.md section 8b): name, num_views, to(), eval(), train(), state_dict(), loa
 super_res(), filter_hr(), filter_lr(), query_mr(), query_sr(), get_preds().
 
 It is NOT a torch.nn.Module: parameters are a flat ordered dict keyed exactly like the reference's state dict
-(all 553 keys, strict), and every forward method sequences hand-written HIP kernels through the C ABI.  There is
+(all 553 keys, strict; 1036 with --norm batch), and every forward method sequences hand-written HIP kernels through the C ABI.  There is
 no training path (backward is out of scope) and no CPU path: methods raise without a GPU / built library.
+
+Encoder options: --norm group | batch and --scale 1..4 (anything else: ValueError at construction).  --norm batch is nn.BatchNorm2d in
+EVAL mode - y = (x - running_mean) / sqrt(running_var + 1e-5) * weight + bias, always from the running statistics: train() here keeps
+every stack's output as the reference does but never switches to batch statistics; num_batches_tracked is loaded, kept and returned by
+state_dict(), and otherwise ignored.  --scale s: img_SR [V,3,sH,sW], feature_lr [V,256,sH/4,sW/4], feature_hr [V,64,sH,sW].
 """
 from collections import OrderedDict
 
@@ -49,7 +54,8 @@ class SuRSNet:
         self.training = True
         self.device = torch.device("cpu")
         self.precision = getattr(opt, "precision", "fp32")
-        self._spec = weights.state_dict_spec(opt)
+        self._spec = weights.state_dict_spec(opt)            # (--norm other than group | batch: ValueError)
+        encoder.check_scale(getattr(opt, "scale", 2))        # (--scale outside 1..4: ValueError)
         # reference init: normal(0, 0.02) conv weights, zero bias, GroupNorm 1/0 (lib/net_util.py:99-132); here the
         # constructor leaves deterministic synthetic weights in place until load_state_dict() replaces them
         self._sd = OrderedDict((k, torch.from_numpy(v)) for k, v in weights.synthetic_state_dict(opt, seed=0).items())
@@ -101,6 +107,7 @@ class SuRSNet:
 
     def load_state_dict(self, sd, strict=True):
         want = {k: tuple(s) for k, s, _ in self._spec}
+        int_keys = {k for k, _, kind in self._spec if kind.endswith("bn_nbt") or kind.endswith("num_batches_tracked")}
         missing = [k for k in want if k not in sd]
         unexpected = [k for k in sd if k not in want]
         if strict and (missing or unexpected):
@@ -110,7 +117,8 @@ class SuRSNet:
         for k, shape in want.items():
             if k in sd:
                 v = sd[k]
-                v = v.detach().to("cpu", torch.float32) if torch.is_tensor(v) else torch.from_numpy(np.asarray(v, np.float32))
+                dt, npdt = (torch.int64, np.int64) if k in int_keys else (torch.float32, np.float32)   # (num_batches_tracked)
+                v = v.detach().to("cpu", dt) if torch.is_tensor(v) else torch.from_numpy(np.asarray(v, npdt))
                 if tuple(v.shape) != shape:
                     raise RuntimeError("size mismatch for %s: %s vs %s" % (k, tuple(v.shape), shape))
                 new[k] = v.contiguous()
@@ -159,7 +167,8 @@ class SuRSNet:
 
     # ------------------------------------------------------------------ encoder
     def super_res(self, images):
-        """images [V,3,H,W] -> (img_SR [V,3,2H,2W], feature_lr [V,256,H/2,W/2], feature_hr [V,64,2H,2W])."""
+        """images [V,3,H,W] -> (img_SR [V,3,2H,2W], feature_lr [V,256,H/2,W/2], feature_hr [V,64,2H,2W]); with --scale s:
+        [V,3,sH,sW], [V,256,sH/4,sW/4], [V,64,sH,sW]."""
         W = self._encoder_weights()
         self._last_images = images   # (kept for reencode_wide: the retry after an f16 overflow)
         self._sharded_encode = None  # (features about to be made by THIS device's encoder: dist.encode_sharded's record is stale)

@@ -287,6 +287,31 @@ def bicubic_up2(x, align_corners, addend=None, out=None, want_stats=False):
     return out
 
 
+def bicubic_up(x, scale, align_corners=False, addend=None, out=None):
+    """Bicubic enlargement by an integer factor in 1..4 with PyTorch's coordinate arithmetic (surs_bicubic_up); 2: bicubic_up2's bits."""
+    out = out or Img(scale * x.h, scale * x.w, x.c, device=x.buf.device)
+    out.stats = None
+    check(lib().surs_bicubic_up(x.ptr(), x.h, x.w, x.c, x.ld, int(scale), int(bool(align_corners)),
+                                addend.ptr() if addend is not None else None, addend.ld if addend is not None else 0,
+                                out.ptr(), out.ld, _stream()))
+    return out
+
+
+def bicubic_up2_block(x, align_corners, addend=None, out=None):
+    """bicubic_up2 as 2 x 2 output blocks per work item - the kernel form of bicubic_up2(want_stats=True) without its statistics."""
+    out = out or Img(2 * x.h, 2 * x.w, x.c, device=x.buf.device)
+    out.stats = None
+    check(lib().surs_bicubic_up2_block(x.ptr(), x.h, x.w, x.c, x.ld, int(bool(align_corners)),
+                                       addend.ptr() if addend is not None else None, addend.ld if addend is not None else 0,
+                                       out.ptr(), out.ld, _stream()))
+    return out
+
+
+def stats_calls():
+    """Calls so far into the library's GroupNorm-statistics entry points (surs_stats_calls): a BatchNorm encoder makes none."""
+    return int(lib().surs_stats_calls())
+
+
 def pixel_shuffle2(x, slope, out=None):
     out = out or Img(2 * x.h, 2 * x.w, x.c // 4, device=x.buf.device)
     check(lib().surs_pixel_shuffle2(x.ptr(), x.h, x.w, x.c, x.ld, slope, out.ptr(), out.ld, _stream()))

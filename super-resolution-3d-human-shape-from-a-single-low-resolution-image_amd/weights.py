@@ -24,7 +24,28 @@ import numpy as np
 from . import prng
 
 
-def _convblock(prefix, cin, cout):
+NORMS = ("group", "batch")   # --norm: what the reference's HGFilter can be built with (lib/model/HGFilters.py:36-45)
+BN_EPS = 1e-5
+_BN_STATS = (("running_mean", "bn_mean"), ("running_var", "bn_var"), ("num_batches_tracked", "bn_nbt"))
+
+
+def check_norm(norm):
+    if norm not in NORMS:
+        raise ValueError("--norm %s: the supported values are 'group' and 'batch'" % (norm,))
+    return norm
+
+
+def _norm(prefix, c, norm, alias=None):
+    """One norm site: nn.GroupNorm(32, c) -> weight, bias; nn.BatchNorm2d(c) -> + running_mean, running_var, num_batches_tracked
+    (an int64 scalar).  alias: the module that shows up under `prefix` a second time."""
+    kind = (lambda name, k: "alias:" + alias + "." + name) if alias else (lambda name, k: k)
+    out = [(prefix + ".weight", (c,), kind("weight", "gn_w")), (prefix + ".bias", (c,), kind("bias", "gn_b"))]
+    if norm == "batch":
+        out += [(prefix + "." + name, () if k == "bn_nbt" else (c,), kind(name, k)) for name, k in _BN_STATS]
+    return out
+
+
+def _convblock(prefix, cin, cout, norm="group"):
     c2, c4 = cout // 2, cout // 4
     out = [
         (prefix + "conv1.weight", (c2, cin, 3, 3), "conv"),
@@ -32,26 +53,25 @@ def _convblock(prefix, cin, cout):
         (prefix + "conv3.weight", (c4, c4, 3, 3), "conv"),
     ]
     for name, c in (("bn1", cin), ("bn2", c2), ("bn3", c4), ("bn4", cin)):
-        out += [(prefix + name + ".weight", (c,), "gn_w"), (prefix + name + ".bias", (c,), "gn_b")]
+        out += _norm(prefix + name, c, norm)
     if cin != cout:
         # nn.Sequential(self.bn4, ReLU, Conv2d 1x1 no bias): bn4 shows up twice in the state dict
-        out += [(prefix + "downsample.0.weight", (cin,), "alias:" + prefix + "bn4.weight"),
-                (prefix + "downsample.0.bias", (cin,), "alias:" + prefix + "bn4.bias"),
-                (prefix + "downsample.2.weight", (cout, cin, 1, 1), "conv")]
+        out += _norm(prefix + "downsample.0", cin, norm, alias=prefix + "bn4")
+        out += [(prefix + "downsample.2.weight", (cout, cin, 1, 1), "conv")]
     return out
 
 
-def _hourglass(prefix, depth, feat):
+def _hourglass(prefix, depth, feat, norm="group"):
     out = []
 
     def gen(level):
-        out.extend(_convblock(prefix + "b1_%d." % level, feat, feat))
-        out.extend(_convblock(prefix + "b2_%d." % level, feat, feat))
+        out.extend(_convblock(prefix + "b1_%d." % level, feat, feat, norm))
+        out.extend(_convblock(prefix + "b2_%d." % level, feat, feat, norm))
         if level > 1:
             gen(level - 1)
         else:
-            out.extend(_convblock(prefix + "b2_plus_%d." % level, feat, feat))
-        out.extend(_convblock(prefix + "b3_%d." % level, feat, feat))
+            out.extend(_convblock(prefix + "b2_plus_%d." % level, feat, feat, norm))
+        out.extend(_convblock(prefix + "b3_%d." % level, feat, feat, norm))
 
     gen(depth)
     return out
@@ -64,26 +84,22 @@ def _conv(prefix, cout, cin, k, bias=True):
     return out
 
 
-def _gn(prefix, c):
-    return [(prefix + ".weight", (c,), "gn_w"), (prefix + ".bias", (c,), "gn_b")]
-
-
-def _hgfilter(prefix, n_stack, depth, in_ch, last_ch, down_type):
-    out = _conv(prefix + "conv1", 64, in_ch, 7) + _gn(prefix + "bn1", 64)
+def _hgfilter(prefix, n_stack, depth, in_ch, last_ch, down_type, norm="group"):
+    out = _conv(prefix + "conv1", 64, in_ch, 7) + _norm(prefix + "bn1", 64, norm)
     if down_type == "low_res":
-        out += _convblock(prefix + "conv2.", 256, 256)
+        out += _convblock(prefix + "conv2.", 256, 256, norm)
     elif down_type == "high_res":
-        out += _convblock(prefix + "conv2.", 64, 128)
+        out += _convblock(prefix + "conv2.", 64, 128, norm)
     else:
         raise ValueError(down_type)
-    out += _convblock(prefix + "conv3.", 128, 128)
-    out += _convblock(prefix + "conv4.", 128, 256)
+    out += _convblock(prefix + "conv3.", 128, 128, norm)
+    out += _convblock(prefix + "conv4.", 128, 256, norm)
     out += _conv(prefix + "conv5", 64, 64, 1)
     for s in range(n_stack):
-        out += _hourglass(prefix + "m%d." % s, depth, 256)
-        out += _convblock(prefix + "top_m_%d." % s, 256, 256)
+        out += _hourglass(prefix + "m%d." % s, depth, 256, norm)
+        out += _convblock(prefix + "top_m_%d." % s, 256, 256, norm)
         out += _conv(prefix + "conv_last%d" % s, 256, 256, 1)
-        out += _gn(prefix + "bn_end%d" % s, 256)
+        out += _norm(prefix + "bn_end%d" % s, 256, norm)
         out += _conv(prefix + "l%d" % s, last_ch, 256, 1)
         if s < n_stack - 1:
             out += _conv(prefix + "bl%d" % s, 256, 256, 1)
@@ -130,10 +146,13 @@ def _mlp(prefix, dims, res_layers, no_residual):
 
 
 def state_dict_spec(opt):
-    """Ordered [(key, shape, kind)] identical to reference SuRSNet(opt).state_dict()."""
+    """Ordered [(key, shape, kind)] identical to reference SuRSNet(opt).state_dict(): 553 keys for --norm group, 1036 for --norm batch
+    (running_mean, running_var and num_batches_tracked of every norm site of the two hourglass filters; the super-resolution net has no
+    norm layers)."""
+    norm = check_norm(getattr(opt, "norm", "group"))
     spec = []
-    spec += _hgfilter("image_filter_lr.", opt.num_stack_lr, opt.hg_depth, 256, opt.hg_dim, "low_res")
-    spec += _hgfilter("image_filter_hr.", opt.num_stack_hr, opt.hg_depth, 64, opt.hg_dim, "high_res")
+    spec += _hgfilter("image_filter_lr.", opt.num_stack_lr, opt.hg_depth, 256, opt.hg_dim, "low_res", norm)
+    spec += _hgfilter("image_filter_hr.", opt.num_stack_hr, opt.hg_depth, 64, opt.hg_dim, "high_res", norm)
     spec += _sr("super_resolution.", list(opt.n_block))
     spec += _mlp("mlp_lr.", list(opt.mlp_dim_lr), list(opt.mlp_res_layers_lr), opt.no_residual)
     spec += _mlp("mlp_hr.", list(opt.mlp_dim_hr), list(opt.mlp_res_layers_hr), opt.no_residual)
@@ -149,7 +168,8 @@ def synthetic_state_dict(opt, seed=0, enc_gain=0.6, mlp_gain=1.0):
     Conv / MLP weights are zero-mean uniform with std = gain * sqrt(2 / fan_in) (gain 0.6 for the
     encoder convolutions, whose residual/concat structure otherwise doubles the scale per stage) so that every
     layer's output is O(1) (parity tests then see every layer at full sensitivity and the
-    occupancy field straddles the 0.5 level)."""
+    occupancy field straddles the 0.5 level).  --norm batch: running means in [-0.2, 0.2], running variances in [0.5, 1.5] (seeded like
+    everything else; the parity fixtures carry statistics calibrated by the reference instead), num_batches_tracked 1."""
     sd = OrderedDict()
     for key, shape, kind in state_dict_spec(opt):
         if kind.startswith("alias:"):
@@ -167,6 +187,13 @@ def synthetic_state_dict(opt, seed=0, enc_gain=0.6, mlp_gain=1.0):
             v = prng.uniform(key, seed, shape, -0.1, 0.1)
         elif kind == "mlp_bias":
             v = prng.uniform(key, seed, shape, -0.1, 0.1)
+        elif kind == "bn_mean":
+            v = prng.uniform(key, seed, shape, -0.2, 0.2)
+        elif kind == "bn_var":
+            v = prng.uniform(key, seed, shape, 0.5, 1.5)
+        elif kind == "bn_nbt":
+            sd[key] = np.array(1, dtype=np.int64)
+            continue
         elif kind == "meanshift_w":
             v = np.eye(3, dtype=np.float32).reshape(3, 3, 1, 1)
         elif kind in ("meanshift_b-", "meanshift_b+"):
@@ -266,3 +293,12 @@ def body_features(hl, hh, seed=4, waves=5):
     X, Y = 2.0 * u - 1.0, 2.0 * v - 1.0                                   # image coordinates; world x = X/2, y = -Y/2
     fl[0] = 1.0 - (X / (2.0 * BODY_AX)) ** 2 - (Y / (2.0 * BODY_AY)) ** 2
     return fl.astype(np.float32), fh.astype(np.float32)
+
+
+def fold_batchnorm(weight, bias, running_mean, running_var, eps=BN_EPS):
+    """BatchNorm2d in eval mode as per-channel coefficients: y = x * scale + shift with scale = weight / sqrt(var + eps),
+    shift = bias - mean * scale, formed in float64 and stored as float32."""
+    w, b = np.asarray(weight, np.float64), np.asarray(bias, np.float64)
+    m, v = np.asarray(running_mean, np.float64), np.asarray(running_var, np.float64)
+    scale = w / np.sqrt(v + eps)
+    return scale.astype(np.float32), (b - m * scale).astype(np.float32)

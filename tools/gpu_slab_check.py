@@ -4,7 +4,7 @@ meshes with the single-process reconstruction: vertices (float64 world coordinat
 every precision twice: the first reconstruction of a workspace extracts each slab in one piece, the second one pipelines
 the extraction into the sweep.
 
-    python tools/gpu_slab_check.py WORLD [R] [H]
+    python tools/gpu_slab_check.py WORLD [R] [H] [encoder options, e.g. --norm batch]
 
 With H (an image size) the encoder runs too, twice: replicated on every rank, and sharded (dist.encode_sharded: the
 super-resolution net on the rank's image strip, feature_lr all-gathered, filter_hr on the strip) - feature maps bit-identical
@@ -24,17 +24,21 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
-def encoder_leg(rank, world, R, H, dev):
+def encoder_leg(rank, world, R, H, dev, extra=()):
     import common
     from surs_amd import dist as sdist, mesh_util, model, options, weights
     calib = torch.from_numpy(common.CALIB[None].copy())
     b_min, b_max = np.array([-0.5] * 3), np.array([0.5] * 3)
-    opt = options.BaseOptions().parse(common.FLAGS + ["--precision", "fp32"])
+    opt = options.BaseOptions().parse(common.FLAGS + ["--precision", "fp32"] + list(extra))
     img = torch.from_numpy(weights.synthetic_image(H, seed=1)).to(dev)
+    sd = weights.synthetic_state_dict(opt, seed=0) if extra else common.state_dict()
+    if "batch" in extra:   # running statistics calibrated by the reference (the seeded ones leave the field without a 0.5 crossing)
+        gold = np.load(os.path.join(ROOT, "tests", "golden", "encoder_bn_h64_stats.npz"))
+        sd.update({k[5:]: gold[k] for k in gold.files if k.startswith("stat:")})
 
     def make():
         net = model.SuRSNet(opt).to(device=dev)
-        net.load_state_dict({k: torch.from_numpy(v) for k, v in common.state_dict().items()})
+        net.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
         net.eval()
         return net
     rep, shd = make(), make()
@@ -64,7 +68,7 @@ def encoder_leg(rank, world, R, H, dev):
                                                                             len(b[0]), len(b[4])), flush=True)
 
 
-def worker(rank, world, port, R, H=0):
+def worker(rank, world, port, R, H=0, extra=()):
     import common
     from surs_amd import dist as sdist, mesh_util, model, options
     os.environ["MASTER_ADDR"] = "127.0.0.1"
@@ -73,7 +77,7 @@ def worker(rank, world, port, R, H=0):
     torch.cuda.set_device(0)
     dev = torch.device("cuda:0")
     if H:
-        encoder_leg(rank, world, R, H, dev)
+        encoder_leg(rank, world, R, H, dev, extra)
         dist.destroy_process_group()
         return
     fl, fh = common.synth_features()
@@ -134,7 +138,7 @@ def main():
     port = s.getsockname()[1]
     s.close()
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    mp.spawn(worker, args=(world, port, R, H), nprocs=world, join=True)
+    mp.spawn(worker, args=(world, port, R, H, tuple(sys.argv[4:])), nprocs=world, join=True)
 
 
 if __name__ == "__main__":
