@@ -264,7 +264,8 @@ size_t surs_encoder_workspace_bytes_enlarged(const SursEncoderNet *net, int eh, 
  * With net->sr_scale = s: feature_lr [sh/4][sw/4][256], feature_hr and img_sr [sh][sw]; s * h and s * w must be multiples of 8. */
 int surs_encoder_super_res(const SursEncoderNet *net, const float *x, int h, int w, int x_ld, int want_image, float *img_sr,
                            float *feature_lr, float *feature_hr, void *workspace, size_t workspace_bytes, void *stream);
-/* feature_lr [h][w][256] (pitch ld) -> outs[s] [h][w][last_ch] for every stack s with outs[s] != NULL (HOST array of num_stack device
+/* feature_lr [h][w][256] (pitch ld) -> outs[s] [h][w][last_ch] (last_ch = l[s].cout = --hg_dim: a multiple of 16 from 16 to 512,
+ * else SURS_E_INVALID; pitch last_ch, never rounded up) for every stack s with outs[s] != NULL (HOST array of num_stack device
  * pointers; the last one is required - eval keeps only it, training keeps all) */
 int surs_encoder_filter_lr(const SursEncoderNet *net, const float *feature_lr, int h, int w, int ld, float *const *outs,
                            void *workspace, size_t workspace_bytes, const SursEncoderStreams *streams, void *stream);
@@ -338,7 +339,11 @@ int surs_query_points_hr(const float *points, int n, const float *calib, float z
 /* One SurfaceClassifier as the reference builds it from --mlp_dim_*, --mlp_res_layers_* and --no_residual
  * (lib/model/SuRSNet.py:67-78, lib/model/SurfaceClassifier.py:7-43): n_layers Conv1d layers of widths dims[0..n_layers];
  * bit l of res_mask = layer l sees cat(y, feature) (zero under no_residual, SurfaceClassifier.py:57-66).  Supported:
- * 1 <= n_layers <= 8, dims[0] = 321 (lr) / 322 (hr), dims[n_layers] = 1, hidden widths 1..2048, res_mask < 2^n_layers. */
+ * 1 <= n_layers <= 8, dims[0] = D + 65 (lr) / D + 66 (hr), dims[n_layers] = 1, hidden widths 1..2048, res_mask < 2^n_layers.
+ * D = lr.dims[0] - 65 is the encoder's --hg_dim (lib/model/HGFilters.py:166-174: a point's features are [D lr | 64 hr | z], + p_lr for
+ * hr): a multiple of 16 from 16 to 512, 256 (321 / 322) in the released model.  Every entry below that takes feat_lr with such a pair
+ * reads it as [hl][wl][D], pitch D.  For D > 256 the LDS of a 16-point tile holds narrower hidden layers: at most
+ * ((160 KiB / 16 - 16) / 4 - 4 - (pad32(D + 66) + 4)) rounded down to 32 (D = 512: 1920); the refusal names the limit and D. */
 typedef struct SursMlpShape {
     int n_layers;
     int dims[9];
@@ -359,7 +364,8 @@ int surs_mlp_generic_info(const SursMlpShape *lr, const SursMlpShape *hr, int *t
 
 /* query_mr + query_sr + get_preds (lib/model/SuRSNet.py:131-187) for classifiers of any supported shape, in ONE launch per call:
  * projection, in-image mask, z_feat, bilinear gather, mlp_lr, masked sigmoid, mlp_hr, masked sigmoid per tile of points, the
- * activations in LDS.  Arguments as surs_query_points, plus the shapes and the blob of surs_mlp_pack_generic.  p_lr non-NULL: the hr
+ * activations in LDS.  Arguments as surs_query_points - but feat_lr is [hl][wl][D], D = lr->dims[0] - 65 (SursMlpShape; the octree's
+ * indexed lattice points come through this entry too) -, plus the shapes and the blob of surs_mlp_pack_generic.  p_lr non-NULL: the hr
  * classifier alone, fed with p_lr [n] (query_sr on other points); pred_lr / logit_lr are then ignored.  Operand split as
  * surs_query_points: surs_set_operand_split_local (1 = one f16 product, 2 = two f16 parts, 3 = three bf16 parts) or the process
  * setting.  logit_* nullable (pre-sigmoid, pre-mask). */
@@ -370,7 +376,7 @@ int surs_query_points_generic(const float *points, int n, const float *calib, fl
 
 /* The dense sweep (create_grid + eval_grid + eval_func, lib/sdf.py:4-52, lib/mesh_util.py:16-34) of grid slab [i0, i1) with the
  * fused evaluator: voxel coordinates made in the kernel in float64 from `mat` (HOST, rows 0..2 of the grid matrix) and cast to
- * float32, as create_grid does.  vol_hr / vol_lr [(i1-i0)][ry][rz]. */
+ * float32, as create_grid does.  feat_lr [hl][wl][D], D = lr->dims[0] - 65.  vol_hr / vol_lr [(i1-i0)][ry][rz]. */
 int surs_query_grid_generic(int i0, int i1, int ry, int rz, const double *mat, const float *calib, float zmul, float zdiv,
                             const float *feat_lr, int hl, int wl, const float *feat_hr, int hh, int wh, const SursMlpShape *lr,
                             const SursMlpShape *hr, const void *blob, float *vol_hr, float *vol_lr, void *stream);
@@ -379,8 +385,8 @@ int surs_query_grid_generic(int i0, int i1, int ry, int rz, const double *mat, c
  * launch per call (csrc/surs_mlp_fused_views.inc): lib/model/SurfaceClassifier.py:53-81 with num_views > 1 - layers 0 .. L/2 per
  * view on that view's features, then the view mean ((sum in view order) * (1/V)) of layer L/2's outputs and of the input features,
  * layers L/2 + 1 .. L-1 once per point (L = 1, 2: the mean of the logits) - and SuRSNet.py:131-187 (view v's prediction = in_img_v *
- * sigmoid(logit); channel 321 of view v's hr input = view v's pred_lr).  points [V][3][n] (lib/train_util.py:40-51), calibs DEVICE
- * [V][12] (rows 0..2 of each view's calibration), feat_lr [V][hl][wl][256], feat_hr [V][hh][wh][64]; pred_hr / pred_lr [V][n];
+ * sigmoid(logit); the last channel (D + 65) of view v's hr input = view v's pred_lr).  points [V][3][n] (lib/train_util.py:40-51), calibs DEVICE
+ * [V][12] (rows 0..2 of each view's calibration), feat_lr [V][hl][wl][D] (D = lr->dims[0] - 65), feat_hr [V][hh][wh][64]; pred_hr / pred_lr [V][n];
  * logit_hr / logit_lr [n] nullable (what the sigmoid takes).  p_lr [V][n] non-NULL: the hr classifier alone (query_sr on other
  * points), pred_lr / logit_lr ignored.  Operand split as surs_query_points_generic; V = 1 gives its bits. */
 int surs_query_points_generic_views(const float *points, int n, int num_views, const float *calibs, float zmul, float zdiv,
@@ -390,7 +396,7 @@ int surs_query_points_generic_views(const float *points, int n, int num_views, c
 
 /* The dense sweep of a multi-view model (eval_grid over eval_func, lib/sdf.py:32-52, lib/mesh_util.py:20-28: every grid point seen
  * by every view, view 0's predictions kept) of grid slab [i0, i1) in one launch: voxels as surs_query_grid_generic, the other
- * arguments as surs_query_points_generic_views; vol_hr / vol_lr [(i1-i0)][ry][rz] = view 0's rows. */
+ * arguments as surs_query_points_generic_views (feat_lr [V][hl][wl][D]); vol_hr / vol_lr [(i1-i0)][ry][rz] = view 0's rows. */
 int surs_query_grid_generic_views(int i0, int i1, int ry, int rz, const double *mat, int num_views, const float *calibs, float zmul,
                                   float zdiv, const float *feat_lr, int hl, int wl, const float *feat_hr, int hh, int wh,
                                   const SursMlpShape *lr, const SursMlpShape *hr, const void *blob, float *vol_hr, float *vol_lr,
@@ -398,7 +404,8 @@ int surs_query_grid_generic_views(int i0, int i1, int ry, int rz, const double *
 
 /* HOST: how the multi-view evaluator runs this pair for num_views views: *tile_points per workgroup and *lds_bytes of LDS per
  * workgroup, or SURS_E_INVALID naming the limit (num_views outside [1, 64], an unsupported shape, a hidden layer wider than 1824:
- * the tile keeps the features and their running view sum in LDS).  The multi-view entries need no device workspace. */
+ * the tile keeps the features and their running view sum in LDS - for D = lr->dims[0] - 65 above 256 less, D = 512: 1312, the
+ * message then names the limit and D).  The multi-view entries need no device workspace. */
 int surs_mlp_generic_views_info(const SursMlpShape *lr, const SursMlpShape *hr, int num_views, int *tile_points, int *lds_bytes);
 
 /* surs_query_points for point arrays that come as RUNS of equal (x, y): what the reference's dense sweep loop hands

@@ -567,6 +567,10 @@ extern "C" int surs_encoder_filter_lr(const SursEncoderNet *net, const float *fe
     SURS_REQUIRE(feature_lr && outs && workspace && outs[net->num_stack - 1], "null argument (the last stack's output is always wanted)");
     SURS_REQUIRE(h > 0 && w > 0 && h % (1 << net->hg_depth) == 0 && w % (1 << net->hg_depth) == 0, "feature_lr size must be a multiple of 2^hg_depth");
     SURS_REQUIRE(ld >= 256 && ld % 4 == 0 && aligned16(feature_lr), "feature_lr: 256 channels, 16-byte aligned pixels");
+    for (int s = 0; s < net->num_stack; ++s) {   // --hg_dim: outs[s] is [h][w][l{s}.cout], pitch l{s}.cout
+        const int d = net->l[s].cout;
+        SURS_REQUIRE(d >= 16 && d <= 512 && d % 16 == 0, "hg_dim %d: the supported values are the multiples of 16 from 16 to 512", d);
+    }
     Arena dr[2];
     dr[0].dry = dr[1].dry = true;
     {

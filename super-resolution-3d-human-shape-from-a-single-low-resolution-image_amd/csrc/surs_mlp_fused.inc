@@ -1,10 +1,11 @@
 // Fused point evaluator for SurfaceClassifier pairs of any supported shape (surs_mlp_generic.h), included at the end of
 // surs_query.hip.  ONE launch per call: per tile of P points, projection -> in-image mask -> z_feat -> 4-tap bilinear gather of the
-// 256 lr + 64 hr channels (the __device__ helpers gather_kernel uses) -> mlp_lr -> masked sigmoid (= channel 321 of the hr input)
-// -> mlp_hr -> masked sigmoid.  Replaces lib/model/SuRSNet.py:131-187 and lib/model/SurfaceClassifier.py:53-81 for those shapes.
+// D lr + 64 hr channels (the __device__ helpers gather_kernel uses; D = --hg_dim = dims_lr[0] - 65, 256 in the released model) ->
+// mlp_lr -> masked sigmoid (= the last channel, D + 65, of the hr input) -> mlp_hr -> masked sigmoid.  Replaces lib/model/SuRSNet.py:131-187 and lib/model/SurfaceClassifier.py:53-81 for those shapes.
 //
 // Budget (gfx950: 160 KiB LDS per CU, 512 VGPR+AGPR per SIMD lane):
-//   - The activations of a tile never leave the CU.  LDS holds the tile's input features fp32 [P][352 + 4] and ONE activation
+//   - The activations of a tile never leave the CU.  LDS holds the tile's input features fp32 [P][pad32(D + 66) + 4] (D = 256:
+//     [P][352 + 4], the numbers of this paragraph; gen_max_hidden and fused_pb carry D) and ONE activation
 //     buffer fp32 [P][max_hidden + 4]: a layer's outputs stay in the accumulators until every wave has finished reading its inputs
 //     (barrier), then overwrite them.  So the widest padded hidden layer W, not (input + output), sets the tile:
 //     P (W + 364) * 4 bytes <= 160 KiB  ->  P = 32 for W <= 896 (the 512-wide family: 112 128 B), P = 16 up to W = 2048 (154 368 B;
@@ -16,11 +17,20 @@
 //   - Weights are read straight from L2 / MALL in A-fragment order (one contiguous 1 KiB wave load per tile, k step and part);
 //     every weight is read once per tile of P points, so weight streaming (bytes of the blob's NP-part image / P per point) is
 //     the limiter of this kernel, and P is what the LDS budget caps.
+//   - Feature row stride pad32(D + 66) + 4 floats: 36 (D = 256, 356) or 4 modulo 64 words, depending on D.  Checked against the B
+//     fragment's read (lane (q, c) reads 32 bytes at row c, word 8 q, as two ds_read_b128; MI355X: four groups of 16 lanes per
+//     instruction, bank = word mod 64): each group holds 8 lanes of one q and 8 of the next, rows {0-3, 12-15} against {4-11}, and for
+//     every 16-byte-aligned stride one pair of those rows lands 8 words apart - one extra LDS cycle per group for residue 36 and
+//     for residue 4 alike, as for every pad that is a multiple of 4 (residues 0 and 32: 7 and 3).  No aligned stride is free of it,
+//     both residues cost the same, so the pad stays 4 for every D; the released D's stride is the 356 it was.
+//   - D is a launch argument (FeatDims): the gather runs a wave per point with its lanes along the point's D + 64 channels, so a tap
+//     stays one contiguous read of 4 D bytes and nothing divides by a run-time count.
 // Arithmetic: NP = 1 (one f16 product per MAC: --precision bf16 / fp16), 2 (two f16 parts, three products: fp32-grade, |x| <
 // 65504) or 3 (three bf16 parts, six products: fp32-grade with fp32's range), products in gemm_x3g_kernel's order.  A point's
 // sums run in one fixed order whatever tile or position it lands in (an MFMA output column depends on its own column only).
-// Resource usage (hipcc -Rpass-analysis=kernel-resource-usage; tests/test_mlp_shapes_host.py reads it from the code object): 122-146
-// VGPRs, 0 AGPRs, 0 bytes of scratch over the six <NP, PB> instantiations, LDS dynamic (above).
+// Resource usage (hipcc -Rpass-analysis=kernel-resource-usage; tests/test_mlp_shapes_host.py reads it from the code object): 124-148
+// VGPRs, 0 AGPRs, 0 bytes of scratch over the six <NP, PB> instantiations of each family (mlp_fused_kernel: D = 256, mlp_anyd_kernel:
+// any other D; tests/test_hg_dim_host.py), LDS dynamic (above).
 // Measured (MI355X, 50 000 random points, full-size feature maps, tools/gpu_shapes_time.py): the released shape 5.28 ms fp32-grade /
 // 3.00 ms one product here against 1.00 / 0.56 ms on the layer kernels - P = 16 makes every tile stream the 9.6 MB two-part image
 // (600 KB of L2 / MALL reads per point) from one 8-wave workgroup per CU; the 512-wide s1 (P = 32) 1.43 / 0.78 ms.
@@ -28,7 +38,6 @@
 namespace surs {
 
 constexpr int FU_WAVES = 8;
-constexpr int FU_FS = GEN_C0PAD + 4;   // feature row stride (floats): 356 = 36 mod 64 words, rows of a B read hit distinct banks
 
 struct FusedArgs {
     PointSource src;
@@ -40,9 +49,36 @@ struct FusedArgs {
     const float *p_lr;   // non-null: the hr classifier alone, channel 321 from here
     float *pred_hr, *pred_lr, *logit_hr, *logit_lr;
     int as;              // activation row stride (floats): max_hidden + 4
-    int reserved;
+    int fs;              // feature row stride (floats): gen_feat_stride(D), D = lay.hg_dim
     GenLayout lay;
 };
+
+// The feature geometry of a launch: D lr channels, D + 64 gathered channels (z_feat behind them, then p_lr), the row stride.  FIXED:
+// the released D = 256 as compile-time constants - mlp_fused_kernel / mlp_fused_views_kernel, instruction for instruction what they
+// were when 256 was the only D; otherwise launch arguments - mlp_anyd_kernel / mlp_anyd_views_kernel, the same bodies.  (Run-time
+// values in the one family, and a uniform branch between the two forms inside each instantiation, both measured 1 - 3 % slower on
+// the released D's 512-wide shape: DESIGN.md section 10.)
+constexpr int FU_FS_256 = 356;
+template <bool FIXED> struct FeatDims {
+    int c_lr, c_g, fs;
+    __device__ __forceinline__ explicit FeatDims(const FusedArgs &a)
+        : c_lr(FIXED ? C_LR : a.lay.hg_dim), c_g(FIXED ? C_G : a.lay.hg_dim + GEN_C_HR), fs(FIXED ? FU_FS_256 : a.fs) {}
+};
+
+// One gathered channel c of tile point p: the 4-tap bilinear sample of the lr (c < c_lr) or hr map at the point's projection.
+// (the map sizes by value: selecting between fields of the kernel argument through a reference made hipcc fetch them per item)
+__device__ __forceinline__ float gather_channel(const float *fl, const float *fh, int hl, int wl, int hh, int wh, int c_lr, float X, float Y,
+                                                int c) {
+    const bool hr = c >= c_lr;
+    const float *fm = hr ? fh : fl;
+    const int H = hr ? hh : hl, W = hr ? wh : wl, C = hr ? C_HR : c_lr, ch = hr ? c - c_lr : c;
+    long long pix[4];
+    float w[4], tv[4];
+    bilinear_taps(X, Y, H, W, pix, w);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) tv[q] = fm[pix[q] * C + ch];
+    return tap_sum(tv, w);
+}
 
 template <int NP> struct Mfma16;
 template <> struct Mfma16<1> {
@@ -60,8 +96,8 @@ template <> struct Mfma16<3> {
 // vsum, the caller's running sum over the views (first: the first view, assigned); each wave owns the same output tiles for every
 // view, so the sum stays in registers.
 template <int NP, int PB, bool VIEWS>
-__device__ __forceinline__ void fused_layers(const FusedArgs &a, int m, int l0, int l1, float *feat, float *act, float *slog, int lane,
-                                             int wave, f32x4 (&vsum)[16 / PB][PB], int mv, bool first) {
+__device__ __forceinline__ void fused_layers(const FusedArgs &a, const int fs, int m, int l0, int l1, float *feat, float *act, float *slog,
+                                             int lane, int wave, f32x4 (&vsum)[16 / PB][PB], int mv, bool first) {
     typedef Mfma16<NP> MF;
     typedef typename MF::vec8 vec8;
     constexpr int TPW = 16 / PB;
@@ -80,7 +116,7 @@ __device__ __forceinline__ void fused_layers(const FusedArgs &a, int m, int l0, 
             // B fragment: lane (q, c) holds k = 8 q + j of point c of each 16-point block (layer 0 and the skip segment read the features)
             const bool first = kt < k1t;
             const float *src = first ? (l == 0 ? feat : act) + kt * GEN_KT : feat + (kt - k1t) * GEN_KT;
-            const int ld = (first && l > 0) ? a.as : FU_FS;
+            const int ld = (first && l > 0) ? a.as : fs;
             vec8 b[PB][NP];
 #pragma unroll
             for (int pb = 0; pb < PB; ++pb) {
@@ -150,17 +186,19 @@ __device__ __forceinline__ void fused_layers(const FusedArgs &a, int m, int l0, 
 
 // One classifier on the tile: layers 0 .. L-1.
 template <int NP, int PB>
-__device__ __forceinline__ void fused_classifier(const FusedArgs &a, int m, float *feat, float *act, float *slog, int lane, int wave) {
+__device__ __forceinline__ void fused_classifier(const FusedArgs &a, const int fs, int m, float *feat, float *act, float *slog, int lane,
+                                                 int wave) {
     f32x4 unused[16 / PB][PB];
-    fused_layers<NP, PB, false>(a, m, 0, a.lay.n_layers[m], feat, act, slog, lane, wave, unused, -1, false);
+    fused_layers<NP, PB, false>(a, fs, m, 0, a.lay.n_layers[m], feat, act, slog, lane, wave, unused, -1, false);
 }
 
-template <int NP, int PB>
-__global__ __launch_bounds__(FU_WAVES * 64) void mlp_fused_kernel(FusedArgs a) {
+template <int NP, int PB, bool FIXED>
+__device__ __forceinline__ void mlp_fused_body(const FusedArgs &a, float *fu_smem) {
     constexpr int P = 16 * PB;
-    extern __shared__ __attribute__((aligned(16))) float fu_smem[];
-    float *feat = fu_smem;                 // [P][FU_FS]: 256 lr, 64 hr, z_feat, p_lr, zeros
-    float *act = feat + P * FU_FS;         // [P][as]
+    const FeatDims<FIXED> fd(a);
+    const int c_lr = fd.c_lr, c_g = fd.c_g, fs = fd.fs;
+    float *feat = fu_smem;                 // [P][fs]: D lr, 64 hr, z_feat, p_lr, zeros
+    float *act = feat + P * fs;            // [P][as]
     float *sx = act + P * a.as, *sy = sx + P, *smask = sy + P, *slog = smask + P;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long long t0 = (long long)blockIdx.x * P;
@@ -178,33 +216,31 @@ __global__ __launch_bounds__(FU_WAVES * 64) void mlp_fused_kernel(FusedArgs a) {
         sx[tid] = X;
         sy[tid] = Y;
         smask[tid] = in;
-        float *f = feat + tid * FU_FS;
-        f[C_G] = zf;
-        f[C_G + 1] = pl;
-        for (int c = C_G + 2; c < FU_FS; ++c) f[c] = 0.0f;
+        float *f = feat + tid * fs;
+        f[c_g] = zf;
+        f[c_g + 1] = pl;
+        for (int c = c_g + 2; c < fs; ++c) f[c] = 0.0f;
     }
     __syncthreads();
-    // gather: lanes along the channels of one point (coalesced 1 KiB / 256 B per tap)
-    for (int item = tid; item < P * C_G; item += FU_WAVES * 64) {
-        const int p = item / C_G, c = item - p * C_G;
-        const bool hr = c >= C_LR;
-        const float *fm = hr ? a.feat_hr : a.feat_lr;
-        const int H = hr ? a.hh : a.hl, W = hr ? a.wh : a.wl, C = hr ? C_HR : C_LR, ch = hr ? c - C_LR : c;
-        long long pix[4];
-        float w[4], tv[4];
-        bilinear_taps(sx[p], sy[p], H, W, pix, w);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) tv[q] = fm[pix[q] * C + ch];
-        feat[p * FU_FS + c] = tap_sum(tv, w);
+    // gather: lanes along the channels of one point (a tap is one contiguous read: 1 KiB / 256 B for D = 256)
+    if (FIXED) {
+        for (int item = tid; item < P * c_g; item += FU_WAVES * 64) {
+            const int p = item / c_g, c = item - p * c_g;
+            feat[p * fs + c] = gather_channel(a.feat_lr, a.feat_hr, a.hl, a.wl, a.hh, a.wh, c_lr, sx[p], sy[p], c);
+        }
+    } else {   // a wave per point: no division by the run-time channel count
+        for (int p = wave; p < P; p += FU_WAVES)
+            for (int c = lane; c < c_g; c += 64)
+                feat[p * fs + c] = gather_channel(a.feat_lr, a.feat_hr, a.hl, a.wl, a.hh, a.wh, c_lr, sx[p], sy[p], c);
     }
     __syncthreads();
     if (!a.p_lr) {
-        fused_classifier<NP, PB>(a, 0, feat, act, slog, lane, wave);
+        fused_classifier<NP, PB>(a, fs, 0, feat, act, slog, lane, wave);
         if (tid < P) {
             const long long t = t0 + tid;
             const float lg = slog[tid];
             const float p = smask[tid] * (1.0f / (1.0f + expf(-lg)));
-            feat[tid * FU_FS + C_G + 1] = p;
+            feat[tid * fs + c_g + 1] = p;
             if (t < a.n) {
                 a.pred_lr[t] = p;
                 if (a.logit_lr) a.logit_lr[t] = lg;
@@ -212,7 +248,7 @@ __global__ __launch_bounds__(FU_WAVES * 64) void mlp_fused_kernel(FusedArgs a) {
         }
         __syncthreads();
     }
-    fused_classifier<NP, PB>(a, 1, feat, act, slog, lane, wave);
+    fused_classifier<NP, PB>(a, fs, 1, feat, act, slog, lane, wave);
     if (tid < P) {
         const long long t = t0 + tid;
         const float lg = slog[tid];
@@ -223,9 +259,26 @@ __global__ __launch_bounds__(FU_WAVES * 64) void mlp_fused_kernel(FusedArgs a) {
     }
 }
 
+template <int NP, int PB>
+__global__ __launch_bounds__(FU_WAVES * 64) void mlp_fused_kernel(FusedArgs a) {   // D = 256
+    extern __shared__ __attribute__((aligned(16))) float fu_smem[];
+    mlp_fused_body<NP, PB, true>(a, fu_smem);
+}
+
+template <int NP, int PB>
+__global__ __launch_bounds__(FU_WAVES * 64) void mlp_anyd_kernel(FusedArgs a) {    // any other D
+    extern __shared__ __attribute__((aligned(16))) float fu_smem[];
+    mlp_fused_body<NP, PB, false>(a, fu_smem);
+}
+
 // points per tile: 32 when the widest hidden layer leaves room for them in LDS, else 16
-static int fused_pb(const GenLayout &lay) { return 32 * (lay.max_hidden + 4 + FU_FS) * 4 + 4 * 32 * 4 <= 160 * 1024 ? 2 : 1; }
-static int fused_lds_bytes(const GenLayout &lay, int pb) { return 16 * pb * ((lay.max_hidden + 4 + FU_FS) * 4 + 16); }
+static int fused_pb(const GenLayout &lay) { return 32 * (lay.max_hidden + 4 + gen_feat_stride(lay.hg_dim)) * 4 + 4 * 32 * 4 <= GEN_LDS_BYTES ? 2 : 1; }
+static int fused_lds_bytes(const GenLayout &lay, int pb) { return 16 * pb * ((lay.max_hidden + 4 + gen_feat_stride(lay.hg_dim)) * 4 + 16); }
+
+static void fused_strides(FusedArgs &a) {
+    a.as = a.lay.max_hidden + 4;
+    a.fs = gen_feat_stride(a.lay.hg_dim);
+}
 
 // operand parts of this call: the calling thread's surs_set_operand_split_local (1: one f16 product), else the process setting
 static int fused_parts() {
@@ -236,6 +289,14 @@ static int fused_parts() {
 
 template <int NP, int PB>
 static int launch_fused_t(hipStream_t st, const FusedArgs &a, int lds) {
+    if (a.lay.hg_dim != C_LR) {
+        static DeviceOnce attr_anyd;
+        if (attr_anyd.first())
+            SURS_HIP_CHECK(hipFuncSetAttribute((const void *)mlp_anyd_kernel<NP, PB>, hipFuncAttributeMaxDynamicSharedMemorySize, lds > 65536 ? 160 * 1024 : 65536));
+        hipLaunchKernelGGL((mlp_anyd_kernel<NP, PB>), dim3((unsigned)ceil_div(a.n, 16 * PB)), dim3(FU_WAVES * 64), lds, st, a);
+        SURS_LAUNCH_CHECK();
+        return 0;
+    }
     static DeviceOnce attr;
     if (attr.first())
         SURS_HIP_CHECK(hipFuncSetAttribute((const void *)mlp_fused_kernel<NP, PB>, hipFuncAttributeMaxDynamicSharedMemorySize, lds > 65536 ? 160 * 1024 : 65536));
@@ -247,7 +308,7 @@ static int launch_fused_t(hipStream_t st, const FusedArgs &a, int lds) {
 static int run_fused(hipStream_t st, FusedArgs &a) {
     if (a.n == 0) return 0;
     const int pb = fused_pb(a.lay), lds = fused_lds_bytes(a.lay, pb), parts = fused_parts();
-    a.as = a.lay.max_hidden + 4;
+    fused_strides(a);
     switch (parts * 2 + pb - 1) {
     case 2: return launch_fused_t<1, 1>(st, a, lds);
     case 3: return launch_fused_t<1, 2>(st, a, lds);
@@ -264,7 +325,8 @@ static int fused_prepare(FusedArgs &a, const SursMlpShape *lr, const SursMlpShap
     SURS_REQUIRE(hl > 0 && wl > 0 && hh > 0 && wh > 0, "bad sizes");
     memset(&a, 0, sizeof(a));
     const int rc = gen_layout(*lr, *hr, a.lay);
-    SURS_REQUIRE(rc == 0, "unsupported SurfaceClassifier shape: %s", gen_shape_error(rc));
+    char why[160];
+    SURS_REQUIRE(rc == 0, "unsupported SurfaceClassifier shape: %s", gen_shape_error(rc, *lr, why));
     for (int i = 0; i < 12; ++i) a.src.calib[i] = calib[i];
     a.src.zmul = zmul;
     a.src.zdiv = zdiv;
@@ -285,7 +347,8 @@ extern "C" int surs_mlp_generic_info(const SursMlpShape *lr, const SursMlpShape 
     SURS_REQUIRE(lr && hr, "null shape");
     GenLayout lay;
     const int rc = gen_layout(*lr, *hr, lay);
-    SURS_REQUIRE(rc == 0, "unsupported SurfaceClassifier shape: %s", gen_shape_error(rc));
+    char why[160];
+    SURS_REQUIRE(rc == 0, "unsupported SurfaceClassifier shape: %s", gen_shape_error(rc, *lr, why));
     const int pb = fused_pb(lay);
     if (tile_points) *tile_points = 16 * pb;
     if (lds_bytes) *lds_bytes = fused_lds_bytes(lay, pb);

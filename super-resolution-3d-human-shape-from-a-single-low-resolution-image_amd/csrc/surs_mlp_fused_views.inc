@@ -2,9 +2,9 @@
 // call, V <= 64 views of one subject (points [V][3][n] / one grid seen by every view, calibs [V][12], feature maps [V][...]):
 // SurfaceClassifier.py:53-81 with num_views > 1 and SuRSNet.py:131-187.  Per tile of P points and classifier (lr, then hr), with
 // M = L / 2 its merge layer:
-//   for every view v in order: projection with calib_v (its in-image bit kept in LDS, [P] x 64 bits), gather of the view's 320
-//   channels + z_feat (+ channel 321 = view v's pred_lr for hr) into feat exactly as mlp_fused_kernel does, and into a running
-//   sum fsum [P][FU_FS] in LDS (each value is summed by the thread that gathered it); layers 0 .. M on them (fused_layers<VIEWS>:
+//   for every view v in order: projection with calib_v (its in-image bit kept in LDS, [P] x 64 bits), gather of the view's D + 64
+//   channels + z_feat (+ channel D + 65 = view v's pred_lr for hr) into feat exactly as mlp_fused_kernel does, and into a running
+//   sum fsum [P][fs] in LDS (fs = gen_feat_stride(D), 356 for the released D = 256) (each value is summed by the thread that gathered it); layers 0 .. M on them (fused_layers<VIEWS>:
 //   layer M's outputs go into a running sum in the accumulating waves' registers - each wave owns the same output tiles for every
 //   view -, not to LDS);
 //   then the two means ((sum in view order) * (1 / V), as mean_views_kernel) into feat and act (or slog when M = L - 1: the mean
@@ -13,7 +13,7 @@
 // order as mlp_fused_kernel: with V = 1 both give the same bits (the means are x * 1), and a point's result does not depend on its
 // tile or position.
 // Budget: LDS = P ((W + 4 + 2 * 356) * 4 + 24) bytes for the widest padded hidden layer W: P = 32 for W <= 544, P = 16 up to
-// W = 1824 - the views limit (FV_WIDTH_LIMIT), below the single-view 2048.  Registers: the single-view kernel's + the 64 of the
+// W = 1824 - the views limit (FV_WIDTH_LIMIT), below the single-view 2048 (D = 256's numbers; D > 256: fused_views_max_hidden).  Registers: the single-view kernel's + the 64 of the
 // layer-M sum: 202-236 VGPRs, 0 AGPRs, 0 bytes of scratch over the six <NP, PB> instantiations.
 
 namespace surs {
@@ -69,21 +69,22 @@ __device__ __forceinline__ void store_view_mean(const FusedArgs &a, const GenLay
     }
 }
 
-template <int NP, int PB>
-__global__ __launch_bounds__(FU_WAVES * 64) void mlp_fused_views_kernel(FusedViewsArgs va) {
+template <int NP, int PB, bool FIXED>
+__device__ __forceinline__ void mlp_fused_views_body(const FusedViewsArgs &va, float *fu_smem) {
     constexpr int P = 16 * PB, TPW = 16 / PB, NT = FU_WAVES * 64;
     const FusedArgs &a = va.f;
-    extern __shared__ __attribute__((aligned(16))) float fu_smem[];
-    float *feat = fu_smem;                 // [P][FU_FS]: 256 lr, 64 hr, z_feat, p_lr, zeros
-    float *fsum = feat + P * FU_FS;        // [P][FU_FS]: their running sum over the views
-    float *act = fsum + P * FU_FS;         // [P][as]
+    const FeatDims<FIXED> fd(a);
+    const int c_lr = fd.c_lr, c_g = fd.c_g, fs = fd.fs;
+    float *feat = fu_smem;                 // [P][fs]: D lr, 64 hr, z_feat, p_lr, zeros
+    float *fsum = feat + P * fs;           // [P][fs]: their running sum over the views
+    float *act = fsum + P * fs;            // [P][as]
     float *sx = act + P * a.as, *sy = sx + P, *slog = sy + P, *sprob = slog + P;   // sprob: sigmoid of the lr logit
-    unsigned long long *sbits = (unsigned long long *)(sprob + P);   // in-image bit of view v (8-byte aligned: P (2 FU_FS + as) is even)
+    unsigned long long *sbits = (unsigned long long *)(sprob + P);   // in-image bit of view v (8-byte aligned: P (2 fs + as) is even)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long long t0 = (long long)blockIdx.x * P;
     const int V = va.V;
     if (tid < P)
-        for (int c = C_G + 2; c < FU_FS; ++c) feat[tid * FU_FS + c] = 0.0f;
+        for (int c = c_g + 2; c < fs; ++c) feat[tid * fs + c] = 0.0f;
     for (int m = a.p_lr ? 1 : 0; m < 2; ++m) {
         const int L = a.lay.n_layers[m], M = L / 2;
         f32x4 vsum[TPW][PB];
@@ -101,40 +102,42 @@ __global__ __launch_bounds__(FU_WAVES * 64) void mlp_fused_views_kernel(FusedVie
                 sx[tid] = X;
                 sy[tid] = Y;
                 sbits[tid] = (v == 0 ? 0ull : sbits[tid]) | ((unsigned long long)(in != 0.0f) << v);
-                float *f = feat + tid * FU_FS;
-                float *fs = fsum + tid * FU_FS;
-                f[C_G] = zf;
-                f[C_G + 1] = pl;
-                fs[C_G] = v == 0 ? zf : fs[C_G] + zf;
-                fs[C_G + 1] = v == 0 ? pl : fs[C_G + 1] + pl;
+                float *f = feat + tid * fs;
+                float *fsm = fsum + tid * fs;
+                f[c_g] = zf;
+                f[c_g + 1] = pl;
+                fsm[c_g] = v == 0 ? zf : fsm[c_g] + zf;
+                fsm[c_g + 1] = v == 0 ? pl : fsm[c_g + 1] + pl;
             }
             __syncthreads();
-            const float *fl = a.feat_lr + (size_t)v * a.hl * a.wl * C_LR, *fh = a.feat_hr + (size_t)v * a.hh * a.wh * C_HR;
-            for (int item = tid; item < P * C_G; item += NT) {
-                const int p = item / C_G, c = item - p * C_G;
-                const bool hr = c >= C_LR;
-                const float *fm = hr ? fh : fl;
-                const int H = hr ? a.hh : a.hl, W = hr ? a.wh : a.wl, C = hr ? C_HR : C_LR, ch = hr ? c - C_LR : c;
-                long long pix[4];
-                float w[4], tv[4];
-                bilinear_taps(sx[p], sy[p], H, W, pix, w);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) tv[q] = fm[pix[q] * C + ch];
-                const float x = tap_sum(tv, w);
-                feat[p * FU_FS + c] = x;
-                fsum[p * FU_FS + c] = v == 0 ? x : fsum[p * FU_FS + c] + x;
+            const float *fl = a.feat_lr + (size_t)v * a.hl * a.wl * c_lr, *fh = a.feat_hr + (size_t)v * a.hh * a.wh * C_HR;
+            auto gather = [&](int p, int c) {
+                const float x = gather_channel(fl, fh, a.hl, a.wl, a.hh, a.wh, c_lr, sx[p], sy[p], c);
+                feat[p * fs + c] = x;
+                fsum[p * fs + c] = v == 0 ? x : fsum[p * fs + c] + x;
+            };
+            if (FIXED) {
+                for (int item = tid; item < P * c_g; item += NT) gather(item / c_g, item % c_g);
+            } else {   // (a wave per point, as mlp_fused_kernel gathers)
+                for (int p = wave; p < P; p += FU_WAVES)
+                    for (int c = lane; c < c_g; c += 64) gather(p, c);
             }
             __syncthreads();
-            fused_layers<NP, PB, true>(a, m, 0, M + 1, feat, act, slog, lane, wave, vsum, M, v == 0);
+            fused_layers<NP, PB, true>(a, fs, m, 0, M + 1, feat, act, slog, lane, wave, vsum, M, v == 0);
         }
         // the view means (SurfaceClassifier.py:70-76): features into feat, layer M's outputs into act (the logits into slog)
-        for (int item = tid; item < P * (C_G + 2); item += NT) {
-            const int p = item / (C_G + 2), c = item - p * (C_G + 2);
-            feat[p * FU_FS + c] = fsum[p * FU_FS + c] * va.inv;
+        if (FIXED) {
+            for (int item = tid; item < P * (c_g + 2); item += NT) {
+                const int p = item / (c_g + 2), c = item - p * (c_g + 2);
+                feat[p * fs + c] = fsum[p * fs + c] * va.inv;
+            }
+        } else {
+            for (int p = wave; p < P; p += FU_WAVES)
+                for (int c = lane; c < c_g + 2; c += 64) feat[p * fs + c] = fsum[p * fs + c] * va.inv;
         }
         store_view_mean<PB>(a, a.lay.layer[m][M], M == L - 1, act, slog, vsum, va.inv, lane, wave);
         __syncthreads();
-        fused_layers<NP, PB, false>(a, m, M + 1, L, feat, act, slog, lane, wave, vsum, -1, false);
+        fused_layers<NP, PB, false>(a, fs, m, M + 1, L, feat, act, slog, lane, wave, vsum, -1, false);
         if (tid < P) {
             const long long t = t0 + tid;
             const float lg = slog[tid];
@@ -151,20 +154,51 @@ __global__ __launch_bounds__(FU_WAVES * 64) void mlp_fused_views_kernel(FusedVie
     }
 }
 
+template <int NP, int PB>
+__global__ __launch_bounds__(FU_WAVES * 64) void mlp_fused_views_kernel(FusedViewsArgs va) {   // D = 256
+    extern __shared__ __attribute__((aligned(16))) float fu_smem[];
+    mlp_fused_views_body<NP, PB, true>(va, fu_smem);
+}
+
+template <int NP, int PB>
+__global__ __launch_bounds__(FU_WAVES * 64) void mlp_anyd_views_kernel(FusedViewsArgs va) {    // any other D
+    extern __shared__ __attribute__((aligned(16))) float fu_smem[];
+    mlp_fused_views_body<NP, PB, false>(va, fu_smem);
+}
+
 // points per tile: 32 when the widest hidden layer leaves room for them in LDS, else 16 (0: not even those - the views limit)
-static int fused_views_point_bytes(const GenLayout &lay) { return (lay.max_hidden + 4 + 2 * FU_FS) * 4 + 24; }
+static int fused_views_point_bytes(const GenLayout &lay) { return (lay.max_hidden + 4 + 2 * gen_feat_stride(lay.hg_dim)) * 4 + 24; }
 static int fused_views_pb(const GenLayout &lay) {
     const int b = fused_views_point_bytes(lay);
-    return 32 * b <= 160 * 1024 ? 2 : (16 * b <= 160 * 1024 ? 1 : 0);
+    return 32 * b <= GEN_LDS_BYTES ? 2 : (16 * b <= GEN_LDS_BYTES ? 1 : 0);
 }
-// the widest padded hidden layer a 16-point tile holds: 1824
-constexpr int FV_MAX_HIDDEN = ((160 * 1024 / 16 - 24) / 4 - 4 - 2 * FU_FS) / GEN_KT * GEN_KT;
+// the widest padded hidden layer a 16-point tile holds: 1824 up to the released D = 256 (whose two 356-float rows set it), less
+// for a larger D (gen_max_hidden: 1312 at D = 512)
+constexpr int FV_MAX_HIDDEN = ((GEN_LDS_BYTES / 16 - 24) / 4 - 4 - 2 * 356) / GEN_KT * GEN_KT;
 #define FV_WIDTH_LIMIT "multi-view: hidden widths must be at most 1824 (the LDS of a 16-point tile)"
 static_assert(FV_MAX_HIDDEN == 1824, "FV_WIDTH_LIMIT names this number");
+static int fused_views_max_hidden(int D) { return gen_max_hidden(D, 2, 24, FV_MAX_HIDDEN); }
+// refuses a pair whose widest hidden layer the multi-view tile cannot hold
+static int fused_views_check_width(const GenLayout &lay) {
+    SURS_REQUIRE(lay.max_hidden <= FV_MAX_HIDDEN, FV_WIDTH_LIMIT);
+    SURS_REQUIRE(lay.max_hidden <= fused_views_max_hidden(lay.hg_dim),
+                 "multi-view: hidden widths must be at most %d with hg_dim %d (the LDS of a 16-point tile)", fused_views_max_hidden(lay.hg_dim),
+                 lay.hg_dim);
+    return 0;
+}
 static int fused_views_lds_bytes(const GenLayout &lay, int pb) { return 16 * pb * fused_views_point_bytes(lay); }
 
 template <int NP, int PB>
 static int launch_fused_views_t(hipStream_t st, const FusedViewsArgs &a, int lds) {
+    if (a.f.lay.hg_dim != C_LR) {
+        static DeviceOnce attr_anyd;
+        if (attr_anyd.first())
+            SURS_HIP_CHECK(hipFuncSetAttribute((const void *)mlp_anyd_views_kernel<NP, PB>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               lds > 65536 ? 160 * 1024 : 65536));
+        hipLaunchKernelGGL((mlp_anyd_views_kernel<NP, PB>), dim3((unsigned)ceil_div(a.f.n, 16 * PB)), dim3(FU_WAVES * 64), lds, st, a);
+        SURS_LAUNCH_CHECK();
+        return 0;
+    }
     static DeviceOnce attr;
     if (attr.first())
         SURS_HIP_CHECK(hipFuncSetAttribute((const void *)mlp_fused_views_kernel<NP, PB>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -177,7 +211,7 @@ static int launch_fused_views_t(hipStream_t st, const FusedViewsArgs &a, int lds
 static int run_fused_views(hipStream_t st, FusedViewsArgs &a) {
     if (a.f.n == 0) return 0;
     const int pb = fused_views_pb(a.f.lay), lds = fused_views_lds_bytes(a.f.lay, pb), parts = fused_parts();
-    a.f.as = a.f.lay.max_hidden + 4;
+    fused_strides(a.f);
     switch (parts * 2 + pb - 1) {
     case 2: return launch_fused_views_t<1, 1>(st, a, lds);
     case 3: return launch_fused_views_t<1, 2>(st, a, lds);
@@ -196,7 +230,7 @@ static int fused_views_prepare(FusedViewsArgs &a, const SursMlpShape *lr, const 
     memset(&a, 0, sizeof(a));
     const int rc = fused_prepare(a.f, lr, hr, no_calib, zmul, zdiv, feat_lr, hl, wl, feat_hr, hh, wh, blob);
     if (rc) return rc;
-    SURS_REQUIRE(a.f.lay.max_hidden <= FV_MAX_HIDDEN, FV_WIDTH_LIMIT);
+    if (const int rcw = fused_views_check_width(a.f.lay)) return rcw;
     a.calibs = calibs;
     a.V = num_views;
     a.inv = 1.0f / (float)num_views;
@@ -211,8 +245,9 @@ extern "C" int surs_mlp_generic_views_info(const SursMlpShape *lr, const SursMlp
     SURS_REQUIRE(num_views >= 1 && num_views <= FV_MAX_VIEWS, "num_views must be in [1, 64]");
     GenLayout lay;
     const int rc = gen_layout(*lr, *hr, lay);
-    SURS_REQUIRE(rc == 0, "unsupported SurfaceClassifier shape: %s", gen_shape_error(rc));
-    SURS_REQUIRE(lay.max_hidden <= FV_MAX_HIDDEN, FV_WIDTH_LIMIT);
+    char why[160];
+    SURS_REQUIRE(rc == 0, "unsupported SurfaceClassifier shape: %s", gen_shape_error(rc, *lr, why));
+    if (const int rcw = fused_views_check_width(lay)) return rcw;
     const int pb = fused_views_pb(lay);
     if (tile_points) *tile_points = 16 * pb;
     if (lds_bytes) *lds_bytes = fused_views_lds_bytes(lay, pb);

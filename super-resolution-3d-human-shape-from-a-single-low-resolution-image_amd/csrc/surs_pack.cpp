@@ -310,7 +310,9 @@ extern "C" size_t surs_mlp_pack_generic(const SursMlpShape *lr, const float *con
     GenLayout lay;
     const int rc = gen_layout(*lr, *hr, lay);
     if (rc) {
-        fail(SURS_E_INVALID, "unsupported SurfaceClassifier shape (%s): %s", rc == gen_shape_check(*lr, 0) ? "lr" : "hr", gen_shape_error(rc));
+        char buf[160];
+        fail(SURS_E_INVALID, "unsupported SurfaceClassifier shape (%s): %s", rc == gen_shape_check(*lr, 0, gen_hg_dim(*lr)) ? "lr" : "hr",
+             gen_shape_error(rc, *lr, buf));
         return 0;
     }
     if (!blob) return (size_t)lay.total;

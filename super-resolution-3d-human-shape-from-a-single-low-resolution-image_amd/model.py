@@ -13,6 +13,8 @@ Encoder options: --norm group | batch and --scale 1..4 (anything else: ValueErro
 EVAL mode - y = (x - running_mean) / sqrt(running_var + 1e-5) * weight + bias, always from the running statistics: train() here keeps
 every stack's output as the reference does but never switches to batch statistics; num_batches_tracked is loaded, kept and returned by
 state_dict(), and otherwise ignored.  --scale s: img_SR [V,3,sH,sW], feature_lr [V,256,sH/4,sW/4], feature_hr [V,64,sH,sW].
+--hg_dim D (multiples of 16 from 16 to 512): im_feat_list_lr [V,D,.,.]; the classifiers then read D + 65 / D + 66 channels
+(--mlp_dim_lr / --mlp_dim_hr must start with them) and run on the fused evaluators of native.query_points_generic.
 """
 from collections import OrderedDict
 
@@ -56,6 +58,7 @@ class SuRSNet:
         self.precision = getattr(opt, "precision", "fp32")
         self._spec = weights.state_dict_spec(opt)            # (--norm other than group | batch: ValueError)
         encoder.check_scale(getattr(opt, "scale", 2))        # (--scale outside 1..4: ValueError)
+        native.check_hg_dim(getattr(opt, "hg_dim", 256))     # (--hg_dim not a multiple of 16 in 16..512: ValueError)
         # reference init: normal(0, 0.02) conv weights, zero bias, GroupNorm 1/0 (lib/net_util.py:99-132); here the
         # constructor leaves deterministic synthetic weights in place until load_state_dict() replaces them
         self._sd = OrderedDict((k, torch.from_numpy(v)) for k, v in weights.synthetic_state_dict(opt, seed=0).items())
@@ -254,7 +257,7 @@ class SuRSNet:
         return out
 
     def views_features(self):
-        """(feat_lr [V,hl,wl,256], feat_hr [V,hh,wh,64]) contiguous NHWC device tensors of every view: what the multi-view evaluator of
+        """(feat_lr [V,hl,wl,hg_dim], feat_hr [V,hh,wh,64]) contiguous NHWC device tensors of every view: what the multi-view evaluator of
         classifiers of any shape reads.  Cached as features() caches (same key rules, invalidate_feature_cache): the octree walk and
         the reference's sweep loop ask for them once per batch."""
         if not self.im_feat_list_lr or not self.im_feat_list_hr:

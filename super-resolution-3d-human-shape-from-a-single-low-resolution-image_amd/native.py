@@ -370,16 +370,53 @@ def pack_mlp(sd, dtype, device):
 
 DEFAULT_MLP_SHAPES = (((321, 1024, 512, 256, 128, 1), (2, 3, 4)), ((322, 1024, 512, 256, 128, 1), (2, 3, 4)))
 MLP_MAX_LAYERS, MLP_MAX_WIDTH = 8, 2048
+HG_DIM_RULE = "the supported values are the multiples of 16 from 16 to 512"
+
+
+def check_hg_dim(hg_dim):
+    """--hg_dim, the channels of the hourglass encoder's output (lib/model/HGFilters.py:166-174): multiples of 16 (the cin % 16 rule
+    of the split-operand convolutions, which al{s} meets with cin = hg_dim) from 16 to 512 (beyond it the LDS of the fused
+    evaluators leaves too little for the hidden layers).  Returns it as an int; ValueError otherwise."""
+    ok = isinstance(hg_dim, (int, np.integer)) and not isinstance(hg_dim, bool) and 16 <= hg_dim <= 512 and hg_dim % 16 == 0
+    if not ok:
+        raise ValueError("hg_dim %r: %s" % (hg_dim, HG_DIM_RULE))
+    return int(hg_dim)
+
+
+def mlp_max_hidden(hg_dim, views=False):
+    """The widest hidden layer the fused evaluator (views: the multi-view one) takes with --hg_dim hg_dim: what a 16-point tile holds
+    in the 160 KiB of LDS beside its feature rows of pad32(hg_dim + 66) + 4 floats (csrc/surs_mlp_generic.h gen_max_hidden): 2048 /
+    1824 up to the released 256, less beyond it."""
+    fs = -(-(hg_dim + 66) // 32) * 32 + 4
+    rows, extra, cap = (2, 24, 1824) if views else (1, 16, MLP_MAX_WIDTH)
+    return min(cap, ((160 * 1024 // 16 - extra) // 4 - 4 - rows * fs) // 32 * 32)
+
+
+def mlp_hg_dim(shapes):
+    """--hg_dim of a classifier pair: its lr input width is [hg_dim lr | 64 hr | z]."""
+    return int(shapes[0][0][0]) - 65
+
+
+def _check_feat_channels(c_lr, c_hr, g):
+    """The feature maps a generic evaluator is about to read against the shape it was packed for: the kernel reads rows of hg_dim
+    floats, so any other channel count would be read out of bounds."""
+    D = mlp_hg_dim(g.shapes)
+    if c_lr != D or c_hr != 64:
+        raise ValueError("feature maps with %d lr / %d hr channels; the classifiers (input width %d) read %d (--hg_dim) / 64"
+                         % (c_lr, c_hr, g.shapes[0][0][0], D))
 
 
 def mlp_shapes(sd, opt=None):
     """((dims_lr, res_lr), (dims_hr, res_hr)) of the two SurfaceClassifiers in state dict `sd`, derived from the weight tensors
     (lib/model/SurfaceClassifier.py:7-43: layer l sees dims[l] channels, plus dims[0] when l is a skip layer) and cross-checked
     against opt's --mlp_dim_* / --mlp_res_layers_* / --no_residual when opt is given.  Raises ValueError naming the limit for
-    anything the evaluators do not support: 1..8 layers, input width 321 (lr) / 322 (hr) - fixed by the encoder -, last width 1,
-    hidden widths 1..2048, skip layers in [0, L)."""
+    anything the evaluators do not support: 1..8 layers, input width hg_dim + 65 (lr) / hg_dim + 66 (hr) - fixed by the encoder's
+    --hg_dim, taken from opt (256 without it: 321 / 322) -, last width 1, hidden widths 1..2048 (less for hg_dim > 256:
+    mlp_max_hidden), skip layers in [0, L)."""
     out = []
-    for m, (prefix, c0) in enumerate((("mlp_lr.", 321), ("mlp_hr.", 322))):
+    hg_dim = check_hg_dim(getattr(opt, "hg_dim", 256)) if opt is not None else 256
+    max_width = mlp_max_hidden(hg_dim)
+    for m, (prefix, c0) in enumerate((("mlp_lr.", hg_dim + 65), ("mlp_hr.", hg_dim + 66))):
         L = 0
         while prefix + "conv%d.weight" % L in sd:
             L += 1
@@ -391,8 +428,8 @@ def mlp_shapes(sd, opt=None):
             cout, cin = int(w.shape[0]), int(w.shape[1])
             if l == 0:
                 if cin not in (c0, 2 * c0):
-                    raise ValueError("%s: input width %d; it must be %d (256 + 64 + z%s), or %d with a skip at layer 0"
-                                     % (prefix[:-1], cin, c0, "" if m == 0 else " + p_lr", 2 * c0))
+                    raise ValueError("%s: input width %d; it must be %d (%d + 64 + z%s: --hg_dim %d), or %d with a skip at layer 0"
+                                     % (prefix[:-1], cin, c0, hg_dim, "" if m == 0 else " + p_lr", hg_dim, 2 * c0))
                 dims.append(c0)
             if cin - dims[l] == c0:
                 res.append(l)
@@ -404,6 +441,9 @@ def mlp_shapes(sd, opt=None):
         for d in dims[1:-1]:
             if not 1 <= d <= MLP_MAX_WIDTH:
                 raise ValueError("%s: hidden width %d; hidden widths must be between 1 and %d" % (prefix[:-1], d, MLP_MAX_WIDTH))
+            if d > max_width:   # (the library's words: gen_shape_error)
+                raise ValueError("%s: hidden width %d; hidden widths must be at most %d with hg_dim %d (the LDS of a 16-point tile)"
+                                 % (prefix[:-1], d, max_width, hg_dim))
         if opt is not None:
             want_dims = [int(v) for v in (opt.mlp_dim_lr if m == 0 else opt.mlp_dim_hr)]
             want_res = [] if opt.no_residual else sorted(set(int(v) for v in (opt.mlp_res_layers_lr if m == 0 else opt.mlp_res_layers_hr)))
@@ -452,7 +492,7 @@ def _shape_struct(dims, res):
 
 def pack_mlp_generic_host(sd, shapes=None):
     """surs_mlp_pack_generic into a numpy uint8 array: (host blob, shapes)."""
-    shapes = mlp_shapes(sd) if shapes is None else shapes
+    shapes = mlp_shapes(sd) if shapes is None else shapes   # (given: any --hg_dim, the library checks them)
     keep, args = [], []
     for m, prefix in enumerate(("mlp_lr.", "mlp_hr.")):
         L = len(shapes[m][0]) - 1
@@ -495,7 +535,8 @@ def query_points_generic(points, calib, zmul, zdiv, feat_lr, feat_hr, g, p_lr=No
     if p_lr is not None:
         lg[1] = None
     cal = (C.c_float * 12)(*[float(v) for v in calib])
-    assert feat_lr.ld == feat_lr.c == 256 and feat_hr.ld == feat_hr.c == 64
+    _check_feat_channels(feat_lr.c, feat_hr.c, g)
+    assert feat_lr.ld == feat_lr.c and feat_hr.ld == feat_hr.c
     check(lib().surs_query_points_generic(_ptr(points), n, cal, float(zmul), float(zdiv), feat_lr.ptr(), feat_lr.h, feat_lr.w,
                                           feat_hr.ptr(), feat_hr.h, feat_hr.w, C.byref(g.lr), C.byref(g.hr), _ptr(g.blob), _ptr(p_lr),
                                           _ptr(phr), None if p_lr is not None else _ptr(plr), _ptr(lg[0]), _ptr(lg[1]), _stream()))
@@ -511,7 +552,8 @@ def query_grid_generic(i0, i1, ry, rz, mat, calib, zmul, zdiv, feat_lr, feat_hr,
         vol_lr = torch.empty_like(vol_hr)
     m = (C.c_double * 12)(*[float(v) for v in np.asarray(mat, np.float64).reshape(-1)[:12]])
     cal = (C.c_float * 12)(*[float(v) for v in calib])
-    assert feat_lr.ld == feat_lr.c == 256 and feat_hr.ld == feat_hr.c == 64
+    _check_feat_channels(feat_lr.c, feat_hr.c, g)
+    assert feat_lr.ld == feat_lr.c and feat_hr.ld == feat_hr.c
     check(lib().surs_query_grid_generic(i0, i1, ry, rz, m, cal, float(zmul), float(zdiv), feat_lr.ptr(), feat_lr.h, feat_lr.w,
                                         feat_hr.ptr(), feat_hr.h, feat_hr.w, C.byref(g.lr), C.byref(g.hr), _ptr(g.blob), _ptr(vol_hr),
                                         _ptr(vol_lr), _stream()))
@@ -539,7 +581,7 @@ def _device_calibs(calibs, dev):
 
 def query_points_generic_views(points, calibs, zmul, zdiv, feat_lr, feat_hr, g, p_lr=None, want_logits=False):
     """surs_query_points_generic_views: both classifiers of GenericMlp g for one subject seen by V views, in one launch.  points
-    [V,3,N] f32 device tensor; calibs [V,12] (host rows or a device tensor); feat_lr [V,hl,wl,256] and feat_hr [V,hh,wh,64]
+    [V,3,N] f32 device tensor; calibs [V,12] (host rows or a device tensor); feat_lr [V,hl,wl,hg_dim] and feat_hr [V,hh,wh,64]
     contiguous NHWC device tensors; p_lr [V,N] given: the hr classifier alone.  Returns (pred_hr [V,N], pred_lr [V,N][, logit_hr [N],
     logit_lr [N]]); with p_lr, pred_lr is p_lr and logit_lr None."""
     points = _f32c(points)
@@ -547,7 +589,8 @@ def query_points_generic_views(points, calibs, zmul, zdiv, feat_lr, feat_hr, g, 
     mlp_generic_views_info(g.shapes, V)
     dev = points.device
     feat_lr, feat_hr = _f32c(feat_lr), _f32c(feat_hr)
-    assert feat_lr.shape[0] == V and feat_hr.shape[0] == V and feat_lr.shape[3] == 256 and feat_hr.shape[3] == 64
+    _check_feat_channels(feat_lr.shape[3], feat_hr.shape[3], g)
+    assert feat_lr.shape[0] == V and feat_hr.shape[0] == V
     cal = _device_calibs(calibs, dev)
     assert cal.shape == (V, 12)
     phr = torch.empty((V, n), dtype=torch.float32, device=dev)
@@ -574,7 +617,8 @@ def query_grid_generic_views(i0, i1, ry, rz, mat, calibs, zmul, zdiv, feat_lr, f
     V = feat_lr.shape[0]
     mlp_generic_views_info(g.shapes, V)
     dev = g.blob.device
-    assert feat_hr.shape[0] == V and feat_lr.shape[3] == 256 and feat_hr.shape[3] == 64
+    _check_feat_channels(feat_lr.shape[3], feat_hr.shape[3], g)
+    assert feat_hr.shape[0] == V
     cal = _device_calibs(calibs, dev)
     assert cal.shape == (V, 12)
     if vol_hr is None:
