@@ -381,6 +381,47 @@ int surs_query_grid_generic(int i0, int i1, int ry, int rz, const double *mat, c
                             const float *feat_lr, int hl, int wl, const float *feat_hr, int hh, int wh, const SursMlpShape *lr,
                             const SursMlpShape *hr, const void *blob, float *vol_hr, float *vol_lr, void *stream);
 
+/* ------------------------------------------------------------------ every hourglass stack: the validation forward
+ * In training mode filter_lr keeps every stack's feature map (lib/model/SuRSNet.py:101-110) and query_mr / query_sr evaluate the
+ * classifiers once per kept map (SuRSNet.py:149-157, 175-185): pass s reads feat_lr[s] and the one hr map; stack s's masked lr
+ * prediction is the last input channel of stack s's hr classifier.  The two entries below do that for the S = num_stacks >= 1 maps of
+ * one image.  feat_lr: HOST array of S device pointers, each map [hl][wl][D]; outputs (and logits, nullable) are [S][n], row s =
+ * stack s.  Three forms:
+ *   both classifiers   p_lr NULL, pred_hr and pred_lr given
+ *   hr only            p_lr [S][n] given (query_sr on other points than query_mr's: row s feeds stack s); pred_lr / logit_lr ignored
+ *   lr only            pred_hr NULL, pred_lr given; logit_hr ignored (the pass of forward() whose hr predictions nothing reads)
+ * Row s is bit for bit what the single-map entry writes for map s in the same form and operand split; S = 1 is the single-map entry. */
+
+/* surs_query_points_generic over S maps in ONE launch (csrc/surs_mlp_fused_stacks.inc: grid = point tiles x stacks, the map pointers
+ * in the launch argument, eight per launch - more maps: one launch per eight).  Other arguments as surs_query_points_generic. */
+int surs_query_points_generic_stacks(const float *points, int n, const float *calib, float zmul, float zdiv, int num_stacks,
+                                     const float *const *feat_lr, int hl, int wl, const float *feat_hr, int hh, int wh,
+                                     const SursMlpShape *lr, const SursMlpShape *hr, const void *blob, const float *p_lr, float *pred_hr,
+                                     float *pred_lr, float *logit_hr, float *logit_lr, void *stream);
+
+/* The released shape: the layer kernels of surs_query_points / surs_query_points_hr sequenced once per map inside the library, in one
+ * call on one workspace (surs_query_workspace_bytes(n), whatever S).  Other arguments as surs_query_points. */
+int surs_query_points_stacks(const float *points, int n, const float *calib, float zmul, float zdiv, int num_stacks,
+                             const float *const *feat_lr, int hl, int wl, const float *feat_hr, int hh, int wh, const void *mlp_blob,
+                             void *workspace, size_t workspace_bytes, const float *p_lr, float *pred_hr, float *pred_lr,
+                             float *logit_hr, float *logit_lr, void *stream);
+
+/* The four terms of SuRSNet.forward's loss (lib/model/SuRSNet.py:196-236) in one deterministic reduction (a fixed partition, float64
+ * partial sums, a second stage in fixed order, no atomics: two runs give the same bits).  Device arrays:
+ *   pred_lr, pred_hr [S][m] (S = num_stacks), lab_lr, lab_hr [m] - the labels the lr / hr predictions are held against -,
+ *   img_sr, img_hr [k] in one common element order.
+ *   terms[0] = mean over stacks of MSE(pred_lr[s], lab_lr)      get_error_lr
+ *   terms[1] = the same of pred_hr and lab_hr                   get_error_hr
+ *   terms[2] = mean |img_sr - img_hr|                           get_errorSR
+ *   terms[3] = MSE(lab_hr - lab_lr, pred_hr[S-1] - pred_lr[S-1]) get_error_disp_1
+ * A term whose inputs are NULL is 0 (terms[3] needs all four of the first group).  weights: HOST [4] (opt.mlp1, mlp2, srweight,
+ * dispweight), total: device, both nullable: *total = w[0] terms[0] + w[1] terms[1] + w[2] terms[2] + w[3] terms[3] in float32, left to
+ * right (SuRSNet.py:265).  workspace: surs_forward_losses_workspace_bytes() bytes, 8-byte aligned.  No synchronisation. */
+size_t surs_forward_losses_workspace_bytes(void);
+int surs_forward_losses(const float *pred_lr, const float *pred_hr, int num_stacks, long long m, const float *lab_lr,
+                        const float *lab_hr, const float *img_sr, const float *img_hr, long long k, const float *weights,
+                        void *workspace, size_t workspace_bytes, float *terms, float *total, void *stream);
+
 /* Multi-view query of one subject (num_views = V in [1, 64], orthogonal projection) for classifiers of any supported shape, in ONE
  * launch per call (csrc/surs_mlp_fused_views.inc): lib/model/SurfaceClassifier.py:53-81 with num_views > 1 - layers 0 .. L/2 per
  * view on that view's features, then the view mean ((sum in view order) * (1/V)) of layer L/2's outputs and of the input features,

@@ -155,6 +155,12 @@ _SIGS = {
                                                   _vp, _vp, _vp]),
     "surs_query_grid_generic_views": (C.c_int, [_i, _i, _i, _i, _vp, _i, _vp, _f, _f, _vp, _i, _i, _vp, _i, _i, _shp, _shp, _vp, _vp,
                                                 _vp, _vp]),
+    "surs_query_points_generic_stacks": (C.c_int, [_vp, _i, _vp, _f, _f, _i, _vp, _i, _i, _vp, _i, _i, _shp, _shp, _vp, _vp, _vp, _vp,
+                                                   _vp, _vp, _vp]),
+    "surs_query_points_stacks": (C.c_int, [_vp, _i, _vp, _f, _f, _i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp,
+                                           _vp]),
+    "surs_forward_losses_workspace_bytes": (_sz, []),
+    "surs_forward_losses": (C.c_int, [_vp, _vp, _i, C.c_longlong, _vp, _vp, _vp, _vp, C.c_longlong, _vp, _vp, _sz, _vp, _vp, _vp]),
     "surs_set_operand_split": (C.c_int, [_i]),
     "surs_set_operand_split_local": (C.c_int, [_i]),
     "surs_set_grid_kernel": (C.c_int, [_i]),

@@ -192,8 +192,10 @@ __device__ __forceinline__ void fused_classifier(const FusedArgs &a, const int f
     fused_layers<NP, PB, false>(a, fs, m, 0, a.lay.n_layers[m], feat, act, slog, lane, wave, unused, -1, false);
 }
 
-template <int NP, int PB, bool FIXED>
-__device__ __forceinline__ void mlp_fused_body(const FusedArgs &a, float *fu_smem) {
+// IO: where the lr feature map, the given lr occupancies and the outputs of THIS workgroup are - the launch argument itself, or the
+// stack's FusedIo of surs_mlp_fused_stacks.inc; LR_ONLY (that file's lr-only form): the tile ends after mlp_lr.
+template <int NP, int PB, bool FIXED, bool LR_ONLY = false, class IO = FusedArgs>
+__device__ __forceinline__ void mlp_fused_body(const FusedArgs &a, float *fu_smem, const IO &io) {
     constexpr int P = 16 * PB;
     const FeatDims<FIXED> fd(a);
     const int c_lr = fd.c_lr, c_g = fd.c_g, fs = fd.fs;
@@ -211,7 +213,7 @@ __device__ __forceinline__ void mlp_fused_body(const FusedArgs &a, float *fu_sme
             project_point(a.src, px, py, pz, X, Y, Z);
             in = in_image(X, Y);
             zf = Z * a.src.zmul / a.src.zdiv;
-            if (a.p_lr) pl = a.p_lr[t];
+            if (io.p_lr) pl = io.p_lr[t];
         }
         sx[tid] = X;
         sy[tid] = Y;
@@ -226,15 +228,15 @@ __device__ __forceinline__ void mlp_fused_body(const FusedArgs &a, float *fu_sme
     if (FIXED) {
         for (int item = tid; item < P * c_g; item += FU_WAVES * 64) {
             const int p = item / c_g, c = item - p * c_g;
-            feat[p * fs + c] = gather_channel(a.feat_lr, a.feat_hr, a.hl, a.wl, a.hh, a.wh, c_lr, sx[p], sy[p], c);
+            feat[p * fs + c] = gather_channel(io.feat_lr, a.feat_hr, a.hl, a.wl, a.hh, a.wh, c_lr, sx[p], sy[p], c);
         }
     } else {   // a wave per point: no division by the run-time channel count
         for (int p = wave; p < P; p += FU_WAVES)
             for (int c = lane; c < c_g; c += 64)
-                feat[p * fs + c] = gather_channel(a.feat_lr, a.feat_hr, a.hl, a.wl, a.hh, a.wh, c_lr, sx[p], sy[p], c);
+                feat[p * fs + c] = gather_channel(io.feat_lr, a.feat_hr, a.hl, a.wl, a.hh, a.wh, c_lr, sx[p], sy[p], c);
     }
     __syncthreads();
-    if (!a.p_lr) {
+    if (!io.p_lr) {
         fused_classifier<NP, PB>(a, fs, 0, feat, act, slog, lane, wave);
         if (tid < P) {
             const long long t = t0 + tid;
@@ -242,19 +244,20 @@ __device__ __forceinline__ void mlp_fused_body(const FusedArgs &a, float *fu_sme
             const float p = smask[tid] * (1.0f / (1.0f + expf(-lg)));
             feat[tid * fs + c_g + 1] = p;
             if (t < a.n) {
-                a.pred_lr[t] = p;
-                if (a.logit_lr) a.logit_lr[t] = lg;
+                io.pred_lr[t] = p;
+                if (io.logit_lr) io.logit_lr[t] = lg;
             }
         }
         __syncthreads();
     }
+    if (LR_ONLY) return;
     fused_classifier<NP, PB>(a, fs, 1, feat, act, slog, lane, wave);
     if (tid < P) {
         const long long t = t0 + tid;
         const float lg = slog[tid];
         if (t < a.n) {
-            a.pred_hr[t] = smask[tid] * (1.0f / (1.0f + expf(-lg)));
-            if (a.logit_hr) a.logit_hr[t] = lg;
+            io.pred_hr[t] = smask[tid] * (1.0f / (1.0f + expf(-lg)));
+            if (io.logit_hr) io.logit_hr[t] = lg;
         }
     }
 }
@@ -262,13 +265,13 @@ __device__ __forceinline__ void mlp_fused_body(const FusedArgs &a, float *fu_sme
 template <int NP, int PB>
 __global__ __launch_bounds__(FU_WAVES * 64) void mlp_fused_kernel(FusedArgs a) {   // D = 256
     extern __shared__ __attribute__((aligned(16))) float fu_smem[];
-    mlp_fused_body<NP, PB, true>(a, fu_smem);
+    mlp_fused_body<NP, PB, true>(a, fu_smem, a);
 }
 
 template <int NP, int PB>
 __global__ __launch_bounds__(FU_WAVES * 64) void mlp_anyd_kernel(FusedArgs a) {    // any other D
     extern __shared__ __attribute__((aligned(16))) float fu_smem[];
-    mlp_fused_body<NP, PB, false>(a, fu_smem);
+    mlp_fused_body<NP, PB, false>(a, fu_smem, a);
 }
 
 // points per tile: 32 when the widest hidden layer leaves room for them in LDS, else 16

@@ -475,7 +475,7 @@ static int launch_layer(hipStream_t st, int parts, int out, const void *W, int M
 static int run_points_fp32(hipStream_t st, const PointSource &src, long long n, const float *feat_lr, int hl, int wl,
                            const float *feat_hr, int hh, int wh, const char *blob, const MlpBlobHeader &h,
                            const Fp32Workspace &w, float *pred_hr, float *pred_lr, float *logit_hr, float *logit_lr,
-                           int parts = 0, const float *p_lr_in = nullptr) {
+                           int parts = 0, const float *p_lr_in = nullptr, bool lr_only = false) {
     const long long np = w.np;
     // (the calling thread asked for the one-product point path - surs_set_operand_split_local(1): one f16 part per operand, the
     //  first plane of the two-part weight image; three times less matrix work than the fp32-grade path, 11 significant bits)
@@ -498,7 +498,7 @@ static int run_points_fp32(hipStream_t st, const PointSource &src, long long n, 
     }
     const SplitSeg none = {nullptr, 0, 0}, f = {w.Fs, fs_part, C0PAD / 16}, y0 = {w.Y0s, (long long)D1 * np, D1 / 16},
                    y1 = {w.Y1s, (long long)D2 * np, D2 / 16}, y2 = {w.Y2s, (long long)D3 * np, D3 / 16};
-    for (int m = p_lr_in ? 1 : 0; m < 2; ++m) {
+    for (int m = p_lr_in ? 1 : 0; m < (lr_only ? 1 : 2); ++m) {   // (lr_only: surs_query_points_stacks' lr-only form)
         auto W = [&](int l) { return (const void *)(blob + (parts <= 2 ? h.wt2[m][l] : h.wt3[m][l])); };   // (one part: the image's first plane, f16(w))
         auto BI = [&](int l) { return (const float *)(blob + h.bias[m][l]); };
         int rc;
@@ -2169,4 +2169,5 @@ extern "C" int surs_query_points_columns(const float *points, long long ld, int 
 }
 
 #include "surs_mlp_fused.inc"
+#include "surs_mlp_fused_stacks.inc"
 #include "surs_mlp_fused_views.inc"

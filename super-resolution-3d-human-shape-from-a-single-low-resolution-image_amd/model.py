@@ -3,11 +3,13 @@
 Same public surface as the reference's `SuRSNet(BaseSuRSNet)` as consumed by eval_SuRS.py / gen_mesh /
 reconstruction (/root/reference/lib/model/SuRSNet.py:44-187, lib/model/BaseSuRSNet.py:20-26,80-85;
 SURVEY.md section 8b): name, num_views, to(), eval(), train(), state_dict(), load_state_dict(), parameters(),
-super_res(), filter_hr(), filter_lr(), query_mr(), query_sr(), get_preds().
+super_res(), filter_hr(), filter_lr(), query_mr(), query_sr(), get_preds(), and - SuRSNet.py:196-266 - get_error_lr(), get_error_hr(),
+get_errorSR(), get_error_disp_1(), forward().
 
 It is NOT a torch.nn.Module: parameters are a flat ordered dict keyed exactly like the reference's state dict
 (all 553 keys, strict; 1036 with --norm batch), and every forward method sequences hand-written HIP kernels through the C ABI.  There is
-no training path (backward is out of scope) and no CPU path: methods raise without a GPU / built library.
+no backward pass and no optimiser (out of scope) and no CPU path: methods raise without a GPU / built library.  forward() is the
+VALIDATION forward: every kept stack's predictions and the reference's loss, without an autograd graph (SuRSNet.py:240-266).
 
 Encoder options: --norm group | batch and --scale 1..4 (anything else: ValueError at construction).  --norm batch is nn.BatchNorm2d in
 EVAL mode - y = (x - running_mean) / sqrt(running_var + 1e-5) * weight + bias, always from the running statistics: train() here keeps
@@ -73,7 +75,10 @@ class SuRSNet:
         self.intermediate_preds_list_lr = []
         self.intermediate_preds_list_hr = []
         self._mr_points = None
+        self._mr_hr = None
         self._feat_cache = None
+        self._stack_feat_cache = None
+        self.labels_lr = self.labels_hr = None
         self._mr_version = 0
         self._sharded_encode = None   # dist.encode_sharded's arguments + the tensor it produced (the overflow retry of slab mode)
         self._last_images = None      # what super_res() last ran on, and which buffers came out of that run (reencode_wide)
@@ -256,6 +261,28 @@ class SuRSNet:
         self._feat_cache = (key, tl, th, out) if cacheable else None
         return out
 
+    def stack_features(self, b=0):
+        """([Img feat_lr of every kept stack], Img feat_hr) of image b of the encoded batch: what the stacks entries read - one pass per
+        entry of im_feat_list_lr, every pass on im_feat_list_hr[0] (SuRSNet.py:149-157, 175-185).  One map: features(b).  Cached as
+        features() caches, on the identity and version of every map."""
+        if len(self.im_feat_list_lr) <= 1:
+            fl, fh = self.features(b)
+            return [fl], fh
+        if not self.im_feat_list_hr:
+            raise RuntimeError("filter_lr / filter_hr must run before a query")
+        tls, th = list(self.im_feat_list_lr), self.im_feat_list_hr[0]
+        if any(b >= t.shape[0] for t in tls) or b >= th.shape[0]:
+            raise RuntimeError("the encoder ran on %d images, the query asks for image %d" % (tls[-1].shape[0], b))
+        ts = tls + [th]
+        cacheable = all(t.is_cuda and not t.is_inference() for t in ts)
+        key = (b,) + tuple((t.data_ptr(), tuple(t.shape), t.stride(), t._version if cacheable else None) for t in ts)
+        hit = self._stack_feat_cache
+        if cacheable and hit is not None and hit[0] == key and len(hit[1]) == len(ts) and all(x is y for x, y in zip(hit[1], ts)):
+            return hit[2]
+        out = [_as_img(t[b:b + 1]) for t in tls], _as_img(th[b:b + 1])
+        self._stack_feat_cache = (key, ts, out) if cacheable else None
+        return out
+
     def views_features(self):
         """(feat_lr [V,hl,wl,hg_dim], feat_hr [V,hh,wh,64]) contiguous NHWC device tensors of every view: what the multi-view evaluator of
         classifiers of any shape reads.  Cached as features() caches (same key rules, invalidate_feature_cache): the octree walk and
@@ -291,6 +318,7 @@ class SuRSNet:
         """Forget the converted copy of hand-assigned feature maps (see features(): needed only after an edit no version counter sees)."""
         self._feat_cache = None
         self._views_feat_cache = None
+        self._stack_feat_cache = None
 
     # ------------------------------------------------------------------ query
     def _zscale(self):
@@ -443,7 +471,9 @@ class SuRSNet:
         way if its features are what overflowed."""
         phr, plr = run() if first is None else first
         # (one small launch and a 4-byte read-back: surs_nonfinite; until round 6 two torch reductions and an addition)
-        if phr.numel() == plr.numel() and phr.dtype == plr.dtype == torch.float32 and phr.is_cuda:
+        if phr is None:   # (the lr-only pass of the stacks route)
+            finite = not native.any_nonfinite(plr)
+        elif phr.numel() == plr.numel() and phr.dtype == plr.dtype == torch.float32 and phr.is_cuda:
             finite = not native.any_nonfinite(phr, plr)
         else:
             finite = math.isfinite((phr.sum() + plr.sum()).item())
@@ -454,32 +484,93 @@ class SuRSNet:
         with native.wide_operands():
             fl, fh = self.features(b) if self.num_views == 1 else (self.im_feat_list_lr[-1], self.im_feat_list_hr[0])
             feats_ok = bool(torch.isfinite(fl.buf if hasattr(fl, "buf") else fl).all()) and bool(torch.isfinite(fh.buf if hasattr(fh, "buf") else fh).all())
+            if feats_ok and self.num_views == 1 and len(self.im_feat_list_lr) > 1:   # (the stacks route read every kept map)
+                feats_ok = all(bool(torch.isfinite(f.buf).all()) for f in self.stack_features(b)[0][:-1])
             if not feats_ok and not self.reencode_wide():
                 raise native._lib.NonFiniteVolumeError("the feature maps hold non-finite values and the images they were encoded "
                                                        "from are not known to this object (set by hand or by another call chain)")
             return run()
 
+    _STACKS_LIMIT = ("every kept hourglass stack (len(im_feat_list_lr) > 1, i.e. features filtered in training mode) and forward(): "
+                     "num_views == 1 and orthogonal projection only")
+
+    def _query_stacks(self, points, calibs, transforms, p_lr=None, lr_only=False):
+        """One pass per entry of im_feat_list_lr (SuRSNet.py:149-157, 175-185), each on im_feat_list_hr[0]: both classifiers, the hr
+        classifier alone fed stack by stack with p_lr (a list of S tensors [B,1,N]), or the lr classifier alone (lr_only).  One
+        library call per image for all stacks.  Returns (list of S pred_hr [B,1,N] - None with lr_only -, list of S pred_lr)."""
+        if self.num_views != 1 or self.projection_mode != "orthogonal":
+            raise NotImplementedError(self._STACKS_LIMIT)
+        dev = self._device()
+        zmul, zdiv = self._zscale()
+        g = self.generic_mlp()
+        S, B = len(self.im_feat_list_lr), points.shape[0]
+        if S == 0 or not self.im_feat_list_hr:
+            raise RuntimeError("filter_lr / filter_hr must run before a query")
+        if calibs.shape[0] != B:
+            raise ValueError("points [%d,3,N] and calibs [%d,4,4] disagree" % (B, calibs.shape[0]))
+        if p_lr is not None and len(p_lr) < S:
+            raise ValueError("query_sr: %d feature maps against the lr predictions of %d stacks (SuRSNet.py:180 indexes them by stack)"
+                             % (S, len(p_lr)))
+        cal = self._calib_rows(calibs, transforms)
+        outs = []
+        for b in range(B):
+            pts = points[b].to(dev, torch.float32).contiguous()
+            pl = None if p_lr is None else torch.stack([p[b].to(dev, torch.float32).reshape(-1) for p in p_lr[:S]])
+            if g is not None:
+                run = lambda: native.query_points_generic_stacks(pts, cal[b], zmul, zdiv, *self.stack_features(b), g, p_lr=pl,
+                                                                 lr_only=lr_only)
+            else:
+                # (the layer kernels whatever the point order: the column kernels of the single-map route have no per-stack form)
+                run = lambda: native.query_points_stacks(pts, cal[b], zmul, zdiv, *self.stack_features(b), self._mlp_blob(),
+                                                         self._workspace(), p_lr=pl, lr_only=lr_only)
+            # --precision bf16 | fp16: one f16 product per MAC, as the single-map query of that precision
+            with native.reduced_point_operands(self.precision in ("bf16", "fp16")):
+                first = run()
+            outs.append(self._finite_or_wide(run, b, first=first))
+
+        def per_stack(i):
+            if outs[0][i] is None:
+                return None
+            if B == 1:
+                return [outs[0][i][s].view(1, 1, -1) for s in range(S)]
+            return [torch.stack([o[i][s] for o in outs]).view(B, 1, -1) for s in range(S)]
+        return per_stack(0), per_stack(1)
+
     def query_mr(self, points, calibs, transforms=None, labels=None):
-        """Evaluates both classifiers in one fused pass; preds_hr is kept for the following query_sr."""
-        phr, plr = self._query(points, calibs, transforms)
+        """Evaluates both classifiers in one fused pass, once per entry of im_feat_list_lr (SuRSNet.py:131-159); the hr predictions
+        are kept for the following query_sr.  labels: stored as labels_lr (what get_error_lr holds the lr predictions against)."""
+        self._query_mr(points, calibs, transforms, labels, lr_only=False)
+
+    def _query_mr(self, points, calibs, transforms, labels, lr_only):
+        if labels is not None:
+            self.labels_lr = labels
+        if len(self.im_feat_list_lr) > 1 or lr_only:
+            phr, plr = self._query_stacks(points, calibs, transforms, lr_only=lr_only)
+        else:
+            phr, plr = self._query(points, calibs, transforms)
+            phr, plr = [phr], [plr]
         self._mr_points, self._mr_hr, self._mr_version = points, phr, points._version
         self._mr_args = (calibs, transforms)
-        self.intermediate_preds_list_lr = [plr]
-        self.preds_lr = plr
+        self.intermediate_preds_list_lr = plr
+        self.preds_lr = plr[-1]
 
     def query_sr(self, points, calibs, transforms=None, labels=None):
         """SuRSNet.py:161-187.  With the points (and calibs / transforms) of the preceding query_mr - the reference's eval_func and
         gen_mesh - the fused pass has already produced preds_hr.  Any other point set of the same N goes through the hr classifier
-        alone, fed with query_mr's lr predictions index by index, exactly as the reference concatenates them."""
+        alone, fed with query_mr's lr predictions index by index (and stack by stack), exactly as the reference concatenates them.
+        labels: stored as labels_hr."""
+        if labels is not None:
+            self.labels_hr = labels
         if self._mr_points is None:
             raise RuntimeError("query_sr needs the preceding query_mr (it consumes its lr predictions, SuRSNet.py:179)")
         # the same points as the preceding query_mr?  Decided without touching the data (a full-tensor compare is a device
         # synchronisation per call): the same tensor object, or the same storage / view / version
         ref, ver = self._mr_points, self._mr_version
-        same = (points is ref and points._version == ver) or (
+        have = self._mr_hr is not None and len(self._mr_hr) == len(self.im_feat_list_lr)   # (not after forward()'s lr-only pass)
+        same = have and ((points is ref and points._version == ver) or (
             points.data_ptr() == ref.data_ptr() and points.shape == ref.shape and points.stride() == ref.stride()
-            and points.dtype == ref.dtype and points._version == ver and ref._version == ver)
-        if not same and points is not ref and ref._version == ver:
+            and points.dtype == ref.dtype and points._version == ver and ref._version == ver))
+        if have and not same and points is not ref and ref._version == ver:
             # another tensor: the fused result stands if it holds the same values (this comparison synchronises; callers that
             # pass the tensor they gave query_mr never get here)
             same = points.shape == ref.shape and bool(torch.equal(points.to(ref.device), ref))
@@ -494,12 +585,92 @@ class SuRSNet:
             if points.shape[-1] != self.preds_lr.shape[-1] or points.shape[0] != self.preds_lr.shape[0]:
                 raise ValueError("query_sr: %s points against lr predictions %s (SuRSNet.py:179 concatenates them channel-wise)"
                                  % (tuple(points.shape), tuple(self.preds_lr.shape)))
-            phr, _ = self._query(points, calibs, transforms, p_lr=self.preds_lr)
-        self.intermediate_preds_list_hr = [phr]
-        self.preds_hr = phr
+            if len(self.im_feat_list_lr) > 1:
+                phr, _ = self._query_stacks(points, calibs, transforms, p_lr=self.intermediate_preds_list_lr)
+            else:
+                phr, _ = self._query(points, calibs, transforms, p_lr=self.intermediate_preds_list_lr[0])
+                phr = [phr]
+        self.intermediate_preds_list_hr = phr
+        self.preds_hr = phr[-1]
 
     def get_preds(self):
         return self.preds_hr, self.preds_lr
 
-    def forward(self, *a, **k):
-        raise NotImplementedError("training forward/backward is out of scope of the inference hot path")
+    # ------------------------------------------------------------------ the validation forward: losses
+    def _stacked(self, preds):
+        """[S,M] device tensor of a list of S predictions [B,1,N] (M = B N)."""
+        dev = self._device()
+        return torch.stack([p.to(dev, torch.float32).reshape(-1) for p in preds])
+
+    def _labels(self, which):
+        lab = self.labels_lr if which == "lr" else self.labels_hr
+        if lab is None:
+            raise RuntimeError("labels_%s is not set: pass labels= to query_%s (SuRSNet.py:134-136, 164-165)"
+                               % (which, "mr" if which == "lr" else "sr"))
+        return lab.to(self._device(), torch.float32).reshape(-1).contiguous()
+
+    def get_error_lr(self):
+        """SuRSNet.py:196-204: the mean over stacks of MSE(intermediate_preds_list_lr[s], labels_lr); 0-dim float32 device tensor."""
+        if not self.intermediate_preds_list_lr:
+            raise RuntimeError("get_error_lr needs a preceding query_mr")
+        return native.forward_losses(pred_lr=self._stacked(self.intermediate_preds_list_lr), lab_lr=self._labels("lr"))[0][0]
+
+    def get_error_hr(self):
+        """SuRSNet.py:206-214: the same of intermediate_preds_list_hr and labels_hr."""
+        if not self.intermediate_preds_list_hr:
+            raise RuntimeError("get_error_hr needs a preceding query_sr")
+        return native.forward_losses(pred_hr=self._stacked(self.intermediate_preds_list_hr), lab_hr=self._labels("hr"))[0][1]
+
+    def get_errorSR(self, image_SR, images_hr):
+        """SuRSNet.py:216-226: the L1 mean of image_SR - images_hr (nn.L1Loss)."""
+        self.images_HR = images_hr
+        dev = self._device()
+        if tuple(image_SR.shape) != tuple(images_hr.shape):
+            raise ValueError("get_errorSR: image_SR %s against images_hr %s" % (tuple(image_SR.shape), tuple(images_hr.shape)))
+        return native.forward_losses(img_sr=image_SR.to(dev, torch.float32), img_hr=images_hr.to(dev, torch.float32))[0][2]
+
+    def get_error_disp_1(self):
+        """SuRSNet.py:228-236: MSE(labels_hr - labels_lr, preds_hr - preds_lr), the last stack's predictions."""
+        if not self.intermediate_preds_list_lr or not self.intermediate_preds_list_hr:
+            raise RuntimeError("get_error_disp_1 needs a preceding query_mr and query_sr")
+        return native.forward_losses(pred_lr=self._stacked(self.intermediate_preds_list_lr[-1:]), lab_lr=self._labels("lr"),
+                                     pred_hr=self._stacked(self.intermediate_preds_list_hr[-1:]), lab_hr=self._labels("hr"))[0][3]
+
+    def loss_terms(self, image_SR, images_hr):
+        """(terms, total): the four terms above as one [4] float32 device tensor - get_error_lr, get_error_hr, get_errorSR,
+        get_error_disp_1 - and their sum weighted with opt.mlp1, opt.mlp2, opt.srweight, opt.dispweight (SuRSNet.py:265), from ONE
+        deterministic reduction (surs_forward_losses) and without a host synchronisation."""
+        dev = self._device()
+        if not self.intermediate_preds_list_lr or len(self.intermediate_preds_list_lr) != len(self.intermediate_preds_list_hr):
+            raise RuntimeError("loss_terms needs a preceding query_mr and query_sr on the same feature maps")
+        if tuple(image_SR.shape) != tuple(images_hr.shape):
+            raise ValueError("get_errorSR: image_SR %s against images_hr %s" % (tuple(image_SR.shape), tuple(images_hr.shape)))
+        self.images_HR = images_hr
+        w = (self.opt.mlp1, self.opt.mlp2, self.opt.srweight, self.opt.dispweight)
+        return native.forward_losses(pred_lr=self._stacked(self.intermediate_preds_list_lr), lab_lr=self._labels("lr"),
+                                     pred_hr=self._stacked(self.intermediate_preds_list_hr), lab_hr=self._labels("hr"),
+                                     img_sr=image_SR.to(dev, torch.float32), img_hr=images_hr.to(dev, torch.float32), weights=w)
+
+    def forward(self, images_lr, images_hr, points_lr, points_hr, calibs, transforms=None, labels_lr=None, labels_hr=None):
+        """The reference's forward (SuRSNet.py:240-266) as a VALIDATION forward: (res_hr, error, res_lr) computed on the device
+        without an autograd graph - error is a 0-dim float32 device tensor with no grad_fn; error.backward() fails with torch's own
+        message.  super_res -> filter_lr -> filter_hr -> query_mr(points_hr, labels=labels_hr) -> query_sr(points_lr,
+        labels=labels_lr) - the reference's own crossing of the two label arguments, kept -, then opt.mlp1 get_error_lr() + opt.mlp2
+        get_error_hr() + opt.srweight get_errorSR(img_SR, images_hr) + opt.dispweight get_error_disp_1().  In training mode every
+        kept stack is evaluated (intermediate_preds_list_lr / _hr: one [B,1,N] entry per stack), in eval mode the last one.
+        --norm batch normalises with the running statistics in EITHER mode, as every other call of this package does: train() keeps
+        the stacks, it never switches to batch statistics and updates nothing.  num_views == 1 and orthogonal projection only.
+        images_lr [B,3,H,W], images_hr [B,3,sH,sW], points_* [B,3,N], calibs [B,4,4], labels_* [B,1,N]."""
+        if self.num_views != 1 or self.projection_mode != "orthogonal":
+            raise NotImplementedError(self._STACKS_LIMIT)
+        if labels_lr is None or labels_hr is None:
+            raise ValueError("forward needs labels_lr and labels_hr (the loss terms are taken against them)")
+        img_SR, feature_lr, feature_hr = self.super_res(images_lr)
+        self.filter_lr(feature_lr)
+        self.filter_hr(feature_hr)
+        # query_sr runs on other points than query_mr: nothing reads the hr classifier on points_hr - an lr-only pass, then an hr-only one
+        self._query_mr(points_hr, calibs, transforms, labels_hr, lr_only=True)
+        self.query_sr(points_lr, calibs, transforms=transforms, labels=labels_lr)
+        res_hr, res_lr = self.get_preds()
+        self.loss_values, error = self.loss_terms(img_SR, images_hr)
+        return res_hr, error, res_lr

@@ -543,6 +543,49 @@ def query_points_generic(points, calib, zmul, zdiv, feat_lr, feat_hr, g, p_lr=No
     return (phr, plr, lg[0], lg[1]) if want_logits else (phr, plr)
 
 
+def _stack_table(feats_lr, feat_hr):
+    """The host table of the S lr map pointers (one geometry for all maps) of the stacks entries."""
+    f0 = feats_lr[0]
+    for f in feats_lr:
+        if (f.h, f.w, f.c) != (f0.h, f0.w, f0.c) or f.ld != f.c:
+            raise ValueError("the feature maps of the stacks must share one size and have ld == c")
+    assert feat_hr.ld == feat_hr.c
+    return (C.c_void_p * len(feats_lr))(*[f.ptr().value for f in feats_lr])
+
+
+def _stack_outputs(points, S, p_lr, lr_only):
+    """(points, n, p_lr [S,n] or None, pred_hr [S,n] or None, pred_lr [S,n]) of a stacks call in one of its three forms."""
+    if p_lr is not None and lr_only:
+        raise ValueError("p_lr (hr only) and lr_only exclude each other")
+    points = _f32c(points)
+    n, dev = points.shape[1], points.device
+    phr = None if lr_only else torch.empty((S, n), dtype=torch.float32, device=dev)
+    if p_lr is not None:
+        p_lr = _f32c(p_lr.reshape(S, -1))
+        assert p_lr.shape[1] == n
+        plr = p_lr
+    else:
+        plr = torch.empty((S, n), dtype=torch.float32, device=dev)
+    return points, n, p_lr, phr, plr
+
+
+def query_points_generic_stacks(points, calib, zmul, zdiv, feats_lr, feat_hr, g, p_lr=None, lr_only=False):
+    """surs_query_points_generic_stacks: GenericMlp g on points [3,N] for every lr map of feats_lr (a list of S Img; one hr map) in
+    one launch.  Returns (pred_hr [S,N], pred_lr [S,N]), row s = query_points_generic on map s, bit for bit.  p_lr [S,N]: the hr
+    classifier alone (pred_lr is p_lr); lr_only: the lr classifier alone (pred_hr is None)."""
+    S = len(feats_lr)
+    points, n, p_lr, phr, plr = _stack_outputs(points, S, p_lr, lr_only)
+    cal = (C.c_float * 12)(*[float(v) for v in calib])
+    for f in feats_lr:
+        _check_feat_channels(f.c, feat_hr.c, g)
+    tab = _stack_table(feats_lr, feat_hr)
+    f0 = feats_lr[0]
+    check(lib().surs_query_points_generic_stacks(_ptr(points), n, cal, float(zmul), float(zdiv), S, tab, f0.h, f0.w, feat_hr.ptr(),
+                                                 feat_hr.h, feat_hr.w, C.byref(g.lr), C.byref(g.hr), _ptr(g.blob), _ptr(p_lr), _ptr(phr),
+                                                 None if p_lr is not None else _ptr(plr), None, None, _stream()))
+    return phr, plr
+
+
 def query_grid_generic(i0, i1, ry, rz, mat, calib, zmul, zdiv, feat_lr, feat_hr, g, vol_hr=None, vol_lr=None):
     """surs_query_grid_generic: the dense sweep of grid slab [i0, i1) with the fused evaluator.  Returns (vol_hr, vol_lr) float32
     device tensors [(i1-i0), ry, rz]."""
@@ -839,6 +882,59 @@ def query_points_hr(points, calib, zmul, zdiv, feat_lr, feat_hr, blob, ws, p_lr)
                                      feat_hr.ptr(), feat_hr.h, feat_hr.w, _ptr(blob), _ptr(w), w.numel(), _ptr(p_lr), _ptr(out), None,
                                      _stream()))
     return out
+
+
+def query_points_stacks(points, calib, zmul, zdiv, feats_lr, feat_hr, blob, ws, p_lr=None, lr_only=False):
+    """surs_query_points_stacks: the released shape's layer kernels on points [3,N] once per lr map of feats_lr (a list of S Img), in
+    one call on one workspace.  Returns (pred_hr [S,N], pred_lr [S,N]), row s = query_points (p_lr [S,N] given: query_points_hr) on
+    map s, bit for bit; lr_only: the lr classifier alone (pred_hr is None)."""
+    S = len(feats_lr)
+    points, n, p_lr, phr, plr = _stack_outputs(points, S, p_lr, lr_only)
+    cal = (C.c_float * 12)(*[float(v) for v in calib])
+    tab = _stack_table(feats_lr, feat_hr)
+    f0 = feats_lr[0]
+    assert f0.c == 256 and feat_hr.c == 64
+    w = ws.get(lib().surs_query_workspace_bytes(n))
+    check(lib().surs_query_points_stacks(_ptr(points), n, cal, float(zmul), float(zdiv), S, tab, f0.h, f0.w, feat_hr.ptr(), feat_hr.h,
+                                         feat_hr.w, _ptr(blob), _ptr(w), w.numel(), _ptr(p_lr), _ptr(phr),
+                                         None if p_lr is not None else _ptr(plr), None, None, _stream()))
+    return phr, plr
+
+
+def forward_losses(pred_lr=None, lab_lr=None, pred_hr=None, lab_hr=None, img_sr=None, img_hr=None, weights=None):
+    """surs_forward_losses: the terms of SuRSNet.forward's loss in one deterministic reduction, without a host synchronisation.
+    pred_lr / pred_hr [S,M] float32 device tensors, lab_lr / lab_hr [M] (the labels each is held against), img_sr / img_hr: equal
+    element counts in one element order; a group left None gives a zero term.  Returns (terms [4] float32 device tensor:
+    get_error_lr, get_error_hr, get_errorSR, get_error_disp_1; total: 0-dim float32 device tensor of weights (4 host floats) times
+    the terms, None without weights)."""
+    ref = next(t for t in (pred_lr, pred_hr, img_sr) if t is not None)
+    dev = ref.device
+    S, M = 1, 0
+    for p, l in ((pred_lr, lab_lr), (pred_hr, lab_hr)):
+        if (p is None) != (l is None):
+            raise ValueError("predictions and their labels come together")
+    if pred_lr is not None or pred_hr is not None:
+        shp = [tuple(p.shape) for p in (pred_lr, pred_hr) if p is not None]
+        if len(shp[0]) != 2 or any(q != shp[0] for q in shp):
+            raise ValueError("predictions must be [S,M] and agree: %s" % (shp,))
+        S, M = shp[0]
+        pred_lr, pred_hr = (None if p is None else _f32c(p) for p in (pred_lr, pred_hr))
+        lab_lr, lab_hr = (None if l is None else _f32c(l.to(dev).reshape(-1)) for l in (lab_lr, lab_hr))
+        if any(l is not None and l.numel() != M for l in (lab_lr, lab_hr)):
+            raise ValueError("labels must hold one value per point: %d" % M)
+    K = 0
+    if img_sr is not None:
+        if img_hr is None or img_hr.numel() != img_sr.numel():
+            raise ValueError("get_errorSR: image_SR %s against images_hr %s" % (tuple(img_sr.shape), None if img_hr is None else tuple(img_hr.shape)))
+        img_sr, img_hr = _f32c(img_sr.reshape(-1)), _f32c(img_hr.reshape(-1))
+        K = img_sr.numel()
+    ws = torch.empty(lib().surs_forward_losses_workspace_bytes() // 8, dtype=torch.float64, device=dev)
+    terms = torch.empty(4, dtype=torch.float32, device=dev)
+    total = torch.empty((), dtype=torch.float32, device=dev) if weights is not None else None
+    wt = (C.c_float * 4)(*[float(v) for v in weights]) if weights is not None else None
+    check(lib().surs_forward_losses(_ptr(pred_lr), _ptr(pred_hr), int(S), int(M), _ptr(lab_lr), _ptr(lab_hr), _ptr(img_sr), _ptr(img_hr),
+                                    int(K), wt, _ptr(ws), ws.numel() * 8, _ptr(terms), _ptr(total), _stream()))
+    return terms, total
 
 
 def query_points_views(points, calibs, projection, zmul, zdiv, feat_lr, feat_hr, blob, ws, want_logits=False):

@@ -3,7 +3,8 @@
 Same flag names and defaults as the reference's argparse set
 (/root/reference/lib/options.py:5-214) so that a reference command line such as
 README.md:41-44 parses unchanged.  Flags that only the reference's training or
-dataset-rendering code reads are accepted and ignored (listed in `_IGNORED`).
+dataset-rendering code reads are accepted and ignored (listed in `_IGNORED`);
+the four loss weights are read by the validation forward (`_LOSS_WEIGHTS`).
 Table-driven instead of one add_argument call per line.
 """
 import argparse
@@ -55,7 +56,6 @@ _IGNORED = [
     ("num_sample_color", int, 0), ("norm_color", str, "instance"), ("num_hourglass", int, 2),
     ("hg_down", str, "ave_pool"), ("hourglass_dim", int, 256), ("mlp_norm", str, "group"),
     ("scale_pifu", float, 0.01), ("gamma", float, 0.1), ("color_loss_type", str, "l1"), ("losses", str, "l1"),
-    ("mlp1", float, 1.0), ("mlp2", float, 1.0), ("srweight", float, 1.0), ("dispweight", float, 1.0),
     ("disp_error", int, 1), ("n_train", int, 300), ("n_val", int, 60), ("optimizer", str, "ADAM"),
     ("momentum", float, 0.9), ("beta1", float, 0.9), ("beta2", float, 0.999), ("epsilon", float, 1e-8),
     ("ams", float, False), ("weight_decay", float, 0), ("num_gen_mesh_test", int, 1), ("n_colors", int, 3),
@@ -64,6 +64,8 @@ _IGNORED = [
     ("aug_alstd", float, 0.0), ("aug_bri", float, 0.0), ("aug_con", float, 0.0), ("aug_sat", float, 0.0),
     ("aug_hue", float, 0.0), ("aug_blur", float, 0.0),
 ]
+# the weights of SuRSNet.forward's four loss terms (lib/model/SuRSNet.py:265): get_error_lr, get_error_hr, get_errorSR, get_error_disp_1
+_LOSS_WEIGHTS = [("mlp1", float, 1.0), ("mlp2", float, 1.0), ("srweight", float, 1.0), ("dispweight", float, 1.0)]
 # extensions of this package (not in the reference)
 _NATIVE = [
     ("precision", str, "fp32"),      # fp32 | bf16 | fp16 : arithmetic of the MLP contractions
@@ -88,7 +90,7 @@ class BaseOptions:
         self.initialized = False
 
     def initialize(self, parser):
-        for name, typ, default in _PATH_FLAGS + _IGNORED:
+        for name, typ, default in _PATH_FLAGS + _IGNORED + _LOSS_WEIGHTS:
             parser.add_argument("--" + name, type=typ, default=default)
         for name, typ, default in _LIST_FLAGS:
             parser.add_argument("--" + name, type=typ, nargs="+", default=list(default))
