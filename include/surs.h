@@ -597,7 +597,10 @@ size_t surs_mc_workspace_bytes(int n0, int n1, int n2);
  * (axis0, axis1, axis2) order), same vertex numbering, same faces (int32, rows reversed for
  * gradient_direction='descent'), normals and values.  Outputs are device buffers of capacity cap_verts /
  * cap_faces; counts is a HOST struct filled before return (this call synchronises the stream).
- * normals / values nullable.  verts == NULL or faces == NULL: count-only call (fills counts, writes nothing). */
+ * normals / values nullable.  verts == NULL or faces == NULL: count-only call (fills counts, writes nothing).
+ * SURS_E_CAPACITY: counts holds the sizes needed; the rows of verts / faces below the capacities are those of the whole
+ * mesh, nothing is written behind them (normals / values are not final).  Like the success path it returns with the
+ * stream synchronised: nothing of the call is still in flight, the buffers and the workspace may be released or reused. */
 int surs_mc_lewiner(const float *vol, int n0, int n1, int n2, double level, void *workspace, size_t workspace_bytes,
                     float *verts, float *normals, float *values, int cap_verts, int32_t *faces, int cap_faces,
                     surs_mc_counts *counts, void *stream);
@@ -609,8 +612,10 @@ int surs_mc_lewiner(const float *vol, int n0, int n1, int n2, double level, void
  * at n0 - 1, the outputs are identical to one surs_mc_lewiner call: Lewiner's sweep has axis 0 outermost, so vertex and
  * face numbering of a layer depend only on the layers before it.  Normals / values of a vertex keep accumulating from
  * later layers: read them after the last range and surs_mc_normalize.  The level-range / no-surface checks are the
- * caller's, from run->vmin / vmax / n_verts after the last range.  Synchronises the stream once per call.
- * SURS_E_CAPACITY leaves run advanced to the sizes needed so far. */
+ * caller's, from run->vmin / vmax / n_verts after the last range (after every range they are those of the planes
+ * 0 .. layer_end read so far).  Synchronises the stream once per call.
+ * SURS_E_CAPACITY leaves run advanced to the sizes needed so far (rows below the capacities are valid and the stream is
+ * synchronised, as above). */
 int surs_mc_lewiner_range(const float *vol, int n0, int n1, int n2, int layer_begin, int layer_end, double level,
                           void *workspace, size_t workspace_bytes, float *verts, float *normals, float *values, int cap_verts,
                           int32_t *faces, int cap_faces, surs_mc_counts *run, void *stream);

@@ -57,6 +57,7 @@ struct Dims {
     long long cell_begin, cell_end;   // the flat (sweep-order) cell range this call processes (whole layers)
     int prow;                         // padded row length of the classification passes: cx rounded up to a multiple of 4
     long long q_begin, q_end;         // the same range as padded indices q = (z * cy + y) * prow + x
+    int ztop;                         // the range's last cell layer: its upper plane is the last plane the range reads
     int base_verts, base_faces;      // vertices / triangles produced by earlier ranges
     int zoff;                        // slab mode: index of the volume's plane 0 in the whole grid (0 = the grid's bottom)
     int ring;                        // planes of the edge -> vertex-id tables: plane z lives in slot z % ring (mc_ring)
@@ -523,7 +524,8 @@ __device__ __forceinline__ int mc_scan_block(const float *__restrict__ vol, cons
             for (int k = 0; k < 4; ++k) e[k] = plast[(k & 1) * sy + (k >> 1) * sz + 4];
         }
         // min / max / NaN: every voxel is in row 0 of some quad, except the last plane of axis 1 (row 1 at the last cell row) and
-        // of axis 0 (rows 2, 3 in the last cell layer of the volume).  An unordered compare of two values is true if either is a NaN.
+        // of axis 0 (rows 2, 3 in the last cell layer of the RANGE: a range reports every plane it reads, its top plane included - the
+        // next range sees that plane again as its row 0).  An unordered compare of two values is true if either is a NaN.
         unsigned long long nanm = 0ull;
 #pragma unroll
         for (int h = 0; h < NQ; ++h) {
@@ -533,7 +535,7 @@ __device__ __forceinline__ int mc_scan_block(const float *__restrict__ vol, cons
             }
             nanm |= (__ballot(__builtin_isunordered(v[h][0][0], v[h][0][1])) | __ballot(__builtin_isunordered(v[h][0][2], v[h][0][3]))) &
                     __ballot(valid[h]);
-            const bool ylast = valid[h] && y[h] == d.cy - 1, zlast = valid[h] && z[h] == d.cz - 1;
+            const bool ylast = valid[h] && y[h] == d.cy - 1, zlast = valid[h] && z[h] == d.ztop;
             if (__ballot(ylast || zlast) != 0ull) {
 #pragma unroll
                 for (int k = 1; k < 4; ++k) {
@@ -615,8 +617,8 @@ __device__ __forceinline__ int mc_scan_block(const float *__restrict__ vol, cons
 #pragma unroll
                 for (int j = 0; j < 5; ++j) r[k][j] = p[(k & 1) * sy + (k >> 1) * sz + min(j, ncell)];
             // min / max: every voxel is covered by row 0 of some quad, except the last plane of axis 1 (row 1 when y is the
-            // last cell row) and of axis 0 (rows 2, 3 when z is the last cell layer of the volume)
-            const bool ylast = y == d.cy - 1, zlast = z == d.cz - 1;
+            // last cell row) and of axis 0 (rows 2, 3 when z is the last cell layer of the range)
+            const bool ylast = y == d.cy - 1, zlast = z == d.ztop;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const bool use = k == 0 || (k == 1 && ylast) || (k == 2 && zlast) || (k == 3 && ylast && zlast);
@@ -1353,6 +1355,7 @@ static int mc_range(const float *vol, int n0, int n1, int n2, long long cell_beg
     SURS_REQUIRE(cell_end - cell_begin <= list_cells, "range of more than ring - 1 cell layers (mc_chunked splits them)");
     d.q_begin = cell_begin / d.cx * d.prow;
     d.q_end = cell_end / d.cx * d.prow;
+    d.ztop = (int)(cell_end / per_layer) - 1;
     {
         auto magic = [](unsigned dv, unsigned &m, unsigned &sh) {   // dv >= 2
             unsigned L = 0;
@@ -1426,9 +1429,14 @@ static int mc_range(const float *vol, int n0, int n1, int n2, long long cell_beg
     const int nactive = host.tot[2];
     run->n_verts = d.base_verts + host.tot[0];
     run->n_faces = d.base_faces + host.tot[1];
-    if (count_only || nactive == 0) return 0;
-    if (run->n_verts > cap_verts || run->n_faces > cap_faces)
+    if (count_only) return 0;
+    // A range that does not fit is still emitted where some of its rows do (the kernels below write rows < cap_verts / cap_faces only,
+    // the vertex-id tables in any case): the rows below the capacities are then the mesh's, whichever chunk ran over.  Where nothing
+    // of it fits - a sizing call with capacities of 0, the chunks behind the last row - it is only counted.
+    const bool fits = run->n_verts <= cap_verts && run->n_faces <= cap_faces;
+    if (!fits && (nactive == 0 || (d.base_verts >= cap_verts && d.base_faces >= cap_faces)))
         return fail(SURS_E_CAPACITY, "output capacity too small: need %d vertices, %d faces", run->n_verts, run->n_faces);
+    if (nactive == 0) return 0;
     const int emit_reclassify = option(OPT_MC_EMIT_RECLASSIFY);   // tests
     if (2ll * nactive > list_cells || emit_reclassify)   // the sorted list would run into the count pass's codes: classify again
         hipLaunchKernelGGL(mc_emit_kernel, dim3(nb < 16384 ? nb : 16384), dim3(SCAN_THREADS), 0, st, vol, d, level, levelf, nb, bcounts, boffs,
@@ -1447,11 +1455,18 @@ static int mc_range(const float *vol, int n0, int n1, int n2, long long cell_beg
         hipLaunchKernelGGL(mc_face_kernel, dim3(ab), dim3(THREADS), 0, st, vol, d, level, alist, nactive, evid, faces, normals, values,
                            cap_verts, cap_faces);
     SURS_LAUNCH_CHECK();
+    if (!fits) {
+        // (the error path only: every SURS_E_CAPACITY return leaves the stream idle, as when the range was not emitted at all - the
+        //  caller may free its buffers or hand the workspace to another stream straight away)
+        SURS_HIP_CHECK(hipStreamSynchronize(st));
+        return fail(SURS_E_CAPACITY, "output capacity too small: need %d vertices, %d faces", run->n_verts, run->n_faces);
+    }
     return 0;
 }
 
 // [cell_begin, cell_end) in chunks of at most ring - 1 layers (the vertex-id ring holds ring planes).  A chunk that does not fit the
-// output buffers turns the rest of the walk into a counting walk: run ends at the sizes the whole range needs, SURS_E_CAPACITY.
+// output buffers is written up to their capacities, as are the chunks behind it as long as rows of theirs fit (mc_range); the rest of
+// the walk only counts: run ends at the sizes the whole range needs, SURS_E_CAPACITY.
 static int mc_chunked(const float *vol, int n0, int n1, int n2, long long cell_begin, long long cell_end, double level,
                       void *workspace, size_t workspace_bytes, float *verts, float *normals, float *values, int cap_verts,
                       int32_t *faces, int cap_faces, bool count_only, surs_mc_counts *run, hipStream_t st, int zoff = 0) {
@@ -1461,7 +1476,7 @@ static int mc_chunked(const float *vol, int n0, int n1, int n2, long long cell_b
     for (long long a = cell_begin; a < cell_end; a += step) {
         const long long b = a + step < cell_end ? a + step : cell_end;
         const int rc = mc_range(vol, n0, n1, n2, a, b, level, workspace, workspace_bytes, verts, normals, values, cap_verts, faces, cap_faces,
-                                count_only || overflow, run, st, zoff);
+                                count_only, run, st, zoff);
         if (rc == SURS_E_CAPACITY) overflow = true;
         else if (rc) return rc;
     }

@@ -67,53 +67,21 @@ def test_gather_slabs_world3_ragged():
 # The per-slab extraction is a GPU kernel; here every rank's slab result is DERIVED from the oracle's mesh of the whole
 # volume exactly as surs_mc_lewiner_range_slab defines it (a slab owns the vertices / faces its cell layers create, numbers
 # them from 0 and refers to the slab below as -(2 + slot)), and the protocol - counts all_gather, boundary-id exchange,
-# renumbering, mesh gather - must give the whole mesh back.  tests/test_gpu_dist.py runs the real kernels.
+# renumbering, mesh gather - must give the whole mesh back.  The derivation is tests/mc_slabs.py (checked on its own by
+# tests/test_mc_slabs_host.py); tests/test_gpu_mc_ranges.py and tests/test_gpu_dist.py run the real kernels.
 
 def _slab_fixture(R=20, world=3):
+    import mc_slabs
     import mc_volumes
-    import oracle
     # a smooth blob that reaches into every slab, plus a little seeded noise (centre vertices, ambiguous cells)
     z, y, x = np.mgrid[:R, :R, :R].astype(np.float64)
     c = (R - 1) / 2.0
     vol = 1.0 / (1.0 + np.exp(((x - c) ** 2 / 30.0 + (y - c - 0.7) ** 2 / 50.0 + (z - c + 0.3) ** 2 / 70.0) - 1.0))
     vol = (vol + 0.08 * (mc_volumes.noise((R, R, R), 5) - 0.5)).astype(np.float32)
-    V, F, _, _ = oracle.marching_cubes_lewiner(vol.astype(np.float64), 0.5)
-
-    def prefix(i1):   # (vertices, faces) created by the cell layers [0, i1)
-        if i1 < 1:
-            return 0, 0
-        try:
-            v, f, _, _ = oracle.marching_cubes_lewiner(vol[:i1 + 1].astype(np.float64), 0.5)
-        except (ValueError, RuntimeError):
-            return 0, 0
-        assert np.array_equal(v, V[:len(v)]) and np.array_equal(f, F[:len(f)])   # a prefix of the whole mesh
-        return len(v), len(f)
-
-    slabs = []
-    for r in range(world):
-        i0, i1 = sdist.slab_range(R, r, world)
-        top = i1 if r < world - 1 else R - 1
-        (v0, f0), (v1, f1) = prefix(i0), prefix(top)
-        faces = F[f0:f1].astype(np.int64).copy()
-        ref = faces < v0
-        pos = V[faces[ref]]                       # vertices of the slab below: on plane i0, on an x- or a y-edge
-        assert np.all(pos[:, 0] == i0)
-        on_x = pos[:, 2] != np.floor(pos[:, 2])
-        slot = np.where(on_x, np.floor(pos[:, 1]) * R + np.floor(pos[:, 2]), R * R + np.floor(pos[:, 1]) * R + np.floor(pos[:, 2]))
-        assert np.all(on_x ^ (pos[:, 1] != np.floor(pos[:, 1])))
-        faces[ref] = -(2 + slot.astype(np.int64))
-        faces[~ref] -= v0
-        ids = np.full((2, R, R), -7, np.int32)    # entries of edges the surface does not cross are undefined
-        own = V[v0:v1]
-        for k in np.nonzero(own[:, 0] == i1)[0]:
-            p = own[k]
-            if p[2] != np.floor(p[2]):
-                ids[0, int(p[1]), int(np.floor(p[2]))] = k
-            elif p[1] != np.floor(p[1]):
-                ids[1, int(np.floor(p[1])), int(p[2])] = k
-        mm = vol[i0:top + 1]
-        slabs.append(dict(verts=own.astype(np.float64), faces=faces.astype(np.int32), ids=ids,
-                          counts=(v1 - v0, f1 - f0, float(mm.min()), float(mm.max()))))
+    V, F, _, _ = mc_slabs.mesh(vol, 0.5)
+    # every rank's slab as surs_mc_lewiner_range_slab defines it (tests/mc_slabs.py; the prefix property is asserted there)
+    bounds = [sdist.slab_range(R, r, world)[0] for r in range(world)] + [R - 1]
+    slabs = [dict(s, verts=s["verts"].astype(np.float64)) for s in mc_slabs.slabs(vol, 0.5, bounds)]
     return V, F, slabs
 
 
