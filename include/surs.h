@@ -422,6 +422,37 @@ int surs_forward_losses(const float *pred_lr, const float *pred_hr, int num_stac
                         const float *lab_hr, const float *img_sr, const float *img_hr, long long k, const float *weights,
                         void *workspace, size_t workspace_bytes, float *terms, float *total, void *stream);
 
+/* ------------------------------------------------------------------ classifier gradients
+ * d error / d (every conv{l}.weight and conv{l}.bias of mlp_lr and mlp_hr) of SuRSNet.forward's loss (lib/model/SuRSNet.py:131-187,
+ * 196-266, lib/model/SurfaceClassifier.py:45-81), the encoder frozen; single view, orthogonal projection; csrc/surs_mlp_grad.hip.
+ * With stacks s < S, q_s = in_img_mr sigmoid(mlp_lr(x_s(points_mr))) and r_s = in_img_sr sigmoid(mlp_hr([x_s(points_sr) | q_s])), q_s
+ * taken index by index:
+ *   error = w[0] mean_s MSE(q_s, lab_lr) + w[1] mean_s MSE(r_s, lab_hr) + w[2] MSE(lab_hr - lab_lr, r_{S-1} - q_{S-1})  (+ the
+ *   super-resolution term, which does not depend on these parameters), every mean over m_total values.
+ * mlp_lr's gradient has three sources: its own term, the displacement term and mlp_hr's last input channel.  LeakyReLU slope 0.01,
+ * its derivative at exactly 0 the negative side's; a point outside the image contributes exactly zero.  fp32 operands on the
+ * f32-input MFMA with fp32 accumulation whatever the operand split of the query entries; no float atomics and a fixed order of every
+ * sum: two runs give the same bits.  Points go in chunks of 2048, so the workspace depends on the shapes only. */
+
+/* Bytes of device workspace surs_mlp_grad needs for this pair, whatever n (0: unsupported pair, surs_last_error names the limit). */
+size_t surs_mlp_grad_workspace_bytes(const SursMlpShape *lr, const SursMlpShape *hr);
+
+/* The gradients of ONE image.  points_mr / points_sr [3][n] device (query_mr's and query_sr's points), calib_mr / calib_sr HOST [12]
+ * rows of [R|t], zmul / zdiv as surs_query_points; feat_lr: HOST array of S = num_stacks device maps [hl][wl][D], feat_hr [hh][wh][64];
+ * w_* / b_*: HOST arrays of n_layers device pointers to the plain fp32 Conv1d weights [out][in] and biases [out]; lab_lr / lab_hr [n]
+ * device: what q / r are held against (the labels as SuRSNet stores them); loss_weights HOST [3] = opt.mlp1, opt.mlp2,
+ * opt.dispweight; m_total = the number of points the batch's means run over (B n: one call per image with accumulate = 1 after the
+ * first gives the batch's gradient).  accumulate 0: the outputs are overwritten, 1: added to.  gw_* / gb_*: HOST arrays of device
+ * pointers, Conv1d layout [out][in] / [out] fp32.  pred_lr / pred_hr: nullable [S][n] device, q_s / r_s of the call's own forward.
+ * workspace: surs_mlp_grad_workspace_bytes(lr, hr) bytes, 256-byte aligned.  No synchronisation. */
+int surs_mlp_grad(const float *points_mr, const float *points_sr, int n, const float *calib_mr, const float *calib_sr, float zmul,
+                  float zdiv, int num_stacks, const float *const *feat_lr, int hl, int wl, const float *feat_hr, int hh, int wh,
+                  const SursMlpShape *lr, const SursMlpShape *hr, const float *const *w_lr, const float *const *b_lr,
+                  const float *const *w_hr, const float *const *b_hr, const float *lab_lr, const float *lab_hr,
+                  const float *loss_weights, long long m_total, int accumulate, float *const *gw_lr, float *const *gb_lr,
+                  float *const *gw_hr, float *const *gb_hr, float *pred_lr, float *pred_hr, void *workspace, size_t workspace_bytes,
+                  void *stream);
+
 /* Multi-view query of one subject (num_views = V in [1, 64], orthogonal projection) for classifiers of any supported shape, in ONE
  * launch per call (csrc/surs_mlp_fused_views.inc): lib/model/SurfaceClassifier.py:53-81 with num_views > 1 - layers 0 .. L/2 per
  * view on that view's features, then the view mean ((sum in view order) * (1/V)) of layer L/2's outputs and of the input features,

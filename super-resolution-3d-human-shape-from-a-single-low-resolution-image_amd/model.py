@@ -8,8 +8,11 @@ get_errorSR(), get_error_disp_1(), forward().
 
 It is NOT a torch.nn.Module: parameters are a flat ordered dict keyed exactly like the reference's state dict
 (all 553 keys, strict; 1036 with --norm batch), and every forward method sequences hand-written HIP kernels through the C ABI.  There is
-no backward pass and no optimiser (out of scope) and no CPU path: methods raise without a GPU / built library.  forward() is the
+no autograd graph and no optimiser and no CPU path: methods raise without a GPU / built library.  forward() is the
 VALIDATION forward: every kept stack's predictions and the reference's loss, without an autograd graph (SuRSNet.py:240-266).
+The one part of the backward pass that exists is the classifiers': forward_backward() / classifier_grads() return d error / d (every
+mlp_lr.* and mlp_hr.* parameter) with the encoder frozen (native.mlp_grads); the encoder's and the super-resolution network's
+gradients, and gradients with respect to the feature maps, are out of scope.
 
 Encoder options: --norm group | batch and --scale 1..4 (anything else: ValueError at construction).  --norm batch is nn.BatchNorm2d in
 EVAL mode - y = (x - running_mean) / sqrt(running_var + 1e-5) * weight + bias, always from the running statistics: train() here keeps
@@ -76,6 +79,10 @@ class SuRSNet:
         self.intermediate_preds_list_hr = []
         self._mr_points = None
         self._mr_hr = None
+        self._sr_points = None        # query_sr's points and (calibs, transforms): what classifier_grads() differentiates
+        self._sr_args = None
+        self._grad_params = None      # native.MlpParams: the device copy of the fp32 classifier weights (dropped like the blob)
+        self._grad_ws = None
         self._feat_cache = None
         self._stack_feat_cache = None
         self.labels_lr = self.labels_hr = None
@@ -94,6 +101,7 @@ class SuRSNet:
             if self._enc is not None:
                 encoder.drop_graphs(self._enc)
             self._enc = self._blob = None
+            self._grad_params = self._grad_ws = None
         return self
 
     def cuda(self, index=None):
@@ -136,6 +144,7 @@ class SuRSNet:
         if self._enc is not None:
             encoder.drop_graphs(self._enc)
         self._enc = self._blob = None
+        self._grad_params = None
         return self
 
     # ------------------------------------------------------------------ lazily packed device state
@@ -563,6 +572,7 @@ class SuRSNet:
             self.labels_hr = labels
         if self._mr_points is None:
             raise RuntimeError("query_sr needs the preceding query_mr (it consumes its lr predictions, SuRSNet.py:179)")
+        self._sr_points, self._sr_args = points, (calibs, transforms)
         # the same points as the preceding query_mr?  Decided without touching the data (a full-tensor compare is a device
         # synchronisation per call): the same tensor object, or the same storage / view / version
         ref, ver = self._mr_points, self._mr_version
@@ -674,3 +684,74 @@ class SuRSNet:
         res_hr, res_lr = self.get_preds()
         self.loss_values, error = self.loss_terms(img_SR, images_hr)
         return res_hr, error, res_lr
+
+    # ------------------------------------------------------------------ classifier gradients
+    _GRADS_LIMIT = ("classifier gradients (forward_backward(), classifier_grads()): num_views == 1 and orthogonal projection only")
+
+    def _mlp_params(self):
+        if self._grad_params is None:
+            sd = {k: v for k, v in self._sd.items() if k.startswith("mlp_")}
+            shapes = native.mlp_shapes({k: v.numpy() for k, v in sd.items()}, self.opt)
+            self._grad_params = native.MlpParams(sd, self._device(), shapes)
+        return self._grad_params
+
+    def classifier_grads(self):
+        """d error / d (every mlp_lr.* and mlp_hr.* parameter) of forward()'s loss - opt.mlp1 get_error_lr() + opt.mlp2 get_error_hr()
+        + opt.dispweight get_error_disp_1(); the super-resolution term does not depend on these parameters - from what the preceding
+        query_mr(labels=...) + query_sr(labels=...) left on this object: their points, calibrations, transforms and labels, the
+        feature maps of im_feat_list_lr (every kept stack in training mode, the last one in eval mode) and im_feat_list_hr[0].
+        Returns an OrderedDict in state_dict() key order holding every mlp_* key: float32 device tensors of the parameters' shapes
+        ([out,in,1] weights), summed over stacks and over the images of the batch.  The encoder is frozen: mlp_lr's gradient
+        has its three sources (its own term, the displacement term, mlp_hr's last input channel), but there are no gradients for the
+        encoder / super-resolution parameters and none with respect to the feature maps (out of scope).  fp32-grade whatever
+        --precision says, deterministic (two calls give the same bits).  num_views == 1 and orthogonal projection only."""
+        if self.num_views != 1 or self.projection_mode != "orthogonal":
+            raise NotImplementedError(self._GRADS_LIMIT)
+        if self._mr_points is None:
+            raise RuntimeError("classifier_grads needs a preceding query_mr(labels=...): its points are not known")
+        if self._sr_points is None:
+            raise RuntimeError("classifier_grads needs a preceding query_sr(labels=...): its points are not known")
+        if self.labels_lr is None:
+            raise RuntimeError("classifier_grads: labels_lr is not set: pass labels= to query_mr (SuRSNet.py:134-136)")
+        if self.labels_hr is None:
+            raise RuntimeError("classifier_grads: labels_hr is not set: pass labels= to query_sr (SuRSNet.py:164-165)")
+        dev = self._device()
+        pm, ps = self._mr_points, self._sr_points
+        if tuple(pm.shape) != tuple(ps.shape):
+            raise ValueError("classifier_grads: query_mr's points %s against query_sr's %s (SuRSNet.py:179 pairs them index by index)"
+                             % (tuple(pm.shape), tuple(ps.shape)))
+        B, N = pm.shape[0], pm.shape[2]
+        lab = [l.to(dev, torch.float32).reshape(B, -1) for l in (self.labels_lr, self.labels_hr)]
+        if any(l.shape[1] != N for l in lab):
+            raise ValueError("classifier_grads: labels %s / %s against %d points per image"
+                             % (tuple(self.labels_lr.shape), tuple(self.labels_hr.shape), N))
+        if not self.im_feat_list_lr or not self.im_feat_list_hr:
+            raise RuntimeError("filter_lr / filter_hr must run before a query")
+        cal_mr, cal_sr = self._calib_rows(*self._mr_args), self._calib_rows(*self._sr_args)
+        if cal_mr.shape[0] != B or cal_sr.shape[0] != B:
+            raise ValueError("points [%d,3,N] and calibs [%d,4,4] / [%d,4,4] disagree" % (B, cal_mr.shape[0], cal_sr.shape[0]))
+        zmul, zdiv = self._zscale()
+        params = self._mlp_params()
+        if self._grad_ws is None or self._grad_ws[0] != params.shapes:
+            need = native.mlp_grad_workspace_bytes(params.shapes)
+            self._grad_ws = (params.shapes, torch.empty(need // 4, dtype=torch.float32, device=dev))
+        w = (self.opt.mlp1, self.opt.mlp2, self.opt.dispweight)
+        grads = None
+        for b in range(B):
+            feats, fh = self.stack_features(b)
+            grads = native.mlp_grads(pm[b].to(dev, torch.float32).contiguous(), ps[b].to(dev, torch.float32).contiguous(), cal_mr[b],
+                                     cal_sr[b], zmul, zdiv, feats, fh, params, lab[0][b], lab[1][b], w, B * N, grads=grads,
+                                     accumulate=b > 0, workspace=self._grad_ws[1])
+        return grads
+
+    def forward_backward(self, images_lr, images_hr, points_lr, points_hr, calibs, transforms=None, labels_lr=None, labels_hr=None):
+        """forward() and the classifiers' gradients of its loss: (res_hr, error, res_lr, grads).  The first three are exactly forward()'s
+        (it is called; error still has no autograd graph), grads is classifier_grads()'s OrderedDict: every mlp_lr.* / mlp_hr.* key in
+        state_dict() order, float32 device tensors of the parameters' shapes.  Out of scope: gradients for the encoder /
+        super-resolution parameters and gradients with respect to the feature maps (the encoder is frozen); num_views == 1 and
+        orthogonal projection only."""
+        if self.num_views != 1 or self.projection_mode != "orthogonal":
+            raise NotImplementedError(self._GRADS_LIMIT)
+        res_hr, error, res_lr = self.forward(images_lr, images_hr, points_lr, points_hr, calibs, transforms=transforms,
+                                             labels_lr=labels_lr, labels_hr=labels_hr)
+        return res_hr, error, res_lr, self.classifier_grads()

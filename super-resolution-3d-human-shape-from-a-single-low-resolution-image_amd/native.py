@@ -6,6 +6,7 @@ device.  Nothing here computes on the CPU and nothing falls back.
 """
 import ctypes as C
 import os
+from collections import OrderedDict
 
 import numpy as np
 import torch
@@ -935,6 +936,106 @@ def forward_losses(pred_lr=None, lab_lr=None, pred_hr=None, lab_hr=None, img_sr=
     check(lib().surs_forward_losses(_ptr(pred_lr), _ptr(pred_hr), int(S), int(M), _ptr(lab_lr), _ptr(lab_hr), _ptr(img_sr), _ptr(img_hr),
                                     int(K), wt, _ptr(ws), ws.numel() * 8, _ptr(terms), _ptr(total), _stream()))
     return terms, total
+
+
+# ------------------------------------------------------------------ classifier gradients
+
+def mlp_param_keys(shapes):
+    """The state-dict keys of both classifiers in state_dict() order: mlp_lr.conv0.weight, mlp_lr.conv0.bias, ..., mlp_hr...."""
+    return [p + "conv%d.%s" % (l, kind) for m, p in enumerate(("mlp_lr.", "mlp_hr.")) for l in range(len(shapes[m][0]) - 1)
+            for kind in ("weight", "bias")]
+
+
+class MlpParams:
+    """The plain fp32 Conv1d weights [out,in] and biases [out] of a classifier pair on the device: what surs_mlp_grad reads."""
+
+    def __init__(self, sd, device, shapes=None):
+        self.shapes = mlp_shapes(sd) if shapes is None else shapes
+        self.lr, self.hr = (_shape_struct(*s) for s in self.shapes)
+        self.tensors = OrderedDict()
+        for k in mlp_param_keys(self.shapes):
+            v = sd[k]
+            v = v.detach() if torch.is_tensor(v) else torch.from_numpy(np.asarray(v, np.float32))
+            v = v.to(device, torch.float32)
+            self.tensors[k] = (v.reshape(v.shape[0], -1) if k.endswith("weight") else v.reshape(-1)).contiguous()
+        for m, p in enumerate(("mlp_lr.", "mlp_hr.")):
+            dims, res = self.shapes[m]
+            for l in range(len(dims) - 1):
+                want = (dims[l + 1], dims[l] + (dims[0] if l in res else 0))
+                if tuple(self.tensors[p + "conv%d.weight" % l].shape) != want or self.tensors[p + "conv%d.bias" % l].numel() != want[0]:
+                    raise ValueError("%sconv%d: weight %s / bias %d against the shape's %s" % (
+                        p, l, tuple(self.tensors[p + "conv%d.weight" % l].shape), self.tensors[p + "conv%d.bias" % l].numel(), want))
+
+    def table(self, m, kind, tensors=None):
+        t = self.tensors if tensors is None else tensors
+        p = ("mlp_lr.", "mlp_hr.")[m]
+        L = len(self.shapes[m][0]) - 1
+        return (C.c_void_p * L)(*[t[p + "conv%d.%s" % (l, kind)].data_ptr() for l in range(L)])
+
+
+def mlp_grad_workspace_bytes(shapes):
+    """surs_mlp_grad_workspace_bytes: the device workspace of mlp_grads for this pair - a function of the shapes, not of n."""
+    lr, hr = (_shape_struct(*s) for s in shapes)
+    n = lib().surs_mlp_grad_workspace_bytes(C.byref(lr), C.byref(hr))
+    if n == 0:
+        raise ValueError(lib().surs_last_error().decode())
+    return n
+
+
+def mlp_grads(points_mr, points_sr, calib_mr, calib_sr, zmul, zdiv, feats_lr, feat_hr, params, lab_lr, lab_hr, loss_weights, m_total,
+              grads=None, accumulate=False, want_preds=False, workspace=None):
+    """surs_mlp_grad: the gradients of SuRSNet.forward's loss with respect to every parameter of MlpParams `params`, for ONE image.
+    points_mr / points_sr [3,N] (query_mr's / query_sr's points), calib_* 12 host floats, feats_lr: a list of S Img (one hr map),
+    lab_lr / lab_hr [N]: what the lr / hr predictions are held against, loss_weights (mlp1, mlp2, dispweight), m_total: the number of
+    points the batch's means run over.  grads: an OrderedDict as this function returns it, to overwrite (accumulate False) or add to
+    (True); None: a new one (accumulate needs one).  Returns grads - keys in state_dict() order, float32 device tensors of the
+    parameters' shapes ([out,in,1] weights) -, with want_preds (grads, pred_lr [S,N], pred_hr [S,N]) of the call's own forward."""
+    S = len(feats_lr)
+    if S < 1:
+        raise ValueError("at least one lr feature map")
+    points_mr, points_sr = _f32c(points_mr), _f32c(points_sr)
+    if points_mr.dim() != 2 or points_mr.shape[0] != 3 or tuple(points_sr.shape) != tuple(points_mr.shape):
+        raise ValueError("points_mr %s and points_sr %s must both be [3,N]" % (tuple(points_mr.shape), tuple(points_sr.shape)))
+    n, dev = points_mr.shape[1], points_mr.device
+    lab_lr, lab_hr = (_f32c(l.to(dev).reshape(-1)) for l in (lab_lr, lab_hr))
+    if lab_lr.numel() != n or lab_hr.numel() != n:
+        raise ValueError("labels must hold one value per point: %d" % n)
+    if len(loss_weights) != 3:
+        raise ValueError("loss_weights: (mlp1, mlp2, dispweight)")
+    if int(m_total) < max(n, 1):
+        raise ValueError("m_total %d: the means run over at least this image's %d points" % (m_total, n))
+    if accumulate and grads is None:
+        raise ValueError("accumulate needs the grads to add to")
+    g = params
+    for f in feats_lr:
+        _check_feat_channels(f.c, feat_hr.c, g)
+    tab = _stack_table(feats_lr, feat_hr)
+    keys = mlp_param_keys(g.shapes)
+    if grads is None:
+        grads = OrderedDict((k, torch.empty(tuple(g.tensors[k].shape) + ((1,) if k.endswith("weight") else ()), dtype=torch.float32,
+                                            device=dev)) for k in keys)
+    else:
+        for k in keys:
+            want = tuple(g.tensors[k].shape) + ((1,) if k.endswith("weight") else ())
+            if k not in grads or tuple(grads[k].shape) != want or grads[k].dtype != torch.float32 or not grads[k].is_contiguous() \
+                    or grads[k].device != dev:
+                raise ValueError("grads[%r] must be a contiguous float32 tensor %s on %s" % (k, want, dev))
+    preds = [torch.empty((S, n), dtype=torch.float32, device=dev) if want_preds else None for _ in range(2)]
+    need = mlp_grad_workspace_bytes(g.shapes)
+    if workspace is None:
+        workspace = torch.empty(need // 4, dtype=torch.float32, device=dev)
+    elif workspace.numel() * workspace.element_size() < need or workspace.device != dev:
+        raise ValueError("workspace: %d bytes needed on %s" % (need, dev))
+    cm, cs = ((C.c_float * 12)(*[float(v) for v in c]) for c in (calib_mr, calib_sr))
+    lw = (C.c_float * 3)(*[float(v) for v in loss_weights])
+    f0 = feats_lr[0]
+    check(lib().surs_mlp_grad(_ptr(points_mr), _ptr(points_sr), n, cm, cs, float(zmul), float(zdiv), S, tab, f0.h, f0.w, feat_hr.ptr(),
+                              feat_hr.h, feat_hr.w, C.byref(g.lr), C.byref(g.hr), g.table(0, "weight"), g.table(0, "bias"),
+                              g.table(1, "weight"), g.table(1, "bias"), _ptr(lab_lr), _ptr(lab_hr), lw, int(m_total),
+                              1 if accumulate else 0, g.table(0, "weight", grads), g.table(0, "bias", grads),
+                              g.table(1, "weight", grads), g.table(1, "bias", grads), _ptr(preds[0]), _ptr(preds[1]),
+                              _ptr(workspace), workspace.numel() * workspace.element_size(), _stream()))
+    return (grads, preds[0], preds[1]) if want_preds else grads
 
 
 def query_points_views(points, calibs, projection, zmul, zdiv, feat_lr, feat_hr, blob, ws, want_logits=False):
