@@ -453,6 +453,32 @@ int surs_mlp_grad(const float *points_mr, const float *points_sr, int n, const f
                   float *const *gw_hr, float *const *gb_hr, float *pred_lr, float *pred_hr, void *workspace, size_t workspace_bytes,
                   void *stream);
 
+/* The same call, and with it d error / d (the feature maps the point rows were sampled from): what an encoder's backward starts
+ * from.  gfeat_lr: HOST array of num_stacks device maps [hl][wl][D] fp32, map s the gradient of feat_lr[s]; gfeat_hr [hh][wh][64]
+ * fp32, the gradient of feat_hr.  accumulate_features 0: the call zeroes the maps first, 1: it adds to them - apart from
+ * `accumulate`, because a batch sums the parameter gradients over its images while every image has maps of its own.  gfeat_lr and
+ * gfeat_hr both NULL: exactly surs_mlp_grad (its launches, its bits, its workspace); one of them NULL is an error.  n == 0 with
+ * accumulate_features 0 still zeroes the maps.  The parameter gradients and predictions have surs_mlp_grad's bits either way.
+ * What is summed: per stack s, chunk of 2048 points and classifier, dX0 = d error / d (the sampled D + 64 channels of the
+ * classifier's input row) = dZ_0 W_0[:, :D + 64] + sum over skip layers l of dZ_l W_l[:, k1 : k1 + D + 64] (fp32 MFMA products, added
+ * layer by layer from the last layer to the first), scattered through the four bilinear taps of the gather (align_corners=True,
+ * zeros padding: the same weights and validity tests; a tap outside the map is dropped, never clamped) - columns [0, D) to
+ * gfeat_lr[s], columns [D, D + 64) to gfeat_hr.  Both classifiers write both maps: mlp_lr at points_mr, mlp_hr at points_sr.
+ * Order: a pixel's contributions of one chunk and classifier are summed from 0 with fmaf in the order (point index, tap (x0,y0),
+ * (x1,y0), (x0,y1), (x1,y1)) and added to the map element once; these partial sums arrive in the order stack, chunk, mlp_hr then
+ * mlp_lr.  No float atomics: two calls give the same bits, wherever the buffers lie.
+ * workspace: surs_mlp_grad_features_workspace_bytes(lr, hr) bytes where maps are given (a function of the shapes alone, neither of n
+ * nor of the map sizes), 256-byte aligned. */
+size_t surs_mlp_grad_features_workspace_bytes(const SursMlpShape *lr, const SursMlpShape *hr);
+int surs_mlp_grad_features(const float *points_mr, const float *points_sr, int n, const float *calib_mr, const float *calib_sr,
+                           float zmul, float zdiv, int num_stacks, const float *const *feat_lr, int hl, int wl, const float *feat_hr,
+                           int hh, int wh, const SursMlpShape *lr, const SursMlpShape *hr, const float *const *w_lr,
+                           const float *const *b_lr, const float *const *w_hr, const float *const *b_hr, const float *lab_lr,
+                           const float *lab_hr, const float *loss_weights, long long m_total, int accumulate, float *const *gw_lr,
+                           float *const *gb_lr, float *const *gw_hr, float *const *gb_hr, float *pred_lr, float *pred_hr,
+                           float *const *gfeat_lr, float *gfeat_hr, int accumulate_features, void *workspace, size_t workspace_bytes,
+                           void *stream);
+
 /* Multi-view query of one subject (num_views = V in [1, 64], orthogonal projection) for classifiers of any supported shape, in ONE
  * launch per call (csrc/surs_mlp_fused_views.inc): lib/model/SurfaceClassifier.py:53-81 with num_views > 1 - layers 0 .. L/2 per
  * view on that view's features, then the view mean ((sum in view order) * (1/V)) of layer L/2's outputs and of the input features,

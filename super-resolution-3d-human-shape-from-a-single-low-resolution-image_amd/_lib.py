@@ -164,6 +164,9 @@ _SIGS = {
     "surs_mlp_grad_workspace_bytes": (_sz, [_shp, _shp]),
     "surs_mlp_grad": (C.c_int, [_vp, _vp, _i, _vp, _vp, _f, _f, _i, _vp, _i, _i, _vp, _i, _i, _shp, _shp, _vp, _vp, _vp, _vp, _vp, _vp,
                                 _vp, C.c_longlong, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "surs_mlp_grad_features_workspace_bytes": (_sz, [_shp, _shp]),
+    "surs_mlp_grad_features": (C.c_int, [_vp, _vp, _i, _vp, _vp, _f, _f, _i, _vp, _i, _i, _vp, _i, _i, _shp, _shp, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, C.c_longlong, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "surs_set_operand_split": (C.c_int, [_i]),
     "surs_set_operand_split_local": (C.c_int, [_i]),
     "surs_set_grid_kernel": (C.c_int, [_i]),

@@ -19,6 +19,19 @@
 // depends on the layer's shape only), every part's product goes to its own slab of the workspace, and a second kernel adds the slabs
 // in order to the output; chunks, stacks and (accumulate = 1) images follow each other on the stream in a fixed order.
 // Workspace: a function of the two shapes alone (surs_mlp_grad_workspace_bytes), whatever n.
+//
+// Feature-map gradients (surs_mlp_grad_features; nothing below runs when the maps are not asked for):
+//   dX0 [points][D + 64] = d error / d (the sampled part of the classifier's input row): dZ_0 W_0[:, :D + 64] plus dZ_l W_l[:, k1 : k1 +
+//                 D + 64] of every skip layer, each product added when backward() visits its layer (EPI_ACC; the first visit overwrites).
+//                 The z and q columns go to no map and are not formed; d q keeps coming from dq_kernel, so that the parameter
+//                 gradients have the bits of the call without maps.
+//   scatter       the transpose of sample(), per chunk and classifier, for the lr map of the stack and the hr map:
+//                 taps_sort_kernel  one workgroup per map: entry e = 4 point + tap gets key (pixel << 13) | e (all ones: tap outside
+//                                   the map) and its weight; bitonic sort of the keys in LDS.  The keys are unique, so the sorted
+//                                   order is a function of the points alone.
+//                 run_sum_kernel    one wave per run of equal pixel, lanes along the channels: sum_e w_e dX0[point_e] in key order
+//                                   (fmaf), then ONE plain read-modify-write of the map row.
+//                 A pixel belongs to one run per launch and launches are serial on the stream: no float atomics, a fixed order.
 #include <hip/hip_runtime.h>
 
 #include "surs_common.h"
@@ -92,7 +105,7 @@ __global__ __launch_bounds__(256) void gather_kernel(GatherArgs a) {
 
 // ------------------------------------------------------------------------------------------------ the GEMM
 // C(m, n) = sum_k A(m, k) B(k, n) over up to two k segments, A(m, k) = A[m a_rs + k a_cs], B(k, n) = B[k b_rs + n b_cs].
-enum { EPI_FWD = 0, EPI_DIN = 1, EPI_PART = 2 };
+enum { EPI_FWD = 0, EPI_DIN = 1, EPI_PART = 2, EPI_ACC = 3 };
 struct GemmSeg {
     const float *A, *B;
     long long a_rs, a_cs, b_rs, b_cs;
@@ -107,6 +120,7 @@ struct GemmArgs {
     const float *aux;     // EPI_FWD: bias [N];  EPI_DIN: the activations H [M][ld_aux] whose sign selects LeakyReLU's slope
     long long ld_aux;
     int leaky;            // EPI_FWD: LeakyReLU(0.01) on the result (every layer but the last)
+    int add;              // EPI_ACC: C += the product (0: C = the product)
 };
 
 // AK: A's k index is the contiguous one (else its m index); BK: the same for B (else its n index) - which way the 64 x 16 tile is
@@ -173,6 +187,8 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
             } else if (EPI == EPI_DIN) {
                 // H = LeakyReLU(Z) has Z's sign; at exactly 0 the derivative is the negative side's slope, as torch
                 v = g.aux[(long long)row * g.ld_aux + col] > 0.0f ? v : 0.01f * v;
+            } else if (EPI == EPI_ACC) {
+                if (g.add) v += C[(long long)row * g.ldc + col];
             }
             C[(long long)row * g.ldc + col] = v;
         }
@@ -218,6 +234,130 @@ __global__ __launch_bounds__(256) void dq_kernel(const float *__restrict__ dz, i
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
     if (lane == 0) dq[p] += s;
+}
+
+// ------------------------------------------------------------------------------------------------ scatter to the feature maps
+constexpr int SC_ENTRIES = 4 * GR_CHUNK;            // taps of a chunk
+constexpr int SC_SHIFT = 13;                        // key = (pixel << SC_SHIFT) | entry
+constexpr unsigned long long SC_NONE = ~0ull;       // a tap outside the map: sorts behind every pixel
+static_assert(SC_ENTRIES == 1 << SC_SHIFT, "an entry must fit the key's low bits");
+
+struct ScatterArgs {
+    const float *pts;     // [3][n]: the classifier's own point set
+    long long n, p0;
+    int nc, pow2;         // points of the chunk; the power of two the sort runs on (>= 4 nc)
+    float calib[12];
+    int H[2], W[2], C[2], col[2];   // map 0: the stack's lr map (columns [0, D) of dX0), map 1: the hr map (columns [D, D + 64))
+    float *map[2];        // [H][W][C]
+    const float *dx0;     // [nc][ld]
+    int ld;
+    unsigned long long *keys;   // [2][SC_ENTRIES] sorted
+    float *wts;                 // [2][SC_ENTRIES] by entry
+};
+
+// NB compare-exchange steps of bitonic stage k on s[0, P), strides j, j / 2, ... j >> (NB - 1) (all >= 1): a thread takes the 2^NB
+// keys whose indices differ in exactly those NB bits, so no key is touched by two threads.  The direction bit k lies above them.
+template <int NB>
+__device__ __forceinline__ void sort_steps(unsigned long long *s, int P, int k, int j) {
+    const int jl = j >> (NB - 1), sh = __ffs(jl) - 1;
+    for (int g = threadIdx.x; g < (P >> NB); g += 1024) {
+        const int base = ((g >> sh) << (sh + NB)) | (g & (jl - 1));
+        const bool up = (base & k) == 0;
+        unsigned long long v[1 << NB];
+#pragma unroll
+        for (int t = 0; t < (1 << NB); ++t) v[t] = s[base + t * jl];
+#pragma unroll
+        for (int b = NB - 1; b >= 0; --b)
+#pragma unroll
+            for (int t = 0; t < (1 << NB); ++t)
+                if (!(t & (1 << b))) {
+                    const unsigned long long x = v[t], y = v[t | (1 << b)];
+                    const bool sw = (x > y) == up;
+                    v[t] = sw ? y : x;
+                    v[t | (1 << b)] = sw ? x : y;
+                }
+#pragma unroll
+        for (int t = 0; t < (1 << NB); ++t) s[base + t * jl] = v[t];
+    }
+}
+
+// Entry e = 4 p + t of map blockIdx.x: tap t of sample() - (x0, y0), (x1, y0), (x0, y1), (x1, y1) - with its weight, validity test
+// and arithmetic; then the sort.  A tap whose x or y index falls outside the map gets no key: it is never written.
+__global__ __launch_bounds__(1024) void taps_sort_kernel(ScatterArgs a) {
+    __shared__ unsigned long long s[SC_ENTRIES];
+    const int mp = blockIdx.x, tid = threadIdx.x;
+    const int H = a.H[mp], W = a.W[mp], P = a.pow2;
+    const float *c = a.calib;
+    for (int e = tid; e < P; e += 1024) {
+        unsigned long long key = SC_NONE;
+        if (e < 4 * a.nc) {
+            const long long t = a.p0 + (e >> 2);
+            const float px = a.pts[t], py = a.pts[a.n + t], pz = a.pts[2 * a.n + t];
+            const float u = c[3] + ((c[0] * px + c[1] * py) + c[2] * pz);
+            const float v = c[7] + ((c[4] * px + c[5] * py) + c[6] * pz);
+            const float ix = ((u + 1.0f) / 2.0f) * (float)(W - 1);
+            const float iy = ((v + 1.0f) / 2.0f) * (float)(H - 1);
+            const float fx = floorf(ix), fy = floorf(iy);
+            const bool finite = fabsf(fx) < 1.0e9f && fabsf(fy) < 1.0e9f;   // (else the int conversion means nothing: no tap is valid)
+            const int x0 = finite ? (int)fx : -2, y0 = finite ? (int)fy : -2, x1 = x0 + 1, y1 = y0 + 1;
+            const int xt = (e & 1) ? x1 : x0, yt = (e & 2) ? y1 : y0;
+            const float wx = (e & 1) ? ix - (float)x0 : (float)x1 - ix;
+            const float wy = (e & 2) ? iy - (float)y0 : (float)y1 - iy;
+            if (finite && xt >= 0 && xt < W && yt >= 0 && yt < H) {
+                key = ((unsigned long long)((long long)yt * W + xt) << SC_SHIFT) | (unsigned long long)e;
+                a.wts[mp * SC_ENTRIES + e] = wx * wy;
+            }
+        }
+        s[e] = key;
+    }
+    __syncthreads();
+    // bitonic sort; the compare-exchange steps of strides j, j / 2, j / 4 of a stage run on 8 keys in registers per pass over LDS:
+    // 35 passes over the 64 KiB for 8192 keys instead of 91
+    for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0;) {
+            const int nb = j >= 4 ? 3 : (j == 2 ? 2 : 1);
+            if (nb == 3) sort_steps<3>(s, P, k, j);
+            else if (nb == 2) sort_steps<2>(s, P, k, j);
+            else sort_steps<1>(s, P, k, j);
+            __syncthreads();
+            j >>= nb;
+        }
+    for (int e = tid; e < 4 * a.nc; e += 1024) a.keys[mp * SC_ENTRIES + e] = s[e];
+}
+
+// One wave per sorted position i of map blockIdx.y; the wave at the first position of a pixel's run sums the run and writes the row.
+__global__ __launch_bounds__(256) void run_sum_kernel(ScatterArgs a) {
+    const int lane = threadIdx.x & 63, mp = blockIdx.y;
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), ne = 4 * a.nc;
+    if (i >= ne) return;
+    const unsigned long long *keys = a.keys + mp * SC_ENTRIES;
+    const unsigned long long k0 = keys[i];
+    if (k0 == SC_NONE) return;
+    const unsigned long long pix = k0 >> SC_SHIFT;
+    if (i > 0 && (keys[i - 1] >> SC_SHIFT) == pix) return;
+    const float *wts = a.wts + mp * SC_ENTRIES;
+    const int C = a.C[mp];
+    float *row = a.map[mp] + (long long)pix * C;
+    for (int c0 = 0; c0 < C; c0 += 256) {   // 4 channels per lane and pass: one pass for every D up to 256
+        float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (int j = i; j < ne; ++j) {
+            const unsigned long long k = keys[j];
+            if ((k >> SC_SHIFT) != pix) break;   // (SC_NONE's pixel is above every map's)
+            const int e = (int)(k & (SC_ENTRIES - 1));
+            const float w = wts[e];
+            const float *src = a.dx0 + (long long)(e >> 2) * a.ld + a.col[mp] + c0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int ch = 64 * r + lane;
+                if (c0 + ch < C) acc[r] = fmaf(w, src[ch], acc[r]);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int ch = c0 + 64 * r + lane;
+            if (ch < C) row[ch] += acc[r];
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ output stages
@@ -295,6 +435,7 @@ static int splits_of(int m, int k) {
 struct Plan {          // workspace offsets in floats
     size_t x0[2], h[2][GEN_MAX_LAYERS], logit[2], dz[2], slabs, vec, total;
     size_t maxw;
+    size_t dx0, keys, wts, total_feat;   // surs_mlp_grad_features' own part, behind `total`: the offsets above do not move
 };
 
 static void plan_of(const Net (&net)[2], Plan &p) {
@@ -323,6 +464,11 @@ static void plan_of(const Net (&net)[2], Plan &p) {
     p.slabs = take(slabs);
     p.vec = take((size_t)8 * GR_CHUNK);   // mask_mr, mask_sr, q, sig_lr, dl_lr, dl_hr, dq, spare
     p.total = off;
+    // dX0 of one classifier at a time (mlp_hr's is scattered before mlp_lr's backward starts); c0 - 1 >= D + 64 of either classifier
+    p.dx0 = take((size_t)GR_CHUNK * (net[0].c0 - 1));
+    p.keys = take((size_t)2 * SC_ENTRIES * 2);   // 64-bit keys of both maps
+    p.wts = take((size_t)2 * SC_ENTRIES);
+    p.total_feat = off;
 }
 
 static int check_pair(const SursMlpShape *lr, const SursMlpShape *hr) {
@@ -359,10 +505,26 @@ static int forward(hipStream_t st, const Net &n, float *ws, const Plan &p, int m
     return 0;
 }
 
-// backward of classifier m: dl [nc] = d logit; gradients added to gw / gb; dq (hr only): += d error / d (last input channel)
+// dX0 [nc][nf] (+)= dZ [nc][mo] W[:, col : col + nf], W [mo][kin]
+static int input_grad(hipStream_t st, const float *dz, int nc, int mo, const float *w, int kin, int col, int nf, float *dx0, bool add) {
+    GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    g.seg[0] = GemmSeg{dz, w + col, mo, 1, kin, 1, mo};
+    g.nseg = 1;
+    g.M = nc;
+    g.N = nf;
+    g.C = dx0;
+    g.ldc = nf;
+    g.add = add ? 1 : 0;
+    return launch_gemm<true, false, EPI_ACC>(st, g, 1);
+}
+
+// backward of classifier m: dl [nc] = d logit; gradients added to gw / gb; dq (hr only): += d error / d (last input channel);
+// dx0 (nullable) [nc][nf] = d error / d (the first nf input channels), every layer's part added as the layer is visited
 static int backward(hipStream_t st, const Net &n, float *ws, const Plan &p, int m, int nc, const float *const *w, const float *dl,
-                    float *const *gw, float *const *gb, float *dq) {
+                    float *const *gw, float *const *gb, float *dq, float *dx0, int nf) {
     const float *dz = dl;
+    bool have_dx0 = false;
     for (int l = n.L - 1; l >= 0; --l) {
         const int mo = n.dims[l + 1], k1 = n.dims[l], kin = n.in[l];
         hipLaunchKernelGGL(bias_grad_kernel, dim3(ceil_div(mo, 64)), dim3(256), 0, st, dz, nc, mo, gb[l]);
@@ -397,6 +559,17 @@ static int backward(hipStream_t st, const Net &n, float *ws, const Plan &p, int 
             if (n.res[l]) {
                 hipLaunchKernelGGL(dq_kernel, dim3(ceil_div(nc, 4)), dim3(256), 0, st, dz, nc, mo, w[l] + k1 + n.c0 - 1, (long long)kin, dq);
                 SURS_LAUNCH_CHECK();
+            }
+        }
+        if (dx0) {   // the skip segment, then layer 0's own inputs
+            if (n.res[l]) {
+                const int rc = input_grad(st, dz, nc, mo, w[l], kin, k1, nf, dx0, have_dx0);
+                if (rc) return rc;
+                have_dx0 = true;
+            }
+            if (l == 0) {
+                const int rc = input_grad(st, dz, nc, mo, w[l], kin, 0, nf, dx0, have_dx0);
+                if (rc) return rc;
             }
         }
         if (l >= 1) {   // dZ of the layer below = (dZ W[:, :k1]) * LeakyReLU'(H_l)
@@ -435,13 +608,26 @@ extern "C" size_t surs_mlp_grad_workspace_bytes(const SursMlpShape *lr, const Su
     return p.total * sizeof(float);
 }
 
-extern "C" int surs_mlp_grad(const float *points_mr, const float *points_sr, int n, const float *calib_mr, const float *calib_sr,
-                             float zmul, float zdiv, int num_stacks, const float *const *feat_lr, int hl, int wl, const float *feat_hr,
-                             int hh, int wh, const SursMlpShape *lr, const SursMlpShape *hr, const float *const *w_lr,
-                             const float *const *b_lr, const float *const *w_hr, const float *const *b_hr, const float *lab_lr,
-                             const float *lab_hr, const float *loss_weights, long long m_total, int accumulate, float *const *gw_lr,
-                             float *const *gb_lr, float *const *gw_hr, float *const *gb_hr, float *pred_lr, float *pred_hr,
-                             void *workspace, size_t workspace_bytes, void *stream) {
+extern "C" size_t surs_mlp_grad_features_workspace_bytes(const SursMlpShape *lr, const SursMlpShape *hr) {
+    if (check_pair(lr, hr)) return 0;
+    Net net[2];
+    net_of(*lr, net[0]);
+    net_of(*hr, net[1]);
+    Plan p;
+    plan_of(net, p);
+    return p.total_feat * sizeof(float);
+}
+
+extern "C" int surs_mlp_grad_features(const float *points_mr, const float *points_sr, int n, const float *calib_mr,
+                                      const float *calib_sr, float zmul, float zdiv, int num_stacks, const float *const *feat_lr, int hl,
+                                      int wl, const float *feat_hr, int hh, int wh, const SursMlpShape *lr, const SursMlpShape *hr,
+                                      const float *const *w_lr, const float *const *b_lr, const float *const *w_hr,
+                                      const float *const *b_hr, const float *lab_lr, const float *lab_hr, const float *loss_weights,
+                                      long long m_total, int accumulate, float *const *gw_lr, float *const *gb_lr, float *const *gw_hr,
+                                      float *const *gb_hr, float *pred_lr, float *pred_hr, float *const *gfeat_lr, float *gfeat_hr,
+                                      int accumulate_features, void *workspace, size_t workspace_bytes, void *stream) {
+    const bool feat = gfeat_lr || gfeat_hr;
+    SURS_REQUIRE(!feat || (gfeat_lr && gfeat_hr), "gfeat_lr and gfeat_hr come together");
     SURS_REQUIRE(n >= 0, "negative point count");
     SURS_REQUIRE(num_stacks >= 1 && num_stacks <= GR_MAX_STACKS, "num_stacks must be between 1 and %d", GR_MAX_STACKS);
     SURS_REQUIRE(m_total >= 1 && m_total >= n, "the denominator M must be at least n (and 1)");
@@ -460,7 +646,13 @@ extern "C" int surs_mlp_grad(const float *points_mr, const float *points_sr, int
     for (int m = 0; m < 2; ++m)
         for (int l = 0; l < net[m].L; ++l) SURS_REQUIRE(w[m][l] && b[m][l] && gw[m][l] && gb[m][l], "null weight or gradient pointer");
     for (int s = 0; s < num_stacks; ++s) SURS_REQUIRE(feat_lr[s], "null feature map");
+    for (int s = 0; feat && s < num_stacks; ++s) SURS_REQUIRE(gfeat_lr[s], "null feature-map gradient");
     hipStream_t st = as_stream(stream);
+    const int D = gen_hg_dim(*lr), nf = D + GEN_C_HR;
+    if (feat && !accumulate_features) {
+        for (int s = 0; s < num_stacks; ++s) SURS_HIP_CHECK(hipMemsetAsync(gfeat_lr[s], 0, sizeof(float) * hl * wl * D, st));
+        SURS_HIP_CHECK(hipMemsetAsync(gfeat_hr, 0, sizeof(float) * hh * wh * GEN_C_HR, st));
+    }
     if (!accumulate)
         for (int m = 0; m < 2; ++m)
             for (int l = 0; l < net[m].L; ++l) {
@@ -469,10 +661,34 @@ extern "C" int surs_mlp_grad(const float *points_mr, const float *points_sr, int
             }
     if (n == 0) return 0;
     SURS_REQUIRE(points_mr && points_sr && lab_lr && lab_hr, "null argument");
-    SURS_REQUIRE(workspace && workspace_bytes >= p.total * sizeof(float), "workspace too small: %zu bytes needed", p.total * sizeof(float));
+    const size_t need = (feat ? p.total_feat : p.total) * sizeof(float);
+    SURS_REQUIRE(workspace && workspace_bytes >= need, "workspace too small: %zu bytes needed", need);
     float *ws = (float *)workspace;
     float *vec = ws + p.vec;
-    const int D = gen_hg_dim(*lr);
+    float *dx0 = feat ? ws + p.dx0 : nullptr;
+    // the transpose of the gather of classifier m's rows: both maps, this chunk
+    auto scatter = [&](int m, int s, long long p0, int nc) -> int {
+        ScatterArgs sa;
+        memset(&sa, 0, sizeof(sa));
+        sa.pts = m ? points_sr : points_mr;
+        sa.n = n;
+        sa.p0 = p0;
+        sa.nc = nc;
+        sa.pow2 = 4;
+        while (sa.pow2 < 4 * nc) sa.pow2 *= 2;
+        for (int i = 0; i < 12; ++i) sa.calib[i] = (m ? calib_sr : calib_mr)[i];
+        sa.H[0] = hl, sa.W[0] = wl, sa.C[0] = D, sa.col[0] = 0, sa.map[0] = gfeat_lr[s];
+        sa.H[1] = hh, sa.W[1] = wh, sa.C[1] = GEN_C_HR, sa.col[1] = D, sa.map[1] = gfeat_hr;
+        sa.dx0 = dx0;
+        sa.ld = nf;
+        sa.keys = (unsigned long long *)(ws + p.keys);
+        sa.wts = ws + p.wts;
+        hipLaunchKernelGGL(taps_sort_kernel, dim3(2), dim3(1024), 0, st, sa);
+        SURS_LAUNCH_CHECK();
+        hipLaunchKernelGGL(run_sum_kernel, dim3(ceil_div(4 * nc, 4), 2), dim3(256), 0, st, sa);
+        SURS_LAUNCH_CHECK();
+        return 0;
+    };
     const double sm = (double)num_stacks * (double)m_total;
     for (int s = 0; s < num_stacks; ++s)
         for (long long p0 = 0; p0 < n; p0 += GR_CHUNK) {
@@ -529,10 +745,24 @@ extern "C" int surs_mlp_grad(const float *points_mr, const float *points_sr, int
             if ((rc = forward(st, net[1], ws, p, 1, nc, w[1], b[1]))) return rc;
             hipLaunchKernelGGL(hr_out_kernel, og, dim3(256), 0, st, oa);
             SURS_LAUNCH_CHECK();
-            if ((rc = backward(st, net[1], ws, p, 1, nc, w[1], oa.dl_hr, gw[1], gb[1], oa.dq))) return rc;
+            if ((rc = backward(st, net[1], ws, p, 1, nc, w[1], oa.dl_hr, gw[1], gb[1], oa.dq, dx0, nf))) return rc;
+            if (feat && (rc = scatter(1, s, p0, nc))) return rc;
             hipLaunchKernelGGL(lr_dlogit_kernel, og, dim3(256), 0, st, oa);
             SURS_LAUNCH_CHECK();
-            if ((rc = backward(st, net[0], ws, p, 0, nc, w[0], oa.dl_lr, gw[0], gb[0], nullptr))) return rc;
+            if ((rc = backward(st, net[0], ws, p, 0, nc, w[0], oa.dl_lr, gw[0], gb[0], nullptr, dx0, nf))) return rc;
+            if (feat && (rc = scatter(0, s, p0, nc))) return rc;
         }
     return 0;
+}
+
+extern "C" int surs_mlp_grad(const float *points_mr, const float *points_sr, int n, const float *calib_mr, const float *calib_sr,
+                             float zmul, float zdiv, int num_stacks, const float *const *feat_lr, int hl, int wl, const float *feat_hr,
+                             int hh, int wh, const SursMlpShape *lr, const SursMlpShape *hr, const float *const *w_lr,
+                             const float *const *b_lr, const float *const *w_hr, const float *const *b_hr, const float *lab_lr,
+                             const float *lab_hr, const float *loss_weights, long long m_total, int accumulate, float *const *gw_lr,
+                             float *const *gb_lr, float *const *gw_hr, float *const *gb_hr, float *pred_lr, float *pred_hr,
+                             void *workspace, size_t workspace_bytes, void *stream) {
+    return surs_mlp_grad_features(points_mr, points_sr, n, calib_mr, calib_sr, zmul, zdiv, num_stacks, feat_lr, hl, wl, feat_hr, hh, wh,
+                                  lr, hr, w_lr, b_lr, w_hr, b_hr, lab_lr, lab_hr, loss_weights, m_total, accumulate, gw_lr, gb_lr, gw_hr,
+                                  gb_hr, pred_lr, pred_hr, nullptr, nullptr, 0, workspace, workspace_bytes, stream);
 }

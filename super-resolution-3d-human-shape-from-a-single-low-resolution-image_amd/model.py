@@ -11,8 +11,9 @@ It is NOT a torch.nn.Module: parameters are a flat ordered dict keyed exactly li
 no autograd graph and no optimiser and no CPU path: methods raise without a GPU / built library.  forward() is the
 VALIDATION forward: every kept stack's predictions and the reference's loss, without an autograd graph (SuRSNet.py:240-266).
 The one part of the backward pass that exists is the classifiers': forward_backward() / classifier_grads() return d error / d (every
-mlp_lr.* and mlp_hr.* parameter) with the encoder frozen (native.mlp_grads); the encoder's and the super-resolution network's
-gradients, and gradients with respect to the feature maps, are out of scope.
+mlp_lr.* and mlp_hr.* parameter) and, with features=True, d error / d (the feature maps of im_feat_list_lr and im_feat_list_hr[0])
+(native.mlp_grads) - where an encoder's backward starts; autograd.point_loss hands them to torch autograd.  The encoder's and the
+super-resolution network's own parameter gradients are out of scope.
 
 Encoder options: --norm group | batch and --scale 1..4 (anything else: ValueError at construction).  --norm batch is nn.BatchNorm2d in
 EVAL mode - y = (x - running_mean) / sqrt(running_var + 1e-5) * weight + bias, always from the running statistics: train() here keeps
@@ -83,6 +84,7 @@ class SuRSNet:
         self._sr_args = None
         self._grad_params = None      # native.MlpParams: the device copy of the fp32 classifier weights (dropped like the blob)
         self._grad_ws = None
+        self.last_classifier_grads = None   # what autograd.point_loss last left: classifier_grads()'s OrderedDict
         self._feat_cache = None
         self._stack_feat_cache = None
         self.labels_lr = self.labels_hr = None
@@ -695,16 +697,20 @@ class SuRSNet:
             self._grad_params = native.MlpParams(sd, self._device(), shapes)
         return self._grad_params
 
-    def classifier_grads(self):
+    def classifier_grads(self, features=False):
         """d error / d (every mlp_lr.* and mlp_hr.* parameter) of forward()'s loss - opt.mlp1 get_error_lr() + opt.mlp2 get_error_hr()
         + opt.dispweight get_error_disp_1(); the super-resolution term does not depend on these parameters - from what the preceding
         query_mr(labels=...) + query_sr(labels=...) left on this object: their points, calibrations, transforms and labels, the
         feature maps of im_feat_list_lr (every kept stack in training mode, the last one in eval mode) and im_feat_list_hr[0].
         Returns an OrderedDict in state_dict() key order holding every mlp_* key: float32 device tensors of the parameters' shapes
         ([out,in,1] weights), summed over stacks and over the images of the batch.  The encoder is frozen: mlp_lr's gradient
-        has its three sources (its own term, the displacement term, mlp_hr's last input channel), but there are no gradients for the
-        encoder / super-resolution parameters and none with respect to the feature maps (out of scope).  fp32-grade whatever
-        --precision says, deterministic (two calls give the same bits).  num_views == 1 and orthogonal projection only."""
+        has its three sources (its own term, the displacement term, mlp_hr's last input channel), and there are no gradients for the
+        encoder / super-resolution parameters (out of scope).  features=True returns (grads, feat_grads): the same grads, bit for
+        bit, and d error / d (the feature maps) - feat_grads["lr"]: a list with one float32 device tensor per entry of
+        im_feat_list_lr, each of that entry's shape [B,D,hl,wl]; feat_grads["hr"]: of im_feat_list_hr[0]'s shape [B,64,hh,wh] -,
+        what an encoder's backward starts from (autograd.point_loss hands them to torch autograd).  An image whose points all fall
+        outside gets exact zeros.  fp32-grade whatever --precision says, deterministic (two calls give the same bits).  num_views
+        == 1 and orthogonal projection only."""
         if self.num_views != 1 or self.projection_mode != "orthogonal":
             raise NotImplementedError(self._GRADS_LIMIT)
         if self._mr_points is None:
@@ -732,26 +738,43 @@ class SuRSNet:
             raise ValueError("points [%d,3,N] and calibs [%d,4,4] / [%d,4,4] disagree" % (B, cal_mr.shape[0], cal_sr.shape[0]))
         zmul, zdiv = self._zscale()
         params = self._mlp_params()
-        if self._grad_ws is None or self._grad_ws[0] != params.shapes:
-            need = native.mlp_grad_workspace_bytes(params.shapes)
+        need = (native.mlp_grad_features_workspace_bytes if features else native.mlp_grad_workspace_bytes)(params.shapes)
+        if self._grad_ws is None or self._grad_ws[0] != params.shapes or self._grad_ws[1].numel() * 4 < need:
             self._grad_ws = (params.shapes, torch.empty(need // 4, dtype=torch.float32, device=dev))
         w = (self.opt.mlp1, self.opt.mlp2, self.opt.dispweight)
         grads = None
+        if features:
+            # NCHW-shaped like the model's maps, NHWC in memory: image b of each is the contiguous [h,w,C] block the library writes
+            like = lambda t: torch.empty((t.shape[0], t.shape[2], t.shape[3], t.shape[1]), dtype=torch.float32, device=dev)
+            g_lr, g_hr = [like(t) for t in self.im_feat_list_lr], like(self.im_feat_list_hr[0])
         for b in range(B):
             feats, fh = self.stack_features(b)
-            grads = native.mlp_grads(pm[b].to(dev, torch.float32).contiguous(), ps[b].to(dev, torch.float32).contiguous(), cal_mr[b],
-                                     cal_sr[b], zmul, zdiv, feats, fh, params, lab[0][b], lab[1][b], w, B * N, grads=grads,
-                                     accumulate=b > 0, workspace=self._grad_ws[1])
+            fg = native.FeatGrads([t[b] for t in g_lr], g_hr[b]) if features else None
+            out = native.mlp_grads(pm[b].to(dev, torch.float32).contiguous(), ps[b].to(dev, torch.float32).contiguous(), cal_mr[b],
+                                   cal_sr[b], zmul, zdiv, feats, fh, params, lab[0][b], lab[1][b], w, B * N, grads=grads,
+                                   accumulate=b > 0, workspace=self._grad_ws[1], feat_grads=fg)
+            grads = out[0] if features else out
+        if features:
+            return grads, dict(lr=[t.permute(0, 3, 1, 2) for t in g_lr], hr=g_hr.permute(0, 3, 1, 2))
         return grads
 
-    def forward_backward(self, images_lr, images_hr, points_lr, points_hr, calibs, transforms=None, labels_lr=None, labels_hr=None):
+    def forward_backward(self, images_lr, images_hr, points_lr, points_hr, calibs, transforms=None, labels_lr=None, labels_hr=None,
+                         features=False):
         """forward() and the classifiers' gradients of its loss: (res_hr, error, res_lr, grads).  The first three are exactly forward()'s
         (it is called; error still has no autograd graph), grads is classifier_grads()'s OrderedDict: every mlp_lr.* / mlp_hr.* key in
-        state_dict() order, float32 device tensors of the parameters' shapes.  Out of scope: gradients for the encoder /
-        super-resolution parameters and gradients with respect to the feature maps (the encoder is frozen); num_views == 1 and
-        orthogonal projection only."""
+        state_dict() order, float32 device tensors of the parameters' shapes.  features=True: (res_hr, error, res_lr, grads,
+        feat_grads) with classifier_grads(features=True)'s feat_grads and feat_grads["img_SR"] = opt.srweight sign(img_SR -
+        images_hr) / numel (torch's L1 backward, 0 at equality) - everything the loss hands back to the encoder.  Out of scope:
+        gradients for the encoder / super-resolution parameters themselves; num_views == 1 and orthogonal projection only."""
         if self.num_views != 1 or self.projection_mode != "orthogonal":
             raise NotImplementedError(self._GRADS_LIMIT)
         res_hr, error, res_lr = self.forward(images_lr, images_hr, points_lr, points_hr, calibs, transforms=transforms,
                                              labels_lr=labels_lr, labels_hr=labels_hr)
-        return res_hr, error, res_lr, self.classifier_grads()
+        if not features:
+            return res_hr, error, res_lr, self.classifier_grads()
+        grads, feat_grads = self.classifier_grads(features=True)
+        img_SR = self.im_SR.to(self._device(), torch.float32)
+        # (an fp32 division, as the backward of torch's mean: the bits of opt.srweight * l1_loss(img_SR, images_hr).backward())
+        scale = torch.full((), float(self.opt.srweight), dtype=torch.float32, device=img_SR.device) / img_SR.numel()
+        feat_grads["img_SR"] = torch.sign(img_SR - images_hr.to(img_SR.device, torch.float32)) * scale
+        return res_hr, error, res_lr, grads, feat_grads

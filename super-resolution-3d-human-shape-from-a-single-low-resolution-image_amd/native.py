@@ -982,14 +982,50 @@ def mlp_grad_workspace_bytes(shapes):
     return n
 
 
+def mlp_grad_features_workspace_bytes(shapes):
+    """surs_mlp_grad_features_workspace_bytes: the workspace of mlp_grads(feat_grads=...) - a function of the shapes, neither of n nor
+    of the map sizes."""
+    lr, hr = (_shape_struct(*s) for s in shapes)
+    n = lib().surs_mlp_grad_features_workspace_bytes(C.byref(lr), C.byref(hr))
+    if n == 0:
+        raise ValueError(lib().surs_last_error().decode())
+    return n
+
+
+class FeatGrads:
+    """d error / d (the feature maps) of one image, as mlp_grads(feat_grads=...) fills them: lr - a list of S NHWC float32 device
+    tensors [hl,wl,D], one per lr map -, hr [hh,wh,64].  Given tensors are used as they are (contiguous float32, e.g. views into
+    a batch's buffer); FeatGrads.like(feats_lr, feat_hr) allocates."""
+
+    def __init__(self, lr, hr):
+        self.lr, self.hr = list(lr), hr
+
+    @staticmethod
+    def like(feats_lr, feat_hr, device):
+        return FeatGrads([torch.empty((f.h, f.w, f.c), dtype=torch.float32, device=device) for f in feats_lr],
+                         torch.empty((feat_hr.h, feat_hr.w, feat_hr.c), dtype=torch.float32, device=device))
+
+    def check(self, feats_lr, feat_hr, device):
+        if len(self.lr) != len(feats_lr):
+            raise ValueError("feat_grads: %d lr maps against %d feature maps" % (len(self.lr), len(feats_lr)))
+        for t, f in zip(self.lr + [self.hr], list(feats_lr) + [feat_hr]):
+            if tuple(t.shape) != (f.h, f.w, f.c) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != device:
+                raise ValueError("feat_grads: a contiguous float32 tensor %s on %s is needed, not %s %s"
+                                 % ((f.h, f.w, f.c), device, tuple(t.shape), t.dtype))
+
+
 def mlp_grads(points_mr, points_sr, calib_mr, calib_sr, zmul, zdiv, feats_lr, feat_hr, params, lab_lr, lab_hr, loss_weights, m_total,
-              grads=None, accumulate=False, want_preds=False, workspace=None):
+              grads=None, accumulate=False, want_preds=False, workspace=None, feat_grads=None, accumulate_features=False):
     """surs_mlp_grad: the gradients of SuRSNet.forward's loss with respect to every parameter of MlpParams `params`, for ONE image.
     points_mr / points_sr [3,N] (query_mr's / query_sr's points), calib_* 12 host floats, feats_lr: a list of S Img (one hr map),
     lab_lr / lab_hr [N]: what the lr / hr predictions are held against, loss_weights (mlp1, mlp2, dispweight), m_total: the number of
     points the batch's means run over.  grads: an OrderedDict as this function returns it, to overwrite (accumulate False) or add to
     (True); None: a new one (accumulate needs one).  Returns grads - keys in state_dict() order, float32 device tensors of the
-    parameters' shapes ([out,in,1] weights) -, with want_preds (grads, pred_lr [S,N], pred_hr [S,N]) of the call's own forward."""
+    parameters' shapes ([out,in,1] weights) -, with want_preds (grads, pred_lr [S,N], pred_hr [S,N]) of the call's own forward.
+    feat_grads (surs_mlp_grad_features): a FeatGrads to overwrite (accumulate_features False: whatever it held, also with N = 0) or
+    add to (True), or True for a new one; it is returned last - (grads, feat_grads) or (grads, pred_lr, pred_hr, feat_grads) - and
+    holds d error / d (the maps of feats_lr) and d error / d feat_hr of this image.  The parameter gradients have the same bits with
+    and without it.  None: the call, launches and workspace of surs_mlp_grad."""
     S = len(feats_lr)
     if S < 1:
         raise ValueError("at least one lr feature map")
@@ -1021,7 +1057,15 @@ def mlp_grads(points_mr, points_sr, calib_mr, calib_sr, zmul, zdiv, feats_lr, fe
                     or grads[k].device != dev:
                 raise ValueError("grads[%r] must be a contiguous float32 tensor %s on %s" % (k, want, dev))
     preds = [torch.empty((S, n), dtype=torch.float32, device=dev) if want_preds else None for _ in range(2)]
-    need = mlp_grad_workspace_bytes(g.shapes)
+    if feat_grads is True:
+        feat_grads = FeatGrads.like(feats_lr, feat_hr, dev)
+    elif feat_grads is False:
+        feat_grads = None
+    if feat_grads is None and accumulate_features:
+        raise ValueError("accumulate_features needs the feat_grads to add to")
+    if feat_grads is not None:
+        feat_grads.check(feats_lr, feat_hr, dev)
+    need = mlp_grad_workspace_bytes(g.shapes) if feat_grads is None else mlp_grad_features_workspace_bytes(g.shapes)
     if workspace is None:
         workspace = torch.empty(need // 4, dtype=torch.float32, device=dev)
     elif workspace.numel() * workspace.element_size() < need or workspace.device != dev:
@@ -1029,13 +1073,20 @@ def mlp_grads(points_mr, points_sr, calib_mr, calib_sr, zmul, zdiv, feats_lr, fe
     cm, cs = ((C.c_float * 12)(*[float(v) for v in c]) for c in (calib_mr, calib_sr))
     lw = (C.c_float * 3)(*[float(v) for v in loss_weights])
     f0 = feats_lr[0]
-    check(lib().surs_mlp_grad(_ptr(points_mr), _ptr(points_sr), n, cm, cs, float(zmul), float(zdiv), S, tab, f0.h, f0.w, feat_hr.ptr(),
-                              feat_hr.h, feat_hr.w, C.byref(g.lr), C.byref(g.hr), g.table(0, "weight"), g.table(0, "bias"),
-                              g.table(1, "weight"), g.table(1, "bias"), _ptr(lab_lr), _ptr(lab_hr), lw, int(m_total),
-                              1 if accumulate else 0, g.table(0, "weight", grads), g.table(0, "bias", grads),
-                              g.table(1, "weight", grads), g.table(1, "bias", grads), _ptr(preds[0]), _ptr(preds[1]),
-                              _ptr(workspace), workspace.numel() * workspace.element_size(), _stream()))
-    return (grads, preds[0], preds[1]) if want_preds else grads
+    head = (_ptr(points_mr), _ptr(points_sr), n, cm, cs, float(zmul), float(zdiv), S, tab, f0.h, f0.w, feat_hr.ptr(), feat_hr.h,
+            feat_hr.w, C.byref(g.lr), C.byref(g.hr), g.table(0, "weight"), g.table(0, "bias"), g.table(1, "weight"),
+            g.table(1, "bias"), _ptr(lab_lr), _ptr(lab_hr), lw, int(m_total), 1 if accumulate else 0, g.table(0, "weight", grads),
+            g.table(0, "bias", grads), g.table(1, "weight", grads), g.table(1, "bias", grads), _ptr(preds[0]), _ptr(preds[1]))
+    tail = (_ptr(workspace), workspace.numel() * workspace.element_size(), _stream())
+    if feat_grads is None:
+        check(lib().surs_mlp_grad(*head, *tail))
+    else:
+        maps = (C.c_void_p * S)(*[t.data_ptr() for t in feat_grads.lr])
+        check(lib().surs_mlp_grad_features(*head, maps, _ptr(feat_grads.hr), 1 if accumulate_features else 0, *tail))
+    out = (grads, preds[0], preds[1]) if want_preds else (grads,)
+    if feat_grads is not None:
+        out += (feat_grads,)
+    return out if len(out) > 1 else out[0]
 
 
 def query_points_views(points, calibs, projection, zmul, zdiv, feat_lr, feat_hr, blob, ws, want_logits=False):
