@@ -69,15 +69,12 @@ __device__ __forceinline__ void grid_mlp_v10(const char *__restrict__ wbase /* t
     auto gl4 = [&](const float *base, int float_off) { return *reinterpret_cast<const f32x4 *>(base + float_off); };
     auto ldB = [&](int byte_base, int slot, int ct) { return *reinterpret_cast<const vec8 *>(ybase + byte_base + (slot * 4 + ct) * 1024); };
     auto cvt8 = [&](const f32x16 &t, int u) {
-        // LeakyReLU = max(x, 0.01 x): the products two at a time (v_pk_mul_f32: same IEEE product, half the instructions)
+        // LeakyReLU = max(x, 0.01 x): one v_mul_f32 and one maximum per value (lrelu01).  Not the products two at a time: beside
+        // MFMAs a v_pk_mul_f32 costs more than the two v_mul_f32 it replaces, and its result needs a wait state before the
+        // maximum that reads it (measured on kernel v12's slab: NOTES, "Column kernels: one maximum per LeakyReLU")
         vec8 b;
 #pragma unroll
-        for (int j = 0; j < 8; j += 2) {
-            const f32x2 x = {t[8 * u + j], t[8 * u + j + 1]};
-            const f32x2 y = x * 0.01f;
-            b[j] = (elem)fmaxf(x[0], y[0]);
-            b[j + 1] = (elem)fmaxf(x[1], y[1]);
-        }
+        for (int j = 0; j < 8; ++j) b[j] = (elem)lrelu01(t[8 * u + j]);
         return b;
     };
     auto ldw = [&](unsigned voff, int imm) { return *reinterpret_cast<const vec8 *>(wbase + (size_t)voff + imm); };

@@ -124,14 +124,10 @@ __device__ __forceinline__ bool grid_mlp_v12(const char *__restrict__ wbase /* t
     auto lds4 = [&](unsigned off, int imm) { return *reinterpret_cast<const f32x4 *>(smem + off + imm); };
     auto ldsB = [&](unsigned off, int imm) { return *reinterpret_cast<const vec8 *>(smem + off + imm); };
     auto cvt8 = [&](const f32x16 &t, int u) {
+        // (v10's: scalar products, one maximum per value - same bits, and faster beside MFMAs than v_pk_mul_f32)
         vec8 b;
 #pragma unroll
-        for (int j = 0; j < 8; j += 2) {
-            const f32x2 x = {t[8 * u + j], t[8 * u + j + 1]};
-            const f32x2 y = x * 0.01f;
-            b[j] = (elem)fmaxf(x[0], y[0]);
-            b[j + 1] = (elem)fmaxf(x[1], y[1]);
-        }
+        for (int j = 0; j < 8; ++j) b[j] = (elem)lrelu01(t[8 * u + j]);
         return b;
     };
 #ifdef SURS_V3_TRACE

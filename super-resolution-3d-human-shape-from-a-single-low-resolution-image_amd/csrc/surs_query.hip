@@ -578,7 +578,15 @@ struct GridArgs {
     float zmul, zdiv;
 };
 
-__device__ __forceinline__ float lrelu01(float x) { return fmaxf(x, 0.01f * x); }
+// max(x, y) where y = 0.01 x: the second half of every LeakyReLU of the column kernels.  fmaxf is llvm.maxnum, and in front of
+// it hipcc canonicalises (v_max_f32 v, v, v) every operand it cannot prove free of signalling NaNs - every MFMA accumulator.
+// That instruction is an identity here: an MFMA produces no signalling NaN, and the kernels run with ieee_mode 1 and f32
+// denormals on, so it neither quiets nor flushes anything.  The IEEE-754-2019 maximum needs no canonical operands and is ONE
+// v_maximum3_f32 v, x, y, y on gfx950, visible to the scheduler and the hazard recogniser (an asm v_max_f32 is not: hipcc
+// pads it with s_nop).  maximum and maxnum differ only where exactly one operand is NaN or the operands are zeros of opposite
+// sign; y = 0.01 x is NaN exactly when x is and has the sign of x, so neither happens: same bits for every x, NaN stays NaN.
+__device__ __forceinline__ float lrelu_max(float x, float y) { return __builtin_elementwise_maximum(x, y); }
+__device__ __forceinline__ float lrelu01(float x) { return lrelu_max(x, 0.01f * x); }
 
 // All LDS addresses in the hot loops are (one per-lane base register) + (compile-time immediate): the per-lane
 // parts are made opaque so that hipcc neither re-associates them into hundreds of distinct hoisted address
