@@ -277,6 +277,65 @@ int surs_encoder_forward(const SursEncoderNet *net, const float *image, int h, i
                          float *im_feat_lr, float *im_feat_hr, void *workspace, size_t workspace_bytes,
                          const SursEncoderStreams *streams, void *stream);
 
+/* ------------------------------------------------------------------ super-resolution gradients
+ * The backward of super_resolution.* (SuRSSR_v3, lib/model/SuRSSR_v3.py:143-181) and of image_filter_hr.conv5
+ * (lib/model/HGFilters.py:179-181): csrc/surs_sr_grad.hip (primitives) and csrc/surs_encoder_net.cpp (the network).  Every product
+ * is an fp32-input MFMA with fp32 accumulation, whatever --precision says; no float atomics; two calls give the same bits wherever
+ * the buffers, the workspace and the tape lie.  All maps are NHWC fp32 with a channel pitch; weights and their gradients are
+ * DEVICE memory in the PLAIN torch layout [cout][cin][k][k], biases [cout].
+ *
+ * The activation derivative is taken from the STORED OUTPUT y of the layer while the gradient operand is read:
+ *   dZ[p][co] = g[p][co] * (y[p][co] > 0 ? 1 : slope)      (y == NULL: dZ = g)
+ * slope 0.2f: LeakyReLU(0.2); 0: ReLU; y == 0 and y == -0 take the negative side, as torch's in-place activations do.
+ *
+ * surs_conv_grad_weight: a k x k convolution (k = 1, or 3 with padding 1; stride 1, or 2 with k = 3) of x [h][w][cin] to [ho][wo][cout]:
+ *   dw[co][ci][ky][kx] = sum_p dZ[p][co] x[p stride + (ky, kx) - pad][ci],   db[co] = sum_p dZ[p][co]   (db nullable)
+ * Order of the sums: the output pixels p = oy wo + ox are cut into parts of 1024 consecutive pixels (parts = ceil(ho wo / 1024)); a
+ * part is summed in steps of 16 pixels on the matrix unit, each part's result goes to its own slab of the workspace, and a second
+ * kernel adds slab 0, 1, 2, ... in this order.  accumulate = 1: the result is added to what dw / db hold (the next image of a batch),
+ * 0: it replaces it.  The bias gradient is one more column of the same product.
+ * surs_conv_grad_input: the same convolution's  dx[q][ci] = sum_{ky, kx, co} dZ[(q + pad - (ky, kx)) / stride][co] w[co][ci][ky][kx]
+ * over the output pixels that exist (stride 2: where the division is exact), summed per element in the order (ky, kx, co);
+ * add = 1: added to what dx holds (the gradient of another consumer of the same map), 0: it replaces it.
+ * surs_pixel_unshuffle2_grad: conv -> LeakyReLU -> PixelShuffle(2) -> LeakyReLU stores only the shuffled map y [2h][2w][c] (the forward
+ * fuses the second LeakyReLU into surs_pixel_shuffle2); g is the gradient of y, dz [h][w][4c] the gradient of the convolution's result:
+ *   dz[i][j][4 ch + 2 dy + dx] = g[2i + dy][2j + dx][ch] * (y[2i + dy][2j + dx][ch] > 0 ? 1 : slope),   slope = 0.2f * 0.2f here. */
+size_t surs_conv_grad_weight_workspace_bytes(int ho, int wo, int cin, int cout, int ksize);   /* 0: bad arguments */
+int surs_conv_grad_weight(const float *g, int ho, int wo, int cout, int g_ld, const float *y, int y_ld, float slope, const float *x,
+                          int h, int w, int cin, int x_ld, int ksize, int stride, float *dw, float *db, int accumulate,
+                          void *workspace, size_t workspace_bytes, void *stream);
+int surs_conv_grad_input(const float *g, int ho, int wo, int cout, int g_ld, const float *y, int y_ld, float slope, const float *weight,
+                         int cin, int ksize, int stride, float *dx, int h, int w, int dx_ld, int add, void *stream);
+int surs_pixel_unshuffle2_grad(const float *g, int h, int w, int c, int g_ld, const float *y, int y_ld, float slope, float *dz, int dz_ld,
+                               void *stream);
+
+/* The plain fp32 parameters (or their gradients) of the super-resolution convolutions and conv5, in SursEncoderNet's order; HOST
+ * struct of DEVICE pointers: weight [cout][cin][k][k], bias [cout]. */
+typedef struct SursSrParam { float *weight, *bias; } SursSrParam;
+typedef struct SursSrParams {
+    SursSrParam head, down[3], tail0[3], tail2[3], bottleneck, bott2, ups2, ups3, ups4, last0, last2;
+    const SursSrParam *body;   /* [2 * (n_block[0] + n_block[1] + n_block[2])]: body{i}.{b}.body.0, .body.2 */
+    SursSrParam conv5;
+} SursSrParams;
+/* bytes of the tape / of the backward's workspace for an h x w input image: functions of the net and the size alone (0: refused) */
+size_t surs_encoder_sr_tape_bytes(const SursEncoderNet *net, int h, int w);
+size_t surs_encoder_sr_backward_workspace_bytes(const SursEncoderNet *net, int h, int w);
+/* surs_encoder_super_res(want_image = 1) followed by surs_encoder_filter_hr - the same kernels, tiles and operand split, the same bits
+ * in img_sr [sh][sw][3], feature_lr [sh/4][sw/4][256], feature_hr [sh][sw][64], im_feat_hr [sh][sw][conv5.cout] (all dense) -, with
+ * every map a backward step reads kept in `tape` (256-byte aligned device memory; one buffer per layer where the forward rotates
+ * three).  net->parts must be 2: training runs the fp32-grade forward. */
+int surs_encoder_super_res_train(const SursEncoderNet *net, const float *x, int h, int w, int x_ld, float *img_sr, float *feature_lr,
+                                 float *feature_hr, float *im_feat_hr, void *tape, size_t tape_bytes, void *stream);
+/* The gradients of L = <g_img_sr, img_sr> + <g_feature_lr, feature_lr> + <g_im_feat_hr, im_feat_hr> with respect to every parameter
+ * of `params` (the weights the forward ran with, plain layout), from the tape of surs_encoder_super_res_train on an h x w image.
+ * g_* are dense NHWC maps of the outputs' shapes, nullable: a missing one counts as zero and the layers only it reaches cost nothing
+ * (their gradients are zero); all three missing is SURS_E_INVALID.  accumulate = 1 adds to what `grads` holds.  One stream, launches
+ * in a fixed order: last.2, last.0, conv5, ups4, ups3, ups2, bott2, bottleneck, then stage 3, 2, 1 (tail.2, tail.0, the blocks
+ * from the last to the first, down), head; the input gradient of head and of the bicubic enlargement is never formed. */
+int surs_encoder_super_res_backward(const SursEncoderNet *net, const SursSrParams *params, const void *tape, int h, int w,
+                                    const float *g_img_sr, const float *g_feature_lr, const float *g_im_feat_hr, const SursSrParams *grads,
+                                    int accumulate, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ point evaluator */
 
 /* HOST: pack the two SurfaceClassifier MLPs (lr: 321-1024-512-256-128-1, hr: 322-..., skip-concat at layers

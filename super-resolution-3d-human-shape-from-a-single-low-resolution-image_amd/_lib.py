@@ -80,6 +80,18 @@ NORM_GROUP, NORM_BATCH = 0, 1             # SursEncoderNet.norm
 SR_SCALE_MIN, SR_SCALE_MAX = 1, 4         # SursEncoderNet.sr_scale / surs_bicubic_up
 
 
+class SrParam(C.Structure):
+    """SursSrParam of include/surs.h: one convolution's plain fp32 weight [cout][cin][k][k] and bias [cout] on the device."""
+    _fields_ = [("weight", C.c_void_p), ("bias", C.c_void_p)]
+
+
+class SrParamsStruct(C.Structure):
+    """SursSrParams of include/surs.h: the super-resolution convolutions and conv5 in SursEncoderNet's order."""
+    _fields_ = [("head", SrParam), ("down", SrParam * 3), ("tail0", SrParam * 3), ("tail2", SrParam * 3), ("bottleneck", SrParam),
+                ("bott2", SrParam), ("ups2", SrParam), ("ups3", SrParam), ("ups4", SrParam), ("last0", SrParam), ("last2", SrParam),
+                ("body", C.POINTER(SrParam)), ("conv5", SrParam)]
+
+
 class EncoderStreams(C.Structure):
     _fields_ = [("side", C.c_void_p * 4)]
 
@@ -144,6 +156,15 @@ _SIGS = {
     "surs_encoder_filter_lr": (C.c_int, [C.POINTER(EncoderNet), _vp, _i, _i, _i, C.POINTER(_vp), _vp, _sz, C.POINTER(EncoderStreams), _vp]),
     "surs_encoder_filter_hr": (C.c_int, [C.POINTER(EncoderNet), _vp, _i, _i, _i, _vp, _vp]),
     "surs_encoder_forward": (C.c_int, [C.POINTER(EncoderNet), _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, C.POINTER(EncoderStreams), _vp]),
+    "surs_conv_grad_weight_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "surs_conv_grad_weight": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _i, _f, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _sz, _vp]),
+    "surs_conv_grad_input": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _i, _f, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp]),
+    "surs_pixel_unshuffle2_grad": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _i, _f, _vp, _i, _vp]),
+    "surs_encoder_sr_tape_bytes": (_sz, [C.POINTER(EncoderNet), _i, _i]),
+    "surs_encoder_sr_backward_workspace_bytes": (_sz, [C.POINTER(EncoderNet), _i, _i]),
+    "surs_encoder_super_res_train": (C.c_int, [C.POINTER(EncoderNet), _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "surs_encoder_super_res_backward": (C.c_int, [C.POINTER(EncoderNet), C.POINTER(SrParamsStruct), _vp, _i, _i, _vp, _vp, _vp,
+                                                  C.POINTER(SrParamsStruct), _i, _vp, _sz, _vp]),
     "surs_mlp_pack": (_sz, [_vp, _vp, _vp, _vp, _i, _vp]),
     "surs_mlp_pack_generic": (_sz, [_shp, _vp, _vp, _shp, _vp, _vp, _vp]),
     "surs_mlp_generic_info": (C.c_int, [_shp, _shp, C.POINTER(C.c_int), C.POINTER(C.c_int), _vp]),

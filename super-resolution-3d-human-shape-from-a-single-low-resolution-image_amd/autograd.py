@@ -41,3 +41,45 @@ def point_loss(net, feat_lr_list, feat_hr, points_mr, points_sr, calibs, labels_
     feat_lr_list = list(feat_lr_list)
     return _PointLoss.apply(net, len(feat_lr_list), points_mr, points_sr, calibs, labels_lr, labels_hr, transforms, *feat_lr_list,
                             feat_hr)
+
+
+class _SuperResFeatures(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, net, images_lr, *params):
+        img_SR, feature_lr, _ = net.super_res_train(images_lr)
+        ctx.net, ctx.tapes, ctx.n_params = net, net._sr_tapes, len(params)
+        ctx.set_materialize_grads(False)   # an output nothing differentiates arrives as None, not as a map of zeros
+        out = (img_SR, feature_lr, net.im_feat_list_hr[0])
+        # (fresh tensors for autograd to own: the model keeps its NHWC views)
+        return tuple(o.clone() for o in out)
+
+    @staticmethod
+    def backward(ctx, g_img, g_lr, g_hr):
+        net = ctx.net
+        if g_img is None and g_lr is None and g_hr is None:
+            return (None,) * (2 + ctx.n_params)
+        kept, net._sr_tapes = net._sr_tapes, ctx.tapes   # the tapes of THIS forward, whatever ran on the net since
+        try:
+            grads = net.super_res_backward(g_img, g_lr, g_hr)
+        finally:
+            net._sr_tapes = kept
+        return (None, None) + tuple(grads.values())
+
+
+def super_res_features(net, images_lr, params=None):
+    """(img_SR, feature_lr, feat_hr) of SuRSNet `net` on images_lr [B,3,H,W] - super_res_train()'s values, feat_hr =
+    im_feat_list_hr[0] -, each with a grad_fn: their backward is net.super_res_backward() with whatever gradients arrive (an output
+    that receives none costs nothing) and hands every entry of `params` - default net.sr_parameters() - its gradient.  So
+        img_SR, feature_lr, feat_hr = autograd.super_res_features(net, images_lr)
+        loss = autograd.point_loss(net, torch_hg_filter(feature_lr), feat_hr, ...) + srweight * l1_loss(img_SR, images_hr)
+        loss.backward()
+    trains the super-resolution network on this package, the hourglass being a torch module with a backward of its own.
+    The VALUES are those of the weights the net has LOADED, not of `params`: after an optimiser step on sr_parameters(), call
+    net.load_state_dict() with the updated values before the next forward (as the classifier example of INTEGRATION.md does).
+    Nothing else in the package grows a graph: forward()'s error.grad_fn stays None."""
+    if params is None:
+        params = net.sr_parameters()
+    keys = list(net.sr_parameters())
+    if list(params) != keys:
+        raise ValueError("params must hold net.sr_parameters()'s keys in their order")
+    return _SuperResFeatures.apply(net, images_lr, *params.values())

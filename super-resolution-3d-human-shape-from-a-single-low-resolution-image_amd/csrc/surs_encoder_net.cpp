@@ -612,3 +612,371 @@ extern "C" int surs_encoder_forward(const SursEncoderNet *net, const float *imag
     outs[net->num_stack - 1] = im_feat_lr;
     return surs_encoder_filter_lr(net, feature_lr, eh / 4, ew / 4, 256, outs, workspace, workspace_bytes, streams, stream);
 }
+
+// ---------------------------------------------------------------- super-resolution gradients (include/surs.h)
+// surs_encoder_super_res_train is super_res() + conv5 on ONE buffer per layer (the tape); surs_encoder_super_res_backward walks the
+// same maps in reverse on the primitives of surs_sr_grad.hip.  Both lay the tape out with sr_tape_maps(): the map addresses are a
+// function of the net and the image size alone.
+#include <vector>
+
+namespace {
+
+struct SrStage {
+    std::vector<Map> a, t;   // a[0]: down's output, a[b + 1]: block b's output; t[b]: block b's inner map (ReLU)
+    Map u;                   // tail.0's output
+};
+struct SrTape {
+    Map up, fin, new3, new2, new1, new_fin, t_last, shuffle_in;
+    SrStage st[3];
+};
+
+void sr_tape_maps(Run &r, int H2, int W2, SrTape &m) {
+    const SursEncoderNet &n = *r.net;
+    m.up = r.map(H2, W2, 3);
+    m.fin = r.map(H2, W2, 64);                 // cat(h, up3)
+    m.new3 = r.map(H2 / 2, W2 / 2, 128);       // cat(d1_f, up2)
+    m.new2 = r.map(H2 / 4, W2 / 4, 256);       // cat(d2_f, up1) = feature_lr
+    m.new1 = r.map(H2 / 8, W2 / 8, 512);       // cat(d3_f, bo)
+    m.new_fin = r.map(H2, W2, 64);             // feature_hr
+    m.t_last = r.map(H2, W2, n.last0.cout);
+    m.shuffle_in = r.map(H2 / 2, W2 / 2, 128); // the convolution in front of a shuffle (ups3's is the largest); nothing reads it back
+    int hs = H2, ws = W2;
+    for (int i = 0; i < 3; ++i) {
+        hs = (hs + 2 - 3) / 2 + 1; ws = (ws + 2 - 3) / 2 + 1;
+        const int c = n.down[i].cout, nb = n.residual ? n.n_block[i] : 0;
+        SrStage &s = m.st[i];
+        s.a.clear(); s.t.clear();
+        s.a.push_back(r.map(hs, ws, c));
+        for (int b = 0; b < nb; ++b) {
+            s.t.push_back(r.map(hs, ws, c));
+            s.a.push_back(r.map(hs, ws, c));
+        }
+        s.u = r.map(hs, ws, c);
+    }
+}
+
+inline const SursConv *sr_body(const SursEncoderNet &n, int stage, int b, int which) {
+    int b0 = 0;
+    for (int i = 0; i < stage; ++i) b0 += n.n_block[i];
+    return &n.body[2 * (b0 + b) + which];
+}
+inline const SursSrParam *sr_body(const SursEncoderNet &n, const SursSrParams *p, int stage, int b, int which) {
+    int b0 = 0;
+    for (int i = 0; i < stage; ++i) b0 += n.n_block[i];
+    return &p->body[2 * (b0 + b) + which];
+}
+
+// the shapes the backward's fixed channel slices rest on (the released SuRSSR_v3; the forward's cat() buffers assume the same)
+int check_sr_shapes(const SursEncoderNet *n) {
+    auto is = [](const SursConv &c, int cin, int cout, int k) { return c.cin == cin && c.cout == cout && c.ksize == k; };
+    bool ok = is(n->head, 3, 32, 3) && is(n->down[0], 32, 32, 3) && is(n->down[1], 64, 64, 3) && is(n->down[2], 128, 128, 3) &&
+              is(n->bottleneck, 256, 256, 3) && is(n->bott2, 512, 512, 3) && is(n->ups2, 256, 256, 3) && is(n->ups3, 128, 128, 3) &&
+              is(n->ups4, 64, 64, 3) && n->last0.cin == 64 && n->last0.ksize == 3 && n->last2.cin == n->last0.cout && n->last2.cout == 3 &&
+              n->last2.ksize == 3 && n->conv5.cin == 64 && n->conv5.ksize == 1 && n->conv5.cout >= 1;
+    for (int i = 0; i < 3 && ok; ++i) {
+        const int c = n->down[i].cout;
+        ok = is(n->tail0[i], c, c, 3) && is(n->tail2[i], c, 2 * c, 3);
+        for (int b = 0; ok && n->residual && b < n->n_block[i]; ++b) ok = n->body && is(*sr_body(*n, i, b, 0), c, c, 3) && is(*sr_body(*n, i, b, 1), c, c, 3);
+    }
+    SURS_REQUIRE(ok, "super-resolution gradients: the convolutions are not SuRSSR_v3's (head 3-32, stages of 32, 64, 128 channels, bott2 512-512, ...)");
+    return 0;
+}
+
+int check_sr_train(const SursEncoderNet *net, int h, int w) {
+    if (int rc = check_net(net)) return rc;
+    SURS_REQUIRE(net->parts == 2, "super-resolution gradients: net->parts == 1 (the bf16 / f16 encoder) has no backward: training runs the "
+                                  "fp32-grade forward (parts == 2)");
+    if (int rc = check_sr_shapes(net)) return rc;
+    return check_image_size(net, h, w);
+}
+
+void sr_train_forward(Run &r, const Map &x, SrTape &m, float *img_sr, float *im_feat_hr) {
+    const SursEncoderNet &n = *r.net;
+    if (sr_scale(&n) == 2) bicubic_up2(r, x, false, nullptr, m.up, false);
+    else bicubic_up(r, x, sr_scale(&n), m.up);
+    Map h = m.fin.slice(0, 32);
+    conv(r, m.up, n.head, h, 1, ACT, LRELU, nullptr);
+    auto stage = [&](int i, const Map &src, Map dst) {
+        SrStage &s = m.st[i];
+        conv(r, src, n.down[i], s.a[0], 2, ACT, LRELU, nullptr);
+        const int nb = (int)s.t.size();
+        for (int b = 0; b < nb; ++b) {
+            conv(r, s.a[b], *sr_body(n, i, b, 0), s.t[b], 1, ACT, RELU, nullptr);
+            conv(r, s.t[b], *sr_body(n, i, b, 1), s.a[b + 1], 1, 0, 0.0f, &s.a[b]);
+        }
+        conv(r, s.a[nb], n.tail0[i], s.u, 1, ACT, LRELU, nullptr);
+        conv(r, s.u, n.tail2[i], dst, 1, ACT, LRELU, nullptr);
+        return dst;
+    };
+    Map d1_f = stage(0, h, m.new3.slice(0, 64));
+    Map d2_f = stage(1, d1_f, m.new2.slice(0, 128));
+    Map d3_f = stage(2, d2_f, m.new1.slice(0, 256));
+    Map bo = m.new1.slice(256, 256);
+    conv(r, d3_f, n.bottleneck, bo, 1, ACT, LRELU, nullptr);
+    auto shuffle = [&](const Map &src, const SursConv &cw, Map dst) {
+        Map t = m.shuffle_in;
+        t.h = src.h; t.w = src.w; t.c = t.ld = cw.cout;
+        conv(r, src, cw, t, 1, ACT, LRELU, nullptr);
+        pixel_shuffle2(r, t, 0.2f, dst);
+    };
+    shuffle(m.new1, n.bott2, m.new2.slice(128, 128));
+    shuffle(m.new2, n.ups2, m.new3.slice(64, 64));
+    shuffle(m.new3, n.ups3, m.fin.slice(32, 32));
+    conv(r, m.fin, n.ups4, m.new_fin, 1, ACT, LRELU, nullptr);
+    Map o;
+    o.p = img_sr; o.h = m.fin.h; o.w = m.fin.w; o.c = o.ld = 3;
+    conv(r, m.new_fin, n.last0, m.t_last, 1, ACT, LRELU, nullptr);
+    conv(r, m.t_last, n.last2, o, 1, 0, 0.0f, nullptr);
+    Map f;
+    f.p = im_feat_hr; f.h = m.fin.h; f.w = m.fin.w; f.c = f.ld = n.conv5.cout;
+    conv(r, m.new_fin, n.conv5, f, 1, 0, 0.0f, nullptr);
+}
+
+size_t sr_wgrad_bytes(const Map &out, const SursConv &cw) { return surs_conv_grad_weight_workspace_bytes(out.h, out.w, cw.cin, cw.cout, cw.ksize); }
+
+struct SrBack {
+    Run &r;
+    const SursSrParams *P, *G;
+    int acc;
+    void *wws = nullptr;        // the weight gradient's slabs
+    size_t wws_bytes = 0, wws_need = 0;
+
+    // dW, db of the convolution x -> (pre-activation of) y from g = d L / d y
+    void wgrad(const Map &g, const Map *y, float slope, const Map &x, const SursConv &cw, int stride, const SursSrParam &gp) {
+        const size_t need = sr_wgrad_bytes(g, cw);
+        if (need > wws_need) wws_need = need;
+        if (r.dry || r.rc) return;
+        r.fail(surs_conv_grad_weight(g.p, g.h, g.w, cw.cout, g.ld, y ? y->p : nullptr, y ? y->ld : 0, slope, x.p, x.h, x.w, cw.cin, x.ld, cw.ksize,
+                                     stride, gp.weight, gp.bias, acc, wws, wws_bytes, r.st));
+    }
+    void dgrad(const Map &g, const Map *y, float slope, const SursConv &cw, const SursSrParam &p, int stride, const Map &dx, bool add) {
+        if (r.dry || r.rc) return;
+        r.fail(surs_conv_grad_input(g.p, g.h, g.w, cw.cout, g.ld, y ? y->p : nullptr, y ? y->ld : 0, slope, p.weight, cw.cin, cw.ksize, stride,
+                                    dx.p, dx.h, dx.w, dx.ld, add ? 1 : 0, r.st));
+    }
+    // a layer no gradient reaches: its gradient is zero (accumulate: nothing to add)
+    void zero(const SursConv &cw, const SursSrParam &gp) {
+        if (r.dry || r.rc || acc) return;
+        if (hipMemsetAsync(gp.weight, 0, sizeof(float) * cw.cout * cw.cin * cw.ksize * cw.ksize, r.st) != hipSuccess ||
+            (gp.bias && hipMemsetAsync(gp.bias, 0, sizeof(float) * cw.cout, r.st) != hipSuccess))
+            r.fail(fail(SURS_E_HIP, "super-resolution gradients: hipMemsetAsync failed"));
+    }
+    void copy(const float *src, const Map &dst) {   // dense map -> dense map
+        if (r.dry || r.rc) return;
+        if (hipMemcpyAsync(dst.p, src, sizeof(float) * dst.h * dst.w * dst.c, hipMemcpyDeviceToDevice, r.st) != hipSuccess)
+            r.fail(fail(SURS_E_HIP, "super-resolution gradients: hipMemcpyAsync failed"));
+    }
+};
+
+constexpr float LRELU2 = 0.2f * 0.2f;   // LeakyReLU(LeakyReLU(z)) below zero
+
+// r.a: the workspace arena (the gradient maps, then the weight gradient's slabs)
+void sr_backward(SrBack &k, const SrTape &m, const float *g_img, const float *g_lr, const float *g_hr) {
+    Run &r = k.r;
+    const SursEncoderNet &n = *r.net;
+    const int H2 = m.fin.h, W2 = m.fin.w;
+    Map g_newfin = r.map(H2, W2, 64), g_tlast = r.map(H2, W2, n.last0.cout), g_fin = r.map(H2, W2, 64);
+    Map g_new3 = r.map(H2 / 2, W2 / 2, 128), g_new2 = r.map(H2 / 4, W2 / 4, 256), g_new1 = r.map(H2 / 8, W2 / 8, 512);
+    Map dzt = r.map(H2 / 2, W2 / 2, 128);   // the gradient in front of a shuffle (ups3's is the largest)
+    Map pq[2] = {r.map(H2 / 2, W2 / 2, 32), r.map(H2 / 2, W2 / 2, 32)};   // the two gradient maps a stage alternates between
+    {   // the slabs: the largest any layer needs (a dry pass over the same calls below finds it)
+        SrBack d{r, k.P, k.G, k.acc};
+        const bool was_dry = r.dry;
+        r.dry = true;
+        auto need = [&](int hh, int ww, const SursConv &cw) {
+            Map o; o.h = hh; o.w = ww;
+            const size_t b = sr_wgrad_bytes(o, cw);
+            if (b > d.wws_need) d.wws_need = b;
+        };
+        need(H2, W2, n.last2); need(H2, W2, n.last0); need(H2, W2, n.conv5); need(H2, W2, n.ups4); need(H2, W2, n.head);
+        need(H2 / 2, W2 / 2, n.ups3); need(H2 / 4, W2 / 4, n.ups2); need(H2 / 8, W2 / 8, n.bott2); need(H2 / 8, W2 / 8, n.bottleneck);
+        for (int i = 0; i < 3; ++i) {
+            need(m.st[i].u.h, m.st[i].u.w, n.down[i]);
+            need(m.st[i].u.h, m.st[i].u.w, n.tail0[i]);   // (the blocks: the same shape)
+            need(m.st[i].u.h, m.st[i].u.w, n.tail2[i]);
+        }
+        r.dry = was_dry;
+        k.wws_bytes = d.wws_need;
+        k.wws = r.a->take(k.wws_bytes);
+    }
+    if (r.dry || r.rc || !r.a->ok()) return;
+
+    const bool top = g_img || g_hr;   // does any gradient reach feature_hr?
+    if (g_img) {
+        Map gi; gi.p = const_cast<float *>(g_img); gi.h = H2; gi.w = W2; gi.c = gi.ld = 3;
+        k.wgrad(gi, nullptr, 1.0f, m.t_last, n.last2, 1, k.G->last2);
+        k.dgrad(gi, nullptr, 1.0f, n.last2, k.P->last2, 1, g_tlast, false);
+        k.wgrad(g_tlast, &m.t_last, LRELU, m.new_fin, n.last0, 1, k.G->last0);
+        k.dgrad(g_tlast, &m.t_last, LRELU, n.last0, k.P->last0, 1, g_newfin, false);
+    } else {
+        k.zero(n.last2, k.G->last2);
+        k.zero(n.last0, k.G->last0);
+    }
+    if (g_hr) {
+        Map gh; gh.p = const_cast<float *>(g_hr); gh.h = H2; gh.w = W2; gh.c = gh.ld = n.conv5.cout;
+        k.wgrad(gh, nullptr, 1.0f, m.new_fin, n.conv5, 1, k.G->conv5);
+        k.dgrad(gh, nullptr, 1.0f, n.conv5, k.P->conv5, 1, g_newfin, g_img != nullptr);
+    } else {
+        k.zero(n.conv5, k.G->conv5);
+    }
+    // a shuffle level: g of the shuffled slice `o` (stored output `y`) -> the convolution cw on src; the gradient of src replaces g_src
+    auto unshuffle = [&](const Map &g_o, const Map &y, const Map &src, const SursConv &cw, const SursSrParam &p, const SursSrParam &gp,
+                         const Map &g_src) {
+        Map t = dzt;
+        t.h = src.h; t.w = src.w; t.c = t.ld = cw.cout;
+        if (!r.rc) r.fail(surs_pixel_unshuffle2_grad(g_o.p, t.h, t.w, g_o.c, g_o.ld, y.p, y.ld, LRELU2, t.p, t.ld, r.st));
+        k.wgrad(t, nullptr, 1.0f, src, cw, 1, gp);
+        k.dgrad(t, nullptr, 1.0f, cw, p, 1, g_src, false);
+    };
+    if (top) {
+        k.wgrad(g_newfin, &m.new_fin, LRELU, m.fin, n.ups4, 1, k.G->ups4);
+        k.dgrad(g_newfin, &m.new_fin, LRELU, n.ups4, k.P->ups4, 1, g_fin, false);
+        unshuffle(g_fin.slice(32, 32), m.fin.slice(32, 32), m.new3, n.ups3, k.P->ups3, k.G->ups3, g_new3);
+        unshuffle(g_new3.slice(64, 64), m.new3.slice(64, 64), m.new2, n.ups2, k.P->ups2, k.G->ups2, g_new2);
+        if (g_lr) {   // feature_lr's own gradient joins the one that came down through ups2
+            Map gl; gl.p = const_cast<float *>(g_lr); gl.h = g_new2.h; gl.w = g_new2.w; gl.c = gl.ld = 256;
+            if (!r.rc) r.fail(surs_add3(g_new2.p, g_new2.ld, gl.p, gl.ld, nullptr, 0, g_new2.h * g_new2.w, 256, g_new2.p, g_new2.ld, r.st));
+        }
+    } else {
+        k.zero(n.ups4, k.G->ups4);
+        k.zero(n.ups3, k.G->ups3);
+        k.zero(n.ups2, k.G->ups2);
+        k.copy(g_lr, g_new2);
+    }
+    unshuffle(g_new2.slice(128, 128), m.new2.slice(128, 128), m.new1, n.bott2, k.P->bott2, k.G->bott2, g_new1);
+    {
+        Map g_bo = g_new1.slice(256, 256), bo = m.new1.slice(256, 256), d3_f = m.new1.slice(0, 256);
+        k.wgrad(g_bo, &bo, LRELU, d3_f, n.bottleneck, 1, k.G->bottleneck);
+        k.dgrad(g_bo, &bo, LRELU, n.bottleneck, k.P->bottleneck, 1, g_new1.slice(0, 256), true);
+    }
+    // a stage in reverse: g_dst = d L / d dst (all consumers added), its input's gradient is added to (or, live == false, replaces) g_src
+    auto stage = [&](int i, const Map &src, const Map &dst, const Map &g_dst, const Map &g_src, bool live) {
+        const SrStage &s = m.st[i];
+        const int nb = (int)s.t.size();
+        Map P = pq[0], Q = pq[1];
+        P.h = Q.h = s.u.h; P.w = Q.w = s.u.w; P.c = P.ld = Q.c = Q.ld = s.u.c;
+        k.wgrad(g_dst, &dst, LRELU, s.u, n.tail2[i], 1, k.G->tail2[i]);
+        k.dgrad(g_dst, &dst, LRELU, n.tail2[i], k.P->tail2[i], 1, P, false);
+        k.wgrad(P, &s.u, LRELU, s.a[nb], n.tail0[i], 1, k.G->tail0[i]);
+        k.dgrad(P, &s.u, LRELU, n.tail0[i], k.P->tail0[i], 1, Q, false);
+        for (int b = nb - 1; b >= 0; --b) {   // a[b + 1] = body.2(relu(body.0(a[b]))) + a[b];  Q = d L / d a[b + 1] -> d L / d a[b]
+            const SursConv &c0 = *sr_body(n, i, b, 0), &c2 = *sr_body(n, i, b, 1);
+            k.wgrad(Q, nullptr, 1.0f, s.t[b], c2, 1, *sr_body(n, k.G, i, b, 1));
+            k.dgrad(Q, nullptr, 1.0f, c2, *sr_body(n, k.P, i, b, 1), 1, P, false);
+            k.wgrad(P, &s.t[b], RELU, s.a[b], c0, 1, *sr_body(n, k.G, i, b, 0));
+            k.dgrad(P, &s.t[b], RELU, c0, *sr_body(n, k.P, i, b, 0), 1, Q, true);
+        }
+        k.wgrad(Q, &s.a[0], LRELU, src, n.down[i], 2, k.G->down[i]);
+        if (g_src.p) k.dgrad(Q, &s.a[0], LRELU, n.down[i], k.P->down[i], 2, g_src, live);
+        if (!n.residual)
+            for (int b = 0; b < n.n_block[i]; ++b) {   // blocks the forward does not run
+                k.zero(*sr_body(n, i, b, 0), *sr_body(n, k.G, i, b, 0));
+                k.zero(*sr_body(n, i, b, 1), *sr_body(n, k.G, i, b, 1));
+            }
+    };
+    stage(2, m.new2.slice(0, 128), m.new1.slice(0, 256), g_new1.slice(0, 256), g_new2.slice(0, 128), true);
+    stage(1, m.new3.slice(0, 64), m.new2.slice(0, 128), g_new2.slice(0, 128), g_new3.slice(0, 64), top);
+    stage(0, m.fin.slice(0, 32), m.new3.slice(0, 64), g_new3.slice(0, 64), g_fin.slice(0, 32), top);
+    Map h = m.fin.slice(0, 32);
+    k.wgrad(g_fin.slice(0, 32), &h, LRELU, m.up, n.head, 1, k.G->head);
+}
+
+size_t sr_tape_need(const SursEncoderNet *net, int eh, int ew) {
+    Arena d;
+    d.dry = true;
+    Run rd{net, &d, nullptr, net->parts, true};
+    SrTape m;
+    sr_tape_maps(rd, eh, ew, m);
+    return align_up(d.peak, 256);
+}
+
+size_t sr_backward_need(const SursEncoderNet *net, int eh, int ew) {
+    Arena t, d;
+    t.dry = d.dry = true;
+    Run rt{net, &t, nullptr, net->parts, true};
+    SrTape m;
+    sr_tape_maps(rt, eh, ew, m);
+    Run rd{net, &d, nullptr, net->parts, true};
+    SrBack k{rd, nullptr, nullptr, 0};
+    sr_backward(k, m, nullptr, nullptr, nullptr);
+    return align_up(d.peak, 256) + 256;
+}
+
+bool sr_params_filled(const SursEncoderNet *n, const SursSrParams *p) {
+    auto ok = [](const SursSrParam &q) { return q.weight && q.bias; };
+    bool all = ok(p->head) && ok(p->bottleneck) && ok(p->bott2) && ok(p->ups2) && ok(p->ups3) && ok(p->ups4) && ok(p->last0) && ok(p->last2) &&
+               ok(p->conv5);
+    int nb = 0;
+    for (int i = 0; i < 3; ++i) {
+        all = all && ok(p->down[i]) && ok(p->tail0[i]) && ok(p->tail2[i]);
+        nb += n->n_block[i];
+    }
+    if (nb && !p->body) return false;
+    for (int b = 0; b < 2 * nb; ++b) all = all && ok(p->body[b]);
+    return all;
+}
+
+}  // namespace
+
+extern "C" size_t surs_encoder_sr_tape_bytes(const SursEncoderNet *net, int h, int w) {
+    if (!net || check_sr_train(net, h, w)) return 0;
+    return sr_tape_need(net, sr_scale(net) * h, sr_scale(net) * w);
+}
+
+extern "C" size_t surs_encoder_sr_backward_workspace_bytes(const SursEncoderNet *net, int h, int w) {
+    if (!net || check_sr_train(net, h, w)) return 0;
+    return sr_backward_need(net, sr_scale(net) * h, sr_scale(net) * w);
+}
+
+extern "C" int surs_encoder_super_res_train(const SursEncoderNet *net, const float *x, int h, int w, int x_ld, float *img_sr,
+                                            float *feature_lr, float *feature_hr, float *im_feat_hr, void *tape, size_t tape_bytes,
+                                            void *stream) {
+    SURS_REQUIRE(net, "null network");
+    if (int rc = check_sr_train(net, h, w)) return rc;
+    SURS_REQUIRE(x && img_sr && feature_lr && feature_hr && im_feat_hr && tape, "super_res_train: null argument");
+    SURS_REQUIRE(x_ld >= 3, "input image: three channels");
+    SURS_REQUIRE(((size_t)tape & 255) == 0, "super_res_train: the tape must be 256-byte aligned");
+    const int eh = sr_scale(net) * h, ew = sr_scale(net) * w;
+    const size_t need = sr_tape_need(net, eh, ew);
+    SURS_REQUIRE(need <= tape_bytes, "super_res_train: tape too small: %zu bytes needed", need);
+    Arena a;
+    a.base = (char *)tape;
+    a.cap = tape_bytes;
+    Run r{net, &a, as_stream(stream), net->parts, false};
+    SrTape m;
+    sr_tape_maps(r, eh, ew, m);
+    sr_train_forward(r, input_map(x, h, w, 3, x_ld), m, img_sr, im_feat_hr);
+    if (r.rc) return r.rc;
+    SURS_HIP_CHECK(hipMemcpyAsync(feature_lr, m.new2.p, sizeof(float) * m.new2.h * m.new2.w * 256, hipMemcpyDeviceToDevice, r.st));
+    SURS_HIP_CHECK(hipMemcpyAsync(feature_hr, m.new_fin.p, sizeof(float) * m.new_fin.h * m.new_fin.w * 64, hipMemcpyDeviceToDevice, r.st));
+    return 0;
+}
+
+extern "C" int surs_encoder_super_res_backward(const SursEncoderNet *net, const SursSrParams *params, const void *tape, int h, int w,
+                                               const float *g_img_sr, const float *g_feature_lr, const float *g_im_feat_hr,
+                                               const SursSrParams *grads, int accumulate, void *workspace, size_t workspace_bytes,
+                                               void *stream) {
+    SURS_REQUIRE(net, "null network");
+    if (int rc = check_sr_train(net, h, w)) return rc;
+    SURS_REQUIRE(params && grads && tape && workspace, "super_res_backward: null argument");
+    SURS_REQUIRE(g_img_sr || g_feature_lr || g_im_feat_hr, "super_res_backward: no upstream gradient (all three are NULL)");
+    SURS_REQUIRE(sr_params_filled(net, params) && sr_params_filled(net, grads), "super_res_backward: a null weight or bias pointer in params / grads");
+    SURS_REQUIRE(((size_t)tape & 255) == 0, "super_res_backward: the tape must be 256-byte aligned");
+    const int eh = sr_scale(net) * h, ew = sr_scale(net) * w;
+    Arena t;
+    t.base = (char *)const_cast<void *>(tape);
+    t.cap = sr_tape_need(net, eh, ew);
+    Run rt{net, &t, nullptr, net->parts, false};
+    SrTape m;
+    sr_tape_maps(rt, eh, ew, m);
+    Arena a;
+    a.base = (char *)align_up((size_t)workspace, 256);
+    const size_t lead = (size_t)(a.base - (char *)workspace);
+    const size_t need = sr_backward_need(net, eh, ew);
+    SURS_REQUIRE(need - 256 + lead <= workspace_bytes, "super_res_backward: workspace too small: %zu bytes needed", need);
+    a.cap = workspace_bytes - lead;
+    Run r{net, &a, as_stream(stream), net->parts, false};
+    SrBack k{r, params, grads, accumulate ? 1 : 0};
+    sr_backward(k, m, g_img_sr, g_feature_lr, g_im_feat_hr);
+    return r.rc;
+}

@@ -12,8 +12,11 @@ no autograd graph and no optimiser and no CPU path: methods raise without a GPU 
 VALIDATION forward: every kept stack's predictions and the reference's loss, without an autograd graph (SuRSNet.py:240-266).
 The one part of the backward pass that exists is the classifiers': forward_backward() / classifier_grads() return d error / d (every
 mlp_lr.* and mlp_hr.* parameter) and, with features=True, d error / d (the feature maps of im_feat_list_lr and im_feat_list_hr[0])
-(native.mlp_grads) - where an encoder's backward starts; autograd.point_loss hands them to torch autograd.  The encoder's and the
-super-resolution network's own parameter gradients are out of scope.
+(native.mlp_grads) - where an encoder's backward starts; autograd.point_loss hands them to torch autograd.  The super-resolution
+network and image_filter_hr.conv5 have a backward too: super_res_train() keeps the forward's maps, super_res_backward() returns the
+gradients of every super_resolution.* convolution and conv5 from the gradients of img_SR, feature_lr and im_feat_list_hr[0]
+(native.sr_backward), sr_parameters() are the fp32 weights it reads, autograd.super_res_features is the torch.autograd.Function over
+them.  The hourglass (image_filter_lr.*) has no backward here: its parameter gradients are out of scope.
 
 Encoder options: --norm group | batch and --scale 1..4 (anything else: ValueError at construction).  --norm batch is nn.BatchNorm2d in
 EVAL mode - y = (x - running_mean) / sqrt(running_var + 1e-5) * weight + bias, always from the running statistics: train() here keeps
@@ -84,6 +87,9 @@ class SuRSNet:
         self._sr_args = None
         self._grad_params = None      # native.MlpParams: the device copy of the fp32 classifier weights (dropped like the blob)
         self._grad_ws = None
+        self._sr_params = None        # native.SrParams + sr_parameters()'s OrderedDict: the plain fp32 super-resolution weights (dropped alike)
+        self._sr_tapes = None         # what super_res_train() left for super_res_backward(): (h, w, [one tape per image])
+        self._sr_ws = None
         self.last_classifier_grads = None   # what autograd.point_loss last left: classifier_grads()'s OrderedDict
         self._feat_cache = None
         self._stack_feat_cache = None
@@ -104,6 +110,7 @@ class SuRSNet:
                 encoder.drop_graphs(self._enc)
             self._enc = self._blob = None
             self._grad_params = self._grad_ws = None
+            self._sr_params = self._sr_tapes = self._sr_ws = None
         return self
 
     def cuda(self, index=None):
@@ -147,6 +154,7 @@ class SuRSNet:
             encoder.drop_graphs(self._enc)
         self._enc = self._blob = None
         self._grad_params = None
+        self._sr_params = None
         return self
 
     # ------------------------------------------------------------------ lazily packed device state
@@ -220,6 +228,86 @@ class SuRSNet:
         self.im_feat_list_hr = [torch.cat([_as_nchw_view(pv[0]) for pv in per_view], 0) if len(per_view) > 1
                                 else _as_nchw_view(per_view[0][0])]
         self._hr_from = self.im_feat_list_hr[0].data_ptr() if (self._sr_out and images.data_ptr() == self._sr_out[1]) else None
+
+    # ------------------------------------------------------------------ super-resolution gradients
+    def _sr_native(self):
+        W = self._encoder_weights()
+        if W.reduced:
+            raise RuntimeError("super-resolution gradients: --encoder_precision f16 (net->parts == 1) has no backward: training runs "
+                               "the fp32-grade forward")
+        return encoder._native_net(W).net, W.scale
+
+    def _sr_param_set(self):
+        if self._sr_params is None:
+            p = native.SrParams(self._sd, self.opt.n_block, self._device())
+            self._sr_params = (p, OrderedDict((k, torch.nn.Parameter(v)) for k, v in p.tensors.items()))
+        return self._sr_params
+
+    def sr_parameters(self):
+        """The cached OrderedDict of torch.nn.Parameter over the plain fp32 device copies of every super_resolution.* convolution and
+        image_filter_hr.conv5 (state_dict() order, no sub_mean / add_mean): the tensors super_res_backward() reads, what an optimiser
+        steps and autograd.super_res_features hands gradients to.  The FORWARD runs on the packed weights of load_state_dict(): after
+        an optimiser step, load_state_dict() the updated values (which drops this cache, as it drops the classifiers')."""
+        return self._sr_param_set()[1]
+
+    def super_res_train(self, images):
+        """super_res(images) followed by filter_hr(feature_hr) - the same kernels and bits in im_SR, feature_lr, feature_hr and
+        im_feat_list_hr - with every map the backward reads kept on this object, one tape per image of the batch
+        (surs_encoder_super_res_train).  Returns (img_SR, feature_lr, feature_hr) as super_res() does."""
+        net, scale = self._sr_native()
+        self._last_images = images
+        self._sharded_encode = None
+        outs, tapes = [], []
+        for v in range(images.shape[0]):
+            x = _as_img(images[v:v + 1])
+            encoder.check_image_size(x.h, x.w, scale)
+            *o, tape = native.sr_train_forward(net, x, scale)
+            outs.append(o)
+            tapes.append(tape)
+        cat = lambda i: torch.cat([_as_nchw_view(o[i]) for o in outs], 0) if len(outs) > 1 else _as_nchw_view(outs[0][i])
+        self.im_SR, self.feature_lr, self.feature_hr = cat(0), cat(1), cat(2)
+        self._sr_out = (self.feature_lr.data_ptr(), self.feature_hr.data_ptr())
+        self._lr_from = None
+        self._feat_hr_imgs = [[o[3] for o in outs]]
+        self.im_feat_list_hr = [cat(3)]
+        self._hr_from = self.im_feat_list_hr[0].data_ptr()
+        self._sr_tapes = (images.shape[2], images.shape[3], tapes)
+        return self.im_SR, self.feature_lr, self.feature_hr
+
+    def super_res_backward(self, grad_img_SR=None, grad_feature_lr=None, grad_feat_hr=None):
+        """The gradients of <grad_img_SR, img_SR> + <grad_feature_lr, feature_lr> + <grad_feat_hr, im_feat_list_hr[0]> with respect to
+        every super_resolution.* convolution and image_filter_hr.conv5 (surs_encoder_super_res_backward), from the tapes of the
+        preceding super_res_train().  The arguments are NCHW tensors of those outputs' shapes, or None (zero; at least one is
+        needed).  Returns an OrderedDict in state_dict() order (sr_parameters()'s keys): float32 device tensors of the parameters'
+        shapes, summed over the images of the batch.  fp32 matrix products whatever --precision says, deterministic.  The gradient of
+        feature_lr through image_filter_lr (the hourglass) is not part of this: whoever owns that network supplies
+        grad_feature_lr."""
+        if self._sr_tapes is None:
+            raise RuntimeError("super_res_backward needs a preceding super_res_train(): the tape of the forward's maps is missing")
+        net, scale = self._sr_native()
+        params = self._sr_param_set()[0]
+        h, w, tapes = self._sr_tapes
+        dev, B = self._device(), len(tapes)
+        H2, W2 = scale * h, scale * w
+        shapes = ((B, 3, H2, W2), (B, 256, H2 // 4, W2 // 4), (B, net.conv5.cout, H2, W2))
+        gs = []
+        for name, g, shape in zip(("grad_img_SR", "grad_feature_lr", "grad_feat_hr"), (grad_img_SR, grad_feature_lr, grad_feat_hr), shapes):
+            if g is None:
+                gs.append(None)
+                continue
+            if tuple(g.shape) != shape:
+                raise ValueError("%s %s against the output's %s" % (name, tuple(g.shape), shape))
+            gs.append(g.detach().to(dev, torch.float32).permute(0, 2, 3, 1).contiguous())
+        if all(g is None for g in gs):
+            raise ValueError("super_res_backward: no upstream gradient (all three are None)")
+        need = native.sr_backward_workspace_bytes(net, h, w)
+        if self._sr_ws is None or self._sr_ws.numel() < need or self._sr_ws.device != dev:
+            self._sr_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        grads = None
+        for b in range(B):
+            grads = native.sr_backward(net, params, tapes[b], h, w, *[None if g is None else g[b] for g in gs], grads=grads,
+                                       accumulate=b > 0, workspace=self._sr_ws, scale=scale)
+        return grads
 
     def reencode_wide(self):
         """Runs the encoder again on the images of the last super_res() call with every fp32-grade product on three bf16 parts
@@ -765,7 +853,9 @@ class SuRSNet:
         state_dict() order, float32 device tensors of the parameters' shapes.  features=True: (res_hr, error, res_lr, grads,
         feat_grads) with classifier_grads(features=True)'s feat_grads and feat_grads["img_SR"] = opt.srweight sign(img_SR -
         images_hr) / numel (torch's L1 backward, 0 at equality) - everything the loss hands back to the encoder.  Out of scope:
-        gradients for the encoder / super-resolution parameters themselves; num_views == 1 and orthogonal projection only."""
+        the parameter gradients of the hourglass (image_filter_lr.*), and this call is NOT extended by those of the super-resolution
+        network (super_res_train() / super_res_backward(), autograd.super_res_features): a gradient that silently lacked the path
+        feature_lr -> filter_lr -> points would be a trap; num_views == 1 and orthogonal projection only."""
         if self.num_views != 1 or self.projection_mode != "orthogonal":
             raise NotImplementedError(self._GRADS_LIMIT)
         res_hr, error, res_lr = self.forward(images_lr, images_hr, points_lr, points_hr, calibs, transforms=transforms,

@@ -1089,6 +1089,218 @@ def mlp_grads(points_mr, points_sr, calib_mr, calib_sr, zmul, zdiv, feats_lr, fe
     return out if len(out) > 1 else out[0]
 
 
+# ------------------------------------------------------------------ super-resolution gradients
+
+def conv_grad_weight_workspace_bytes(ho, wo, cin, cout, ksize):
+    """surs_conv_grad_weight_workspace_bytes: ceil(ho wo / 1024) slabs of [cout][k k cin + 1] floats."""
+    n = lib().surs_conv_grad_weight_workspace_bytes(ho, wo, cin, cout, ksize)
+    if n == 0:
+        raise ValueError("surs_conv_grad_weight_workspace_bytes refused %dx%d, %d -> %d, k = %d" % (ho, wo, cin, cout, ksize))
+    return n
+
+
+def _mask_args(g, y):
+    if y is None:
+        return None, 0
+    if (y.h, y.w, y.c) != (g.h, g.w, g.c):
+        raise ValueError("the stored output %s must have the gradient's shape %s" % ((y.h, y.w, y.c), (g.h, g.w, g.c)))
+    return y.ptr(), y.ld
+
+
+def conv_grad_weight(g, x, ksize, stride=1, y=None, slope=1.0, dw=None, db=None, accumulate=False, workspace=None):
+    """surs_conv_grad_weight: (dw [cout,cin,k,k], db [cout]) of the k x k convolution (padding k // 2) that took Img x to an Img of g's
+    shape, from g = d L / d (its stored output y); y None: g is the gradient of the convolution's own result.  slope: what the
+    activation's derivative is where y <= 0 (0.2 LeakyReLU, 0 ReLU).  accumulate adds to the given dw / db."""
+    dev = g.buf.device
+    if dw is None:
+        if accumulate:
+            raise ValueError("accumulate needs the dw / db to add to")
+        dw = torch.empty((g.c, x.c, ksize, ksize), dtype=torch.float32, device=dev)
+        db = torch.empty((g.c,), dtype=torch.float32, device=dev)
+    elif tuple(dw.shape) != (g.c, x.c, ksize, ksize) or not dw.is_contiguous() or dw.dtype != torch.float32 or \
+            (db is not None and (db.numel() != g.c or not db.is_contiguous() or db.dtype != torch.float32)):
+        raise ValueError("dw must be a contiguous float32 %s, db %s" % ((g.c, x.c, ksize, ksize), (g.c,)))
+    yp, yld = _mask_args(g, y)
+    if workspace is None:
+        workspace = torch.empty(conv_grad_weight_workspace_bytes(g.h, g.w, x.c, g.c, ksize) // 4, dtype=torch.float32, device=dev)
+    check(lib().surs_conv_grad_weight(g.ptr(), g.h, g.w, g.c, g.ld, yp, yld, float(slope), x.ptr(), x.h, x.w, x.c, x.ld, ksize, stride,
+                                      _ptr(dw), _ptr(db), 1 if accumulate else 0, _ptr(workspace),
+                                      workspace.numel() * workspace.element_size(), _stream()))
+    return dw, db
+
+
+def conv_grad_input(g, weight, h, w, stride=1, y=None, slope=1.0, dx=None, add=False):
+    """surs_conv_grad_input: Img dx [h,w,cin] = d L / d (the convolution's input) from g (as conv_grad_weight) and the plain weight
+    [cout,cin,k,k] (device).  add: added to what the given dx holds."""
+    weight = _f32c(weight)
+    cout, cin, k, _ = weight.shape
+    if cout != g.c:
+        raise ValueError("weight %s against a gradient of %d channels" % (tuple(weight.shape), g.c))
+    if dx is None:
+        if add:
+            raise ValueError("add needs the dx to add to")
+        dx = Img(h, w, cin, device=g.buf.device)
+    elif (dx.h, dx.w, dx.c) != (h, w, cin):
+        raise ValueError("dx %s against %s" % ((dx.h, dx.w, dx.c), (h, w, cin)))
+    yp, yld = _mask_args(g, y)
+    check(lib().surs_conv_grad_input(g.ptr(), g.h, g.w, g.c, g.ld, yp, yld, float(slope), _ptr(weight), cin, k, stride, dx.ptr(), h, w,
+                                     dx.ld, 1 if add else 0, _stream()))
+    return dx
+
+
+def pixel_unshuffle2_grad(g, y, slope, out=None):
+    """surs_pixel_unshuffle2_grad: g, y Img [2h,2w,c] (the gradient of the shuffled map and the map itself) -> Img [h,w,4c], the
+    gradient in front of conv -> LeakyReLU -> PixelShuffle(2) -> LeakyReLU's first LeakyReLU (slope = 0.2f * 0.2f there)."""
+    if (y.h, y.w, y.c) != (g.h, g.w, g.c) or g.h % 2 or g.w % 2:
+        raise ValueError("pixel_unshuffle2_grad: g %s / y %s must be one even-sized shape" % ((g.h, g.w, g.c), (y.h, y.w, y.c)))
+    if out is None:
+        out = Img(g.h // 2, g.w // 2, 4 * g.c, device=g.buf.device)
+    check(lib().surs_pixel_unshuffle2_grad(g.ptr(), g.h // 2, g.w // 2, g.c, g.ld, y.ptr(), y.ld, float(slope), out.ptr(), out.ld, _stream()))
+    return out
+
+
+def sr_conv_names(n_block):
+    """The super-resolution convolutions in SursEncoderNet's order, as (field, index, state-dict module name)."""
+    names = [("head", None, "head.0")]
+    names += [("down", i, "down%d.0" % (i + 1)) for i in range(3)]
+    names += [("tail0", i, "tail%d.0" % (i + 1)) for i in range(3)]
+    names += [("tail2", i, "tail%d.2" % (i + 1)) for i in range(3)]
+    names += [(f, None, k) for f, k in (("bottleneck", "bottleneck.0"), ("bott2", "bott2.0"), ("ups2", "ups2.0"), ("ups3", "ups3.0"),
+                                        ("ups4", "ups4.0"), ("last0", "last.0"), ("last2", "last.2"))]
+    j = 0
+    for i, nb in enumerate(n_block):
+        for b in range(nb):
+            for part in (0, 2):
+                names.append(("body", j, "body%d.%d.body.%d" % (i + 1, b, part)))
+                j += 1
+    return names
+
+
+def sr_param_keys(sd, n_block):
+    """The state-dict keys super_res_backward returns gradients for, in sd's order: every super_resolution.* convolution (not the
+    sub_mean / add_mean the forward never runs) and image_filter_hr.conv5."""
+    mods = {"super_resolution." + k for _, _, k in sr_conv_names(n_block)} | {"image_filter_hr.conv5"}
+    return [k for k in sd if k.rsplit(".", 1)[0] in mods and k.rsplit(".", 1)[1] in ("weight", "bias")]
+
+
+class SrParams:
+    """The plain fp32 weights [cout,cin,k,k] and biases [cout] of the super-resolution convolutions and conv5 on the device: what
+    surs_encoder_super_res_backward reads (the forward runs on PACKED copies of the same values)."""
+
+    def __init__(self, sd, n_block, device):
+        self.n_block = [int(v) for v in n_block]
+        self.keys = sr_param_keys(sd, self.n_block)
+        self.tensors = OrderedDict()
+        for k in self.keys:
+            v = sd[k]
+            v = v.detach() if torch.is_tensor(v) else torch.from_numpy(np.asarray(v, np.float32))
+            self.tensors[k] = v.to(device, torch.float32).contiguous()
+        want = 2 * (len(sr_conv_names(self.n_block)) + 1)
+        if len(self.keys) != want:
+            raise ValueError("the state dict holds %d of the %d super-resolution / conv5 parameters" % (len(self.keys), want))
+
+    def struct(self, tensors=None):
+        """SursSrParams of `tensors` (default: the parameters themselves; else an OrderedDict of gradients with the same keys).
+        Returns (struct, keep-alive)."""
+        t = self.tensors if tensors is None else tensors
+        s = _lib.SrParamsStruct()
+        n_body = max(1, 2 * sum(self.n_block))
+        body = (_lib.SrParam * n_body)()
+        for field, i, name in sr_conv_names(self.n_block):
+            p = _lib.SrParam(t["super_resolution.%s.weight" % name].data_ptr(), t["super_resolution.%s.bias" % name].data_ptr())
+            if field == "body":
+                body[i] = p
+            elif i is None:
+                setattr(s, field, p)
+            else:
+                getattr(s, field)[i] = p
+        s.body = body
+        s.conv5 = _lib.SrParam(t["image_filter_hr.conv5.weight"].data_ptr(), t["image_filter_hr.conv5.bias"].data_ptr())
+        return s, body
+
+
+def _sr_size(fn, what, net, h, w):
+    n = fn(C.byref(net), h, w)
+    if n == 0:
+        raise ValueError("%s refused a %dx%d image: %s" % (what, h, w, lib().surs_last_error().decode()))
+    return n
+
+
+def sr_tape_bytes(net, h, w):
+    """surs_encoder_sr_tape_bytes: the tape of sr_train_forward for an h x w input image (net: _lib.EncoderNet)."""
+    return _sr_size(lib().surs_encoder_sr_tape_bytes, "surs_encoder_sr_tape_bytes", net, h, w)
+
+
+def sr_backward_workspace_bytes(net, h, w):
+    """surs_encoder_sr_backward_workspace_bytes."""
+    return _sr_size(lib().surs_encoder_sr_backward_workspace_bytes, "surs_encoder_sr_backward_workspace_bytes", net, h, w)
+
+
+def sr_scale(net):
+    """--scale as the library reads it off a _lib.EncoderNet: sr_scale with ENC_EXTENDED in flags, else 2."""
+    return int(net.sr_scale) if (net.flags & _lib.ENC_EXTENDED) and net.sr_scale else 2
+
+
+def sr_train_forward(net, x, scale=None, tape=None):
+    """surs_encoder_super_res_train: super_res(want_image) + filter_hr of Img x [h,w,3] with every map the backward reads kept in `tape`
+    (a uint8 / float32 device tensor of sr_tape_bytes, 256-byte aligned; None: a new one).  Returns (img_sr, feature_lr, feature_hr,
+    im_feat_hr, tape) - the four as Img, bit for bit those of the two calls."""
+    dev = x.buf.device
+    need = sr_tape_bytes(net, x.h, x.w)
+    if tape is None:
+        tape = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif tape.numel() * tape.element_size() < need or tape.device != dev:
+        raise ValueError("tape: %d bytes needed on %s" % (need, dev))
+    if scale not in (None, sr_scale(net)):
+        raise ValueError("scale %r against the net's %d" % (scale, sr_scale(net)))
+    H2, W2 = sr_scale(net) * x.h, sr_scale(net) * x.w
+    img_sr, f_lr, f_hr = Img(H2, W2, 3, device=dev), Img(H2 // 4, W2 // 4, 256, device=dev), Img(H2, W2, 64, device=dev)
+    im_hr = Img(H2, W2, net.conv5.cout, device=dev)
+    check(lib().surs_encoder_super_res_train(C.byref(net), x.ptr(), x.h, x.w, x.ld, img_sr.ptr(), f_lr.ptr(), f_hr.ptr(), im_hr.ptr(),
+                                             _ptr(tape), tape.numel() * tape.element_size(), _stream()))
+    return img_sr, f_lr, f_hr, im_hr, tape
+
+
+def sr_backward(net, params, tape, h, w, g_img_sr=None, g_feature_lr=None, g_im_feat_hr=None, grads=None, accumulate=False,
+                workspace=None, scale=None):
+    """surs_encoder_super_res_backward for ONE image: the gradients of <g_img_sr, img_sr> + <g_feature_lr, feature_lr> + <g_im_feat_hr,
+    im_feat_hr> with respect to every parameter of SrParams `params`, from the tape sr_train_forward left for the h x w input image.
+    g_*: contiguous float32 NHWC device tensors of the outputs' shapes, or None (zero).  grads: an OrderedDict as returned, to
+    overwrite or (accumulate) add to; None: a new one.  Returns grads: params.keys in order, tensors of the parameters' shapes."""
+    dev = tape.device
+    if accumulate and grads is None:
+        raise ValueError("accumulate needs the grads to add to")
+    if grads is None:
+        grads = OrderedDict((k, torch.empty_like(v)) for k, v in params.tensors.items())
+    else:
+        for k, v in params.tensors.items():
+            if k not in grads or tuple(grads[k].shape) != tuple(v.shape) or grads[k].dtype != torch.float32 \
+                    or not grads[k].is_contiguous() or grads[k].device != dev:
+                raise ValueError("grads[%r] must be a contiguous float32 tensor %s on %s" % (k, tuple(v.shape), dev))
+    if scale not in (None, sr_scale(net)):
+        raise ValueError("scale %r against the net's %d" % (scale, sr_scale(net)))
+    H2, W2 = sr_scale(net) * h, sr_scale(net) * w
+    for name, g, shape in (("g_img_sr", g_img_sr, (H2, W2, 3)), ("g_feature_lr", g_feature_lr, (H2 // 4, W2 // 4, 256)),
+                           ("g_im_feat_hr", g_im_feat_hr, (H2, W2, net.conv5.cout))):
+        if g is not None and (tuple(g.shape[-3:]) != shape or g.numel() != shape[0] * shape[1] * shape[2] or g.dtype != torch.float32
+                              or not g.is_contiguous() or g.device != dev):
+            raise ValueError("%s must be a contiguous float32 NHWC tensor %s on %s, not %s" % (name, shape, dev, tuple(g.shape)))
+    if tape.numel() * tape.element_size() < sr_tape_bytes(net, h, w):
+        raise ValueError("tape: %d bytes needed for a %dx%d image" % (sr_tape_bytes(net, h, w), h, w))
+    need = sr_backward_workspace_bytes(net, h, w)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif workspace.numel() * workspace.element_size() < need or workspace.device != dev:
+        raise ValueError("workspace: %d bytes needed on %s" % (need, dev))
+    ps, keep_p = params.struct()
+    gs, keep_g = params.struct(grads)
+    check(lib().surs_encoder_super_res_backward(C.byref(net), C.byref(ps), _ptr(tape), h, w, _ptr(g_img_sr), _ptr(g_feature_lr),
+                                                _ptr(g_im_feat_hr), C.byref(gs), 1 if accumulate else 0, _ptr(workspace),
+                                                workspace.numel() * workspace.element_size(), _stream()))
+    del keep_p, keep_g
+    return grads
+
+
 def query_points_views(points, calibs, projection, zmul, zdiv, feat_lr, feat_hr, blob, ws, want_logits=False):
     """Multi-view / perspective query.  points [V,3,N] f32 device tensor; calibs [V,12] (host); feat_lr [V,hl,wl,256] and
     feat_hr [V,hh,wh,64] contiguous NHWC device tensors; projection 'orthogonal' | 'perspective'.
