@@ -336,6 +336,77 @@ int surs_encoder_super_res_backward(const SursEncoderNet *net, const SursSrParam
                                     const float *g_img_sr, const float *g_feature_lr, const float *g_im_feat_hr, const SursSrParams *grads,
                                     int accumulate, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ hourglass gradients
+ * The backward of image_filter_lr's ConvBlock (lib/model/HGFilters.py:29-74, in_planes == out_planes == 256: every block of the
+ * low-resolution filter) and of its HourGlass module m{s} (:76-120): csrc/surs_hg_grad.hip (primitives) and
+ * csrc/surs_encoder_net.cpp (the modules).  --norm group and net->parts == 2 only.  The rules of the super-resolution gradients
+ * hold: fp32 with fp32 accumulation, no float atomics, two calls give the same bits wherever buffers, workspace and tape lie, NHWC
+ * maps with a channel pitch (here: multiples of 4, 16-byte aligned pixels - every access is 16 bytes), parameters and their
+ * gradients in the plain torch layout.  The stack's tail (conv_last, bn_end, l, bl, al) is not part of this.
+ *
+ * surs_groupnorm_fold: the four vectors of a GroupNorm(32) site - mean[32], rstd[32] (per group) and scale[c] = rstd gamma,
+ * shift[c] = beta - mean rstd gamma (per channel) - from the statistics the producer of the map left (stats, the in-kernel fold of
+ * the convolutions restated: the same formulas in double, the same order, the same float results) or, stats == NULL, from the map x
+ * [hw][c] itself (surs_groupnorm_coeffs_ws' two launches, whose partial sums - scratch: surs_groupnorm_scratch_bytes() - a third
+ * folds into mean and rstd in the order its second launch uses).  gamma is never divided by.
+ *
+ * surs_groupnorm_relu_grad: out = relu(z), z = x * scale + shift = GroupNorm32(x; gamma, beta); g = d L / d out, c = 64, 128 or 256.
+ *   gy = g where z > 0 else 0 (z recomputed from x and the forward's scale / shift in the convolutions' staging expression, a
+ *   multiply and an add: the forward's own mask; z == 0 and -0 take the negative side), xh = (x - mean) rstd, m = hw c / 32,
+ *   dbeta[c] = sum_p gy,  dgamma[c] = sum_p gy xh,  s1[grp] = sum_{c in grp} gamma dbeta,  s2[grp] = sum_{c in grp} gamma dgamma,
+ *   dx = rstd (gy gamma - s1 / m - xh s2 / m)      add = 1: added to what dx holds; accumulate = 1: dgamma / dbeta are added to.
+ * Order of the sums: the pixels are cut into parts of 64 consecutive pixels; inside a part a channel's pixels are summed by
+ * 1024 / c lanes, lane l taking pixels l, l + 1024 / c, ... in order, and the lanes are added in lane order; the parts are added in
+ * the order 0, 1, 2, ...; s1 and s2 add the group's channels in channel order.  Two passes over g and x: one reads them for the
+ * sums, one reads them again and writes dx.
+ *
+ * surs_avgpool2_grad: g [h][w][c] -> dx [2h][2w][c] (+)= 0.25 g[y / 2][x / 2], the transpose of surs_avgpool2.
+ * surs_bicubic_up2_grad: g [2h][2w][c] -> dx [h][w][c], the transpose of surs_bicubic_up2(align_corners = 1) with the forward's own
+ * fp32 coordinate and coefficient expressions (A = -0.75, border-clamped taps; the clamped taps of one output coordinate that fall
+ * on one source pixel add their weights in tap order): dx[sy][sx] (+)= sum_oy Wy(oy, sy) (sum_ox Wx(ox, sx) g[oy][ox]), gathered
+ * per element with oy ascending and, inside a row, ox ascending. */
+int surs_groupnorm_fold(const SursGnStats *stats, const float *x, int hw, int c, int x_ld, float eps, const float *gamma,
+                        const float *beta, float *mean, float *rstd, float *scale, float *shift, void *scratch, void *stream);
+size_t surs_groupnorm_relu_grad_workspace_bytes(int hw, int c);   /* 0: bad arguments */
+int surs_groupnorm_relu_grad(const float *g, int g_ld, const float *x, int x_ld, int hw, int c, const float *mean, const float *rstd,
+                             const float *scale, const float *shift, const float *gamma, float *dx, int dx_ld, int add, float *dgamma,
+                             float *dbeta, int accumulate, void *workspace, size_t workspace_bytes, void *stream);
+int surs_avgpool2_grad(const float *g, int h, int w, int c, int g_ld, float *dx, int dx_ld, int add, void *stream);
+int surs_bicubic_up2_grad(const float *g, int h, int w, int c, int g_ld, float *dx, int dx_ld, int add, void *stream);
+
+/* The plain fp32 parameters (or their gradients) of one ConvBlock, mirroring SursConvBlock; HOST struct of DEVICE pointers:
+ * weight[k] = conv{k+1}.weight [cout][cin][3][3] (256 -> 128, 128 -> 64, 64 -> 64; no bias), gamma[k] / beta[k] = bn{k+1}.weight / .bias. */
+typedef struct SursHgBlockParams { float *weight[3], *gamma[3], *beta[3]; } SursHgBlockParams;
+/* bytes of the tape / of the backward's workspace of one block, and of one stack's hourglass (net->hg_depth levels), on an h x w
+ * map: functions of the net and the size alone; 0: refused (h or w not a multiple of 2^hg_depth for the hourglass, --norm batch,
+ * parts == 1). */
+size_t surs_encoder_convblock_tape_bytes(const SursEncoderNet *net, int h, int w);
+size_t surs_encoder_convblock_backward_workspace_bytes(const SursEncoderNet *net, int h, int w);
+size_t surs_encoder_hourglass_tape_bytes(const SursEncoderNet *net, int h, int w);
+size_t surs_encoder_hourglass_backward_workspace_bytes(const SursEncoderNet *net, int h, int w);
+/* The forward of `block` (any ConvBlock of the net: conv2, hg[i], top_m[s]) / of stack `stack`'s hourglass on x [h][w][256] (pitch
+ * ld; it carries no statistics) into out [h][w][256] (dense): the launches of the inference forward in its separate-sum form (the
+ * host mirror's; the hourglass on ONE stream) plus one surs_groupnorm_fold per norm site, the same bits.  The tape (256-byte aligned)
+ * keeps, per block, the input, the raw cat(o1, o2, o3) - the closing sum writes a map of its own - and the four vectors of its
+ * three norm sites; the joins of a level (average pool, bicubic + sum) are linear and need nothing. */
+int surs_encoder_convblock_train(const SursEncoderNet *net, const SursConvBlock *block, const float *x, int h, int w, int ld, float *out,
+                                 void *tape, size_t tape_bytes, void *stream);
+int surs_encoder_hourglass_train(const SursEncoderNet *net, int stack, const float *x, int h, int w, int ld, float *out, void *tape,
+                                 size_t tape_bytes, void *stream);
+/* g = d L / d out (dense [h][w][256]) -> dx = d L / d x (dense, always produced) and the gradients of the module's parameters
+ * (params / grads: one SursHgBlockParams for a block, 3 hg_depth + 1 in the stack's module order for an hourglass); accumulate = 1
+ * adds to what grads holds.  One stream, launches in a fixed order.  A block: dx = g (the identity path); then for conv3, conv2,
+ * conv1 in this order: relu(norm(input)) is materialised (surs_scale_shift_act), surs_conv_grad_weight, surs_conv_grad_input,
+ * surs_groupnorm_relu_grad ADDED to the gradient of the map that norm read (slice [128, 192), slice [0, 128) of g's copy, dx).  A
+ * level of the hourglass: b1 (into the level input's gradient), the bicubic transpose, b3, the level below (or b2_plus), b2, the
+ * pool transpose ADDED onto the level input's gradient. */
+int surs_encoder_convblock_backward(const SursEncoderNet *net, const SursConvBlock *block, const SursHgBlockParams *params, const void *tape,
+                                    int h, int w, const float *g, float *dx, const SursHgBlockParams *grads, int accumulate,
+                                    void *workspace, size_t workspace_bytes, void *stream);
+int surs_encoder_hourglass_backward(const SursEncoderNet *net, int stack, const SursHgBlockParams *params, const void *tape, int h, int w,
+                                    const float *g, float *dx, const SursHgBlockParams *grads, int accumulate, void *workspace,
+                                    size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ point evaluator */
 
 /* HOST: pack the two SurfaceClassifier MLPs (lr: 321-1024-512-256-128-1, hr: 322-..., skip-concat at layers

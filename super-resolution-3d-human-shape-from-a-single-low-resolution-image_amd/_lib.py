@@ -92,6 +92,11 @@ class SrParamsStruct(C.Structure):
                 ("body", C.POINTER(SrParam)), ("conv5", SrParam)]
 
 
+class HgBlockParams(C.Structure):
+    """SursHgBlockParams of include/surs.h: one ConvBlock's plain fp32 conv{1,2,3}.weight and bn{1,2,3}.weight / .bias on the device."""
+    _fields_ = [("weight", C.c_void_p * 3), ("gamma", C.c_void_p * 3), ("beta", C.c_void_p * 3)]
+
+
 class EncoderStreams(C.Structure):
     _fields_ = [("side", C.c_void_p * 4)]
 
@@ -165,6 +170,21 @@ _SIGS = {
     "surs_encoder_super_res_train": (C.c_int, [C.POINTER(EncoderNet), _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "surs_encoder_super_res_backward": (C.c_int, [C.POINTER(EncoderNet), C.POINTER(SrParamsStruct), _vp, _i, _i, _vp, _vp, _vp,
                                                   C.POINTER(SrParamsStruct), _i, _vp, _sz, _vp]),
+    "surs_groupnorm_fold": (C.c_int, [C.POINTER(GnStats), _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "surs_groupnorm_relu_grad_workspace_bytes": (_sz, [_i, _i]),
+    "surs_groupnorm_relu_grad": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _sz, _vp]),
+    "surs_avgpool2_grad": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "surs_bicubic_up2_grad": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "surs_encoder_convblock_tape_bytes": (_sz, [C.POINTER(EncoderNet), _i, _i]),
+    "surs_encoder_convblock_backward_workspace_bytes": (_sz, [C.POINTER(EncoderNet), _i, _i]),
+    "surs_encoder_hourglass_tape_bytes": (_sz, [C.POINTER(EncoderNet), _i, _i]),
+    "surs_encoder_hourglass_backward_workspace_bytes": (_sz, [C.POINTER(EncoderNet), _i, _i]),
+    "surs_encoder_convblock_train": (C.c_int, [C.POINTER(EncoderNet), C.POINTER(ConvBlock), _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "surs_encoder_hourglass_train": (C.c_int, [C.POINTER(EncoderNet), _i, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "surs_encoder_convblock_backward": (C.c_int, [C.POINTER(EncoderNet), C.POINTER(ConvBlock), C.POINTER(HgBlockParams), _vp, _i, _i, _vp,
+                                                  _vp, C.POINTER(HgBlockParams), _i, _vp, _sz, _vp]),
+    "surs_encoder_hourglass_backward": (C.c_int, [C.POINTER(EncoderNet), _i, C.POINTER(HgBlockParams), _vp, _i, _i, _vp, _vp,
+                                                  C.POINTER(HgBlockParams), _i, _vp, _sz, _vp]),
     "surs_mlp_pack": (_sz, [_vp, _vp, _vp, _vp, _i, _vp]),
     "surs_mlp_pack_generic": (_sz, [_shp, _vp, _vp, _shp, _vp, _vp, _vp]),
     "surs_mlp_generic_info": (C.c_int, [_shp, _shp, C.POINTER(C.c_int), C.POINTER(C.c_int), _vp]),

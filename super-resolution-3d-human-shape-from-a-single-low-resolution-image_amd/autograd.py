@@ -1,6 +1,7 @@
 """The point path as a torch.autograd.Function: gather, both classifiers on every kept stack and the three classifier terms of
 SuRSNet.forward's loss, differentiable with respect to the feature maps.  An encoder that has a backward of its own - a torch encoder
-under autograd - trains against this library's point evaluator through it.  Nothing else in the package grows an autograd graph."""
+under autograd - trains against this library's point evaluator through it.  super_res_features, conv_block and hourglass are the
+Functions over the parts of the encoder that have a backward here; nothing else in the package grows an autograd graph."""
 import torch
 
 from . import native
@@ -83,3 +84,57 @@ def super_res_features(net, images_lr, params=None):
     if list(params) != keys:
         raise ValueError("params must hold net.sr_parameters()'s keys in their order")
     return _SuperResFeatures.apply(net, images_lr, *params.values())
+
+
+class _HgModule(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, net, which, keys, x, *params):
+        hourglass = isinstance(which, int)
+        out = net.hourglass_train(which, x) if hourglass else net.conv_block_train(which, x)
+        key = which   # (an hourglass is filed under its stack, a block under its full prefix: net._hg_train)
+        ctx.net, ctx.which, ctx.keys, ctx.key, ctx.tapes = net, which, keys, key, net._hg_tapes[key]
+        return out.clone()   # (a fresh tensor for autograd to own)
+
+    @staticmethod
+    def backward(ctx, g):
+        net = ctx.net
+        kept = net._hg_tapes.get(ctx.key)
+        net._hg_tapes[ctx.key] = ctx.tapes   # the tapes of THIS forward, whatever ran on the net since
+        try:
+            fn = net.hourglass_backward if isinstance(ctx.which, int) else net.conv_block_backward
+            dx, grads = fn(ctx.which, g)
+        finally:
+            if kept is None:
+                del net._hg_tapes[ctx.key]
+            else:
+                net._hg_tapes[ctx.key] = kept
+        return (None, None, None, dx) + tuple(grads[k] for k in ctx.keys)
+
+
+def _hg_apply(net, which, prefixes, x, params):
+    from . import native
+    own = net.hg_parameters()
+    keys = [k for p in prefixes for k in native.hg_block_keys(p)]
+    if params is None:
+        params = own
+    missing = [k for k in keys if k not in params]
+    if missing:
+        raise ValueError("params lacks %s" % missing[:3])
+    return _HgModule.apply(net, which, keys, x, *[params[k] for k in keys])
+
+
+def conv_block(net, prefix, x, params=None):
+    """ConvBlock `prefix` of image_filter_lr (conv2. / top_m_{s}. / m{s}.b1_{l}. ...) of SuRSNet `net` on x [B,256,h,w], with a grad_fn:
+    its backward is net.conv_block_backward() and hands x its gradient and the block's nine entries of `params` - default
+    net.hg_parameters() - theirs, summed over the batch in image order.  The VALUES are those of the weights the net has LOADED (see
+    super_res_features)."""
+    _, _, prefixes = net._hg_module(prefix)
+    return _hg_apply(net, prefixes[0], prefixes, x, params)
+
+
+def hourglass(net, stack, x, params=None):
+    """The HourGlass module image_filter_lr.m{stack} on x [B,256,h,w] (h, w multiples of 2^hg_depth), with a grad_fn: its backward is
+    net.hourglass_backward() and hands x and every parameter of the module its gradient.  With conv_block and four 1 x 1 layers in
+    plain torch on net.hg_parameters() this composes a trainable filter_lr ("Hourglass gradients")."""
+    _, _, prefixes = net._hg_module(int(stack))
+    return _hg_apply(net, int(stack), prefixes, x, params)

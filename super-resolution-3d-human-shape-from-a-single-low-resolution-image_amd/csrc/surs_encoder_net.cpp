@@ -980,3 +980,350 @@ extern "C" int surs_encoder_super_res_backward(const SursEncoderNet *net, const 
     sr_backward(k, m, g_img_sr, g_feature_lr, g_im_feat_hr);
     return r.rc;
 }
+
+// ---------------------------------------------------------------- hourglass gradients (include/surs.h)
+// surs_encoder_convblock_train / surs_encoder_hourglass_train run conv_block() / hourglass() above in the separate-sum form - the
+// launches of the host mirror (encoder.py) for an input without statistics - with EVERY map in the tape: the block's input, the
+// raw cat(o1, o2, o3) (the closing sum goes to a map of its own instead of overwriting the slices) and, per norm site, the four
+// coefficient vectors surs_groupnorm_fold forms from what the forward's kernels folded themselves.  The backward lays the tape out
+// by running the same sequencing without launches: the addresses are a function of the net and the size alone.
+namespace {
+
+struct NormTape { float *mean, *rstd, *scale, *shift; };
+struct BlockTape {
+    Map x, cat, out;
+    NormTape nt[3];
+};
+struct HgTape {
+    std::vector<BlockTape> blocks;   // in the order of the net's block array
+};
+
+NormTape norm_vectors(Run &r, int c) {
+    NormTape t;
+    t.mean = (float *)r.a->take(sizeof(float) * 32);
+    t.rstd = (float *)r.a->take(sizeof(float) * 32);
+    t.scale = (float *)r.a->take(sizeof(float) * c);
+    t.shift = (float *)r.a->take(sizeof(float) * c);
+    return t;
+}
+
+// conv_block() in the separate-sum form, on the tape
+Map conv_block_train(Run &r, const SursConvBlock &b, const Map &x, bool want_stats, BlockTape &t) {
+    const int c = x.c;
+    t.x = x;
+    t.cat = r.map(x.h, x.w, c);
+    t.out = r.map(x.h, x.w, c);
+    Map o1 = t.cat.slice(0, c / 2), o2 = t.cat.slice(c / 2, c / 4), o3 = t.cat.slice(3 * c / 4, c / 4);
+    auto eligible = [&](const Map &m, const SursConv &cw) {
+        return (cw.ksize == 1 || cw.ksize == 3) && cw.w_split && m.c % 32 == 0 && m.ld % 4 == 0 && aligned16(m.p);
+    };
+    const bool fused = c % 128 == 0 && eligible(x, b.conv[0]) && eligible(o1, b.conv[1]) && eligible(o2, b.conv[2]);
+    Map ins[3] = {x, o1, o2};
+    Map outs[3] = {o1, o2, o3};
+    for (int k = 0; k < 3; ++k) t.nt[k] = norm_vectors(r, ins[k].c);
+    if (fused && x.st.sums && x.st.g1 == 0) {
+        for (int k = 0; k < 3; ++k) {
+            conv_gn(r, ins[k], b.conv[k], outs[k], &b.bn[k], k < 2);
+            if (k < 2) ins[k + 1].st = outs[k].st;   // (the slice the next convolution reads, with the statistics this one left)
+            if (!r.dry && !r.rc)
+                r.fail(surs_groupnorm_fold(&ins[k].st, nullptr, x.h * x.w, ins[k].c, ins[k].ld, 1e-5f, b.bn[k].gamma, b.bn[k].beta, t.nt[k].mean,
+                                           t.nt[k].rstd, t.nt[k].scale, t.nt[k].shift, nullptr, r.st));
+        }
+        add3(r, t.cat, x, t.out, want_stats);
+        return t.out;
+    }
+    void *scratch = r.a->take(surs_groupnorm_scratch_bytes());
+    for (int k = 0; k < 3; ++k) {
+        if (!r.dry && !r.rc)
+            r.fail(surs_groupnorm_fold(nullptr, ins[k].p, x.h * x.w, ins[k].c, ins[k].ld, 1e-5f, b.bn[k].gamma, b.bn[k].beta, t.nt[k].mean,
+                                       t.nt[k].rstd, t.nt[k].scale, t.nt[k].shift, scratch, r.st));
+        conv(r, ins[k], b.conv[k], outs[k], 1, 0, 0.0f, nullptr, t.nt[k].scale, t.nt[k].shift);
+    }
+    add3(r, t.cat, x, t.out, want_stats && fused);
+    return t.out;
+}
+
+// hourglass() on one stream, on the tape; blocks: the stack's 3 depth + 1 blocks in module order
+Map hourglass_train(Run &r, const SursConvBlock *blocks, int depth, const Map &x, HgTape &m) {
+    m.blocks.assign(3 * depth + 1, BlockTape());
+    struct Fwd {
+        Run &r; const SursConvBlock *blocks; HgTape &m; int next;
+        Map run(int level, const Map &inp) {
+            const int i1 = next++, i2 = next++;
+            Map up1 = conv_block_train(r, blocks[i1], inp, false, m.blocks[i1]);
+            Map pooled = avgpool2(r, inp, true);
+            Map low1 = conv_block_train(r, blocks[i2], pooled, true, m.blocks[i2]);
+            Map low2;
+            if (level > 1) {
+                low2 = run(level - 1, low1);
+            } else {
+                const int ip = next++;
+                low2 = conv_block_train(r, blocks[ip], low1, true, m.blocks[ip]);
+            }
+            const int i3 = next++;
+            Map low3 = conv_block_train(r, blocks[i3], low2, false, m.blocks[i3]);
+            Map out = r.map(2 * low3.h, 2 * low3.w, low3.c);
+            bicubic_up2(r, low3, true, &up1, out, true);
+            return out;
+        }
+    } f{r, blocks, m, 0};
+    return f.run(depth, x);
+}
+
+struct HgBack {
+    Run &r;
+    int acc;
+    Map G, A, T;               // a block's scratch: its gradient (the slices take the inner gradients), relu(norm(x)), d / d that
+    void *wws = nullptr;       // the weight gradient's slabs
+    size_t wws_bytes = 0;
+    void *gws = nullptr;       // the GroupNorm gradient's parts
+    size_t gws_bytes = 0;
+
+    void alloc(int h, int w) {
+        G = r.map(h, w, 256); A = r.map(h, w, 256); T = r.map(h, w, 256);
+        wws_bytes = surs_conv_grad_weight_workspace_bytes(h, w, 256, 128, 3);
+        wws = r.a->take(wws_bytes);
+        gws_bytes = surs_groupnorm_relu_grad_workspace_bytes(h * w, 256);
+        gws = r.a->take(gws_bytes);
+    }
+    void copy(const Map &src, const Map &dst) {   // dense map -> dense map
+        if (r.dry || r.rc) return;
+        if (hipMemcpyAsync(dst.p, src.p, sizeof(float) * src.h * src.w * src.c, hipMemcpyDeviceToDevice, r.st) != hipSuccess)
+            r.fail(fail(SURS_E_HIP, "hourglass gradients: hipMemcpyAsync failed"));
+    }
+    // g = d L / d (the block's output), dense -> dx = d L / d (its input), dense, replaced; the parameters' gradients
+    void block(const BlockTape &t, const SursHgBlockParams &P, const SursHgBlockParams &D, const Map &g, const Map &dx) {
+        if (r.dry || r.rc) return;
+        const int h = t.x.h, w = t.x.w, hw = h * w;
+        Map Gm = G, Am = A, Tm = T;
+        Gm.h = Am.h = Tm.h = h; Gm.w = Am.w = Tm.w = w;
+        copy(g, dx);    // the identity path
+        copy(g, Gm);
+        const Map ins[3] = {t.x, t.cat.slice(0, 128), t.cat.slice(128, 64)};
+        const int c0[3] = {0, 128, 192}, cout[3] = {128, 64, 64};
+        for (int k = 2; k >= 0 && !r.rc; --k) {
+            const int cin = ins[k].c;
+            Map a = Am, d = Tm;
+            a.c = a.ld = d.c = d.ld = cin;
+            const Map gk = Gm.slice(c0[k], cout[k]);
+            r.fail(surs_scale_shift_act(ins[k].p, hw, cin, ins[k].ld, t.nt[k].scale, t.nt[k].shift, 1, a.p, a.ld, r.st));
+            if (!r.rc)
+                r.fail(surs_conv_grad_weight(gk.p, h, w, cout[k], gk.ld, nullptr, 0, 1.0f, a.p, h, w, cin, a.ld, 3, 1, D.weight[k], nullptr, acc,
+                                             wws, wws_bytes, r.st));
+            if (!r.rc)
+                r.fail(surs_conv_grad_input(gk.p, h, w, cout[k], gk.ld, nullptr, 0, 1.0f, P.weight[k], cin, 3, 1, d.p, h, w, d.ld, 0, r.st));
+            // into the gradient of the map this norm read: slice [0, 128) / [128, 192) of the block's gradient, or the input's
+            const Map into = k == 0 ? dx : Gm.slice(c0[k - 1], cout[k - 1]);
+            if (!r.rc)
+                r.fail(surs_groupnorm_relu_grad(d.p, d.ld, ins[k].p, ins[k].ld, hw, cin, t.nt[k].mean, t.nt[k].rstd, t.nt[k].scale,
+                                                t.nt[k].shift, P.gamma[k], into.p, into.ld, 1, D.gamma[k], D.beta[k], acc, gws, gws_bytes, r.st));
+        }
+    }
+};
+
+void hourglass_backward(HgBack &k, const HgTape &m, int depth, const SursHgBlockParams *P, const SursHgBlockParams *D, const Map &g,
+                        const Map &dx) {
+    struct Bwd {
+        HgBack &k; const HgTape &m; const SursHgBlockParams *P, *D; int next;
+        void run(int level, const Map &g, const Map &dinp) {
+            Run &r = k.r;
+            const int i1 = next++, i2 = next++;
+            Map p = r.map(g.h / 2, g.w / 2, 256), q = r.map(g.h / 2, g.w / 2, 256);
+            // the forward's block indices below this level, taken in the forward's order; the launches run in reverse
+            const int below = next;
+            int ip = -1;
+            if (level > 1) next += 3 * (level - 1) + 1; else ip = next++;
+            const int i3 = next++;
+            k.block(m.blocks[i1], P[i1], D[i1], g, dinp);
+            if (!r.dry && !r.rc) r.fail(surs_bicubic_up2_grad(g.p, p.h, p.w, 256, g.ld, p.p, p.ld, 0, r.st));
+            k.block(m.blocks[i3], P[i3], D[i3], p, q);
+            if (level > 1) {
+                const int keep = next;
+                next = below;
+                run(level - 1, q, p);
+                next = keep;
+            } else {
+                k.block(m.blocks[ip], P[ip], D[ip], q, p);
+            }
+            k.block(m.blocks[i2], P[i2], D[i2], p, q);
+            if (!r.dry && !r.rc) r.fail(surs_avgpool2_grad(q.p, q.h, q.w, 256, q.ld, dinp.p, dinp.ld, 1, r.st));
+        }
+    } b{k, m, P, D, 0};
+    b.run(depth, g, dx);
+}
+
+bool is_hg_block(const SursConvBlock &b) {
+    auto is = [](const SursConv &c, int cin, int cout) { return c.cin == cin && c.cout == cout && c.ksize == 3 && c.w_split && !c.bias; };
+    return is(b.conv[0], 256, 128) && is(b.conv[1], 128, 64) && is(b.conv[2], 64, 64) && b.bn[0].gamma && b.bn[0].beta && b.bn[1].gamma &&
+           b.bn[1].beta && b.bn[2].gamma && b.bn[2].beta;
+}
+
+int check_hg_train(const SursEncoderNet *net, int h, int w, int depth) {
+    SURS_REQUIRE(net, "null network");
+    SURS_REQUIRE(!((net->flags & SURS_ENC_EXTENDED) && net->norm == SURS_NORM_BATCH), "hourglass gradients: --norm group only");
+    if (int rc = check_net(net)) return rc;
+    SURS_REQUIRE(net->parts == 2, "hourglass gradients: net->parts == 1 (the f16 encoder) has no backward: training runs the fp32-grade "
+                                  "forward (parts == 2)");
+    SURS_REQUIRE(h > 0 && w > 0 && h % (1 << depth) == 0 && w % (1 << depth) == 0 && (long long)h * w < (1ll << 22),
+                 "hourglass gradients: a %d x %d map is not a multiple of 2^%d (or too large)", h, w, depth);
+    return 0;
+}
+
+bool hg_params_filled(const SursHgBlockParams *p, int count) {
+    for (int i = 0; i < count; ++i)
+        for (int k = 0; k < 3; ++k)
+            if (!p[i].weight[k] || !p[i].gamma[k] || !p[i].beta[k]) return false;
+    return true;
+}
+
+// the tape of a block (depth 0) or of a stack's hourglass: the input's copy, then the sequencing's maps
+struct HgLayout {
+    Map x;
+    BlockTape bt;
+    HgTape ht;
+    Map out;
+};
+
+// x (pitch ld): the input, copied into the tape in front of the launches; a run without launches lays the tape out
+void hg_layout(Run &r, const SursConvBlock *blocks, int depth, int h, int w, HgLayout &L, const float *x = nullptr, int ld = 0) {
+    L.x = r.map(h, w, 256);
+    if (!r.dry && hipMemcpy2DAsync(L.x.p, sizeof(float) * 256, x, sizeof(float) * ld, sizeof(float) * 256, (size_t)h * w,
+                                   hipMemcpyDeviceToDevice, r.st) != hipSuccess)
+        r.fail(fail(SURS_E_HIP, "hourglass gradients: hipMemcpy2DAsync failed"));
+    if (depth == 0) L.out = conv_block_train(r, blocks[0], L.x, false, L.bt);
+    else L.out = hourglass_train(r, blocks, depth, L.x, L.ht);
+}
+
+size_t hg_tape_need(const SursEncoderNet *net, const SursConvBlock *blocks, int depth, int h, int w) {
+    Arena d;
+    d.dry = true;
+    Run rd{net, &d, nullptr, net->parts, true};
+    HgLayout L;
+    hg_layout(rd, blocks, depth, h, w, L);
+    return align_up(d.peak, 256);
+}
+
+void hg_back_all(HgBack &k, const HgLayout &L, int depth, const SursHgBlockParams *P, const SursHgBlockParams *D, const Map &g, const Map &dx) {
+    k.alloc(dx.h, dx.w);
+    if (depth == 0) k.block(L.bt, P[0], D[0], g, dx);
+    else hourglass_backward(k, L.ht, depth, P, D, g, dx);
+}
+
+size_t hg_backward_need(const SursEncoderNet *net, int depth, int h, int w) {
+    Arena d;
+    d.dry = true;
+    Run rd{net, &d, nullptr, net->parts, true};
+    HgBack k{rd, 0};
+    HgLayout L;
+    if (depth > 0) L.ht.blocks.assign(3 * depth + 1, BlockTape());
+    Map g = input_map(nullptr, h, w, 256, 256);
+    const std::vector<SursHgBlockParams> none(3 * depth + 1);   // (a dry run reads no parameter)
+    hg_back_all(k, L, depth, none.data(), none.data(), g, g);
+    return align_up(d.peak, 256) + 256;
+}
+
+int hg_train(const SursEncoderNet *net, const SursConvBlock *blocks, int depth, const float *x, int h, int w, int ld, float *out, void *tape,
+             size_t tape_bytes, void *stream, const char *what) {
+    for (int i = 0; i < (depth ? 3 * depth + 1 : 1); ++i)
+        SURS_REQUIRE(is_hg_block(blocks[i]), "%s: the block is not image_filter_lr's (3 x 3, 256 -> 128 / 64 / 64, no bias, GroupNorm)", what);
+    SURS_REQUIRE(x && out && tape, "%s: null argument", what);
+    SURS_REQUIRE(ld >= 256, "%s: a map of 256 channels", what);
+    SURS_REQUIRE(((size_t)tape & 255) == 0, "%s: the tape must be 256-byte aligned", what);
+    const size_t need = hg_tape_need(net, blocks, depth, h, w);
+    SURS_REQUIRE(need <= tape_bytes, "%s: tape too small: %zu bytes needed", what, need);
+    Arena a;
+    a.base = (char *)tape;
+    a.cap = tape_bytes;
+    Run r{net, &a, as_stream(stream), net->parts, false};
+    HgLayout L;
+    hg_layout(r, blocks, depth, h, w, L, x, ld);
+    if (r.rc) return r.rc;
+    SURS_HIP_CHECK(hipMemcpyAsync(out, L.out.p, sizeof(float) * h * w * 256, hipMemcpyDeviceToDevice, r.st));
+    return 0;
+}
+
+int hg_backward(const SursEncoderNet *net, const SursConvBlock *blocks, int depth, const SursHgBlockParams *params, const void *tape, int h,
+                int w, const float *g, float *dx, const SursHgBlockParams *grads, int accumulate, void *workspace, size_t workspace_bytes,
+                void *stream, const char *what) {
+    const int count = depth ? 3 * depth + 1 : 1;
+    for (int i = 0; i < count; ++i)
+        SURS_REQUIRE(is_hg_block(blocks[i]), "%s: the block is not image_filter_lr's (3 x 3, 256 -> 128 / 64 / 64, no bias, GroupNorm)", what);
+    SURS_REQUIRE(params && grads && tape && g && dx && workspace, "%s: null argument", what);
+    SURS_REQUIRE(hg_params_filled(params, count) && hg_params_filled(grads, count), "%s: a null pointer in params / grads", what);
+    SURS_REQUIRE(((size_t)tape & 255) == 0 && aligned16(g) && aligned16(dx), "%s: the tape must be 256-byte aligned, the maps 16-byte", what);
+    Arena t;
+    t.base = (char *)const_cast<void *>(tape);
+    t.cap = hg_tape_need(net, blocks, depth, h, w);
+    Run rt{net, &t, nullptr, net->parts, true};   // (no launches: the addresses)
+    HgLayout L;
+    hg_layout(rt, blocks, depth, h, w, L);
+    Arena a;
+    a.base = (char *)align_up((size_t)workspace, 256);
+    const size_t lead = (size_t)(a.base - (char *)workspace);
+    const size_t need = hg_backward_need(net, depth, h, w);
+    SURS_REQUIRE(need - 256 + lead <= workspace_bytes, "%s: workspace too small: %zu bytes needed", what, need);
+    a.cap = workspace_bytes - lead;
+    Run r{net, &a, as_stream(stream), net->parts, false};
+    HgBack k{r, accumulate ? 1 : 0};
+    hg_back_all(k, L, depth, params, grads, input_map(g, h, w, 256, 256), input_map(dx, h, w, 256, 256));
+    return r.rc;
+}
+
+const SursConvBlock *stack_blocks(const SursEncoderNet *net, int stack) { return net->hg + (size_t)stack * per_stack_blocks(net); }
+
+}  // namespace
+
+extern "C" size_t surs_encoder_convblock_tape_bytes(const SursEncoderNet *net, int h, int w) {
+    if (!net || check_hg_train(net, h, w, 0) || !is_hg_block(net->conv2)) return 0;
+    return hg_tape_need(net, &net->conv2, 0, h, w);
+}
+
+extern "C" size_t surs_encoder_convblock_backward_workspace_bytes(const SursEncoderNet *net, int h, int w) {
+    if (!net || check_hg_train(net, h, w, 0)) return 0;
+    return hg_backward_need(net, 0, h, w);
+}
+
+extern "C" size_t surs_encoder_hourglass_tape_bytes(const SursEncoderNet *net, int h, int w) {
+    if (!net || check_hg_train(net, h, w, net->hg_depth) || !net->hg) return 0;
+    for (int i = 0; i < per_stack_blocks(net); ++i)
+        if (!is_hg_block(net->hg[i])) return 0;
+    return hg_tape_need(net, net->hg, net->hg_depth, h, w);
+}
+
+extern "C" size_t surs_encoder_hourglass_backward_workspace_bytes(const SursEncoderNet *net, int h, int w) {
+    if (!net || check_hg_train(net, h, w, net->hg_depth)) return 0;
+    return hg_backward_need(net, net->hg_depth, h, w);
+}
+
+extern "C" int surs_encoder_convblock_train(const SursEncoderNet *net, const SursConvBlock *block, const float *x, int h, int w, int ld,
+                                            float *out, void *tape, size_t tape_bytes, void *stream) {
+    SURS_REQUIRE(net && block, "convblock_train: null argument");
+    if (int rc = check_hg_train(net, h, w, 0)) return rc;
+    return hg_train(net, block, 0, x, h, w, ld, out, tape, tape_bytes, stream, "convblock_train");
+}
+
+extern "C" int surs_encoder_convblock_backward(const SursEncoderNet *net, const SursConvBlock *block, const SursHgBlockParams *params,
+                                               const void *tape, int h, int w, const float *g, float *dx, const SursHgBlockParams *grads,
+                                               int accumulate, void *workspace, size_t workspace_bytes, void *stream) {
+    SURS_REQUIRE(net && block, "convblock_backward: null argument");
+    if (int rc = check_hg_train(net, h, w, 0)) return rc;
+    return hg_backward(net, block, 0, params, tape, h, w, g, dx, grads, accumulate, workspace, workspace_bytes, stream, "convblock_backward");
+}
+
+extern "C" int surs_encoder_hourglass_train(const SursEncoderNet *net, int stack, const float *x, int h, int w, int ld, float *out,
+                                            void *tape, size_t tape_bytes, void *stream) {
+    SURS_REQUIRE(net && net->hg, "hourglass_train: null argument");
+    if (int rc = check_hg_train(net, h, w, net->hg_depth)) return rc;
+    SURS_REQUIRE(stack >= 0 && stack < net->num_stack, "hourglass_train: stack %d of %d", stack, net->num_stack);
+    return hg_train(net, stack_blocks(net, stack), net->hg_depth, x, h, w, ld, out, tape, tape_bytes, stream, "hourglass_train");
+}
+
+extern "C" int surs_encoder_hourglass_backward(const SursEncoderNet *net, int stack, const SursHgBlockParams *params, const void *tape, int h,
+                                               int w, const float *g, float *dx, const SursHgBlockParams *grads, int accumulate,
+                                               void *workspace, size_t workspace_bytes, void *stream) {
+    SURS_REQUIRE(net && net->hg, "hourglass_backward: null argument");
+    if (int rc = check_hg_train(net, h, w, net->hg_depth)) return rc;
+    SURS_REQUIRE(stack >= 0 && stack < net->num_stack, "hourglass_backward: stack %d of %d", stack, net->num_stack);
+    return hg_backward(net, stack_blocks(net, stack), net->hg_depth, params, tape, h, w, g, dx, grads, accumulate, workspace, workspace_bytes,
+                       stream, "hourglass_backward");
+}

@@ -16,7 +16,10 @@ mlp_lr.* and mlp_hr.* parameter) and, with features=True, d error / d (the featu
 network and image_filter_hr.conv5 have a backward too: super_res_train() keeps the forward's maps, super_res_backward() returns the
 gradients of every super_resolution.* convolution and conv5 from the gradients of img_SR, feature_lr and im_feat_list_hr[0]
 (native.sr_backward), sr_parameters() are the fp32 weights it reads, autograd.super_res_features is the torch.autograd.Function over
-them.  The hourglass (image_filter_lr.*) has no backward here: its parameter gradients are out of scope.
+them.  Of the hourglass (image_filter_lr.*) the ConvBlock and the HourGlass module m{s} have a backward (--norm group):
+conv_block_train() / conv_block_backward(), hourglass_train() / hourglass_backward() (native.hg_backward), hg_parameters(),
+autograd.conv_block and autograd.hourglass, from which a trainable filter_lr is composed with the stack tails' 1 x 1 layers in torch;
+forward_backward() does not return encoder gradients.
 
 Encoder options: --norm group | batch and --scale 1..4 (anything else: ValueError at construction).  --norm batch is nn.BatchNorm2d in
 EVAL mode - y = (x - running_mean) / sqrt(running_var + 1e-5) * weight + bias, always from the running statistics: train() here keeps
@@ -90,6 +93,9 @@ class SuRSNet:
         self._sr_params = None        # native.SrParams + sr_parameters()'s OrderedDict: the plain fp32 super-resolution weights (dropped alike)
         self._sr_tapes = None         # what super_res_train() left for super_res_backward(): (h, w, [one tape per image])
         self._sr_ws = None
+        self._hg_params = None        # native.HgParams + hg_parameters()'s OrderedDict: the plain fp32 image_filter_lr weights (dropped alike)
+        self._hg_tapes = {}           # what conv_block_train() / hourglass_train() left: module -> (h, w, [one tape per image])
+        self._hg_ws = None
         self.last_classifier_grads = None   # what autograd.point_loss last left: classifier_grads()'s OrderedDict
         self._feat_cache = None
         self._stack_feat_cache = None
@@ -111,6 +117,8 @@ class SuRSNet:
             self._enc = self._blob = None
             self._grad_params = self._grad_ws = None
             self._sr_params = self._sr_tapes = self._sr_ws = None
+            self._hg_params = self._hg_ws = None
+            self._hg_tapes = {}
         return self
 
     def cuda(self, index=None):
@@ -155,6 +163,7 @@ class SuRSNet:
         self._enc = self._blob = None
         self._grad_params = None
         self._sr_params = None
+        self._hg_params = None
         return self
 
     # ------------------------------------------------------------------ lazily packed device state
@@ -308,6 +317,96 @@ class SuRSNet:
             grads = native.sr_backward(net, params, tapes[b], h, w, *[None if g is None else g[b] for g in gs], grads=grads,
                                        accumulate=b > 0, workspace=self._sr_ws, scale=scale)
         return grads
+
+    # ------------------------------------------------------------------ hourglass gradients
+    def _hg_native(self):
+        if weights.check_norm(getattr(self.opt, "norm", "group")) == "batch":
+            raise NotImplementedError("hourglass gradients: --norm group only (a BatchNorm encoder runs in eval mode and has no backward)")
+        W = self._encoder_weights()
+        if W.reduced:
+            raise RuntimeError("hourglass gradients: --encoder_precision f16 (net->parts == 1) has no backward: training runs the "
+                               "fp32-grade forward")
+        return encoder._native_net(W).net
+
+    def _hg_param_set(self):
+        if self._hg_params is None:
+            p = native.HgParams(self._sd, self.opt.num_stack_lr, self.opt.hg_depth, self._device())
+            self._hg_params = (p, OrderedDict((k, torch.nn.Parameter(v)) for k, v in p.tensors.items()))
+        return self._hg_params
+
+    def hg_parameters(self):
+        """The cached OrderedDict of torch.nn.Parameter over the plain fp32 device copies of every image_filter_lr.* tensor the forward
+        reads (state_dict() order: the ConvBlocks' conv1-3.weight and bn1-3.weight / .bias - not bn4 -, conv_last, bn_end, l, bl, al):
+        what conv_block_backward() / hourglass_backward() read and autograd.conv_block / autograd.hourglass hand gradients to.  The
+        FORWARD runs on the packed weights of load_state_dict(), which drops this cache (as it drops sr_parameters()'s)."""
+        return self._hg_param_set()[1]
+
+    def _hg_module(self, which):
+        """(the library's handle, the module's ConvBlock prefixes) of a stack index (its hourglass m{s}) or a ConvBlock's prefix."""
+        net = self._hg_native()
+        if isinstance(which, (int, np.integer)) and not isinstance(which, bool):
+            if not 0 <= which < self.opt.num_stack_lr:
+                raise ValueError("stack %d of %d" % (which, self.opt.num_stack_lr))
+            return net, int(which), native.hg_block_prefixes(int(which), self.opt.hg_depth)
+        prefix = which if which.endswith(".") else which + "."
+        if not prefix.startswith(native.HG):
+            prefix = native.HG + prefix
+        return net, native.hg_block_of(net, prefix, self.opt.hg_depth), [prefix]
+
+    def _hg_train(self, which, x):
+        net, handle, prefixes = self._hg_module(which)
+        if x.dim() != 4 or x.shape[1] != 256:
+            raise ValueError("a [B,256,h,w] tensor is expected, not %s" % (tuple(x.shape),))
+        outs, tapes = [], []
+        for b in range(x.shape[0]):
+            out, tape = native.hg_train_forward(net, handle, _as_img(x[b:b + 1].detach().to(self._device(), torch.float32)))
+            outs.append(_as_nchw_view(out))
+            tapes.append(tape)
+        self._hg_tapes[prefixes[0] if len(prefixes) == 1 else handle] = (x.shape[2], x.shape[3], tapes)
+        return torch.cat(outs, 0) if len(outs) > 1 else outs[0]
+
+    def _hg_backward(self, which, grad_out, what):
+        net, handle, prefixes = self._hg_module(which)
+        kept = self._hg_tapes.get(prefixes[0] if len(prefixes) == 1 else handle)
+        if kept is None:
+            raise RuntimeError("%s_backward needs a preceding %s_train() of the same module: the tape of the forward's maps is missing"
+                               % (what, what))
+        h, w, tapes = kept
+        dev, B = self._device(), len(tapes)
+        if tuple(grad_out.shape) != (B, 256, h, w):
+            raise ValueError("grad_out %s against the output's %s" % (tuple(grad_out.shape), (B, 256, h, w)))
+        g = grad_out.detach().to(dev, torch.float32).permute(0, 2, 3, 1).contiguous()
+        params = self._hg_param_set()[0].tensors
+        need = native.hg_backward_workspace_bytes(net, h, w, len(prefixes) > 1)
+        if self._hg_ws is None or self._hg_ws.numel() < need or self._hg_ws.device != dev:
+            self._hg_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        grads, dxs = None, []
+        for b in range(B):
+            dx, grads = native.hg_backward(net, handle, prefixes, params, tapes[b], h, w, g[b], grads=grads, accumulate=b > 0,
+                                           workspace=self._hg_ws)
+            dxs.append(dx)
+        return torch.stack(dxs, 0).permute(0, 3, 1, 2), grads
+
+    def conv_block_train(self, prefix, x):
+        """ConvBlock `prefix` (image_filter_lr.conv2. / .top_m_{s}. / .m{s}.b1_{l}. ...; 'image_filter_lr.' may be left out) on x
+        [B,256,h,w]: encoder.conv_block's values, with what the backward reads kept on this object, one tape per image
+        (surs_encoder_convblock_train)."""
+        return self._hg_train(prefix, x)
+
+    def conv_block_backward(self, prefix, grad_out):
+        """(d <grad_out, out> / d x [B,256,h,w], OrderedDict of the gradients of the block's nine parameters summed over the batch in
+        image order) from the tapes of the preceding conv_block_train(prefix, x)."""
+        return self._hg_backward(prefix, grad_out, "conv_block")
+
+    def hourglass_train(self, stack, x):
+        """image_filter_lr.m{stack} on x [B,256,h,w] (h, w multiples of 2^hg_depth): encoder.hourglass's values, tapes kept
+        (surs_encoder_hourglass_train)."""
+        return self._hg_train(int(stack), x)
+
+    def hourglass_backward(self, stack, grad_out):
+        """(d <grad_out, out> / d x, OrderedDict of the gradients of every parameter of m{stack}, blocks in module order) from the
+        tapes of the preceding hourglass_train(stack, x)."""
+        return self._hg_backward(int(stack), grad_out, "hourglass")
 
     def reencode_wide(self):
         """Runs the encoder again on the images of the last super_res() call with every fp32-grade product on three bf16 parts

@@ -1301,6 +1301,230 @@ def sr_backward(net, params, tape, h, w, g_img_sr=None, g_feature_lr=None, g_im_
     return grads
 
 
+# ------------------------------------------------------------------ hourglass gradients
+
+def groupnorm_fold(x, gamma, beta, eps=1e-5):
+    """surs_groupnorm_fold: (mean [32], rstd [32], scale [c], shift [c]) of GroupNorm(32) on Img x - from x.stats where the kernel that
+    wrote x left them (the convolutions' in-kernel fold, restated), else from the map (groupnorm_coeffs' launches and one more)."""
+    dev = x.buf.device
+    mean, rstd = torch.empty(32, dtype=torch.float32, device=dev), torch.empty(32, dtype=torch.float32, device=dev)
+    scale, shift = torch.empty(x.c, dtype=torch.float32, device=dev), torch.empty(x.c, dtype=torch.float32, device=dev)
+    if x.stats is not None:
+        st = _lib.GnStats(x.stats.buf.data_ptr(), x.stats.slots, 0, 0, (C.c_int * 3)(x.stats.slots, x.stats.slots, x.stats.slots))
+        check(lib().surs_groupnorm_fold(C.byref(st), None, x.h * x.w, x.c, x.ld, eps, _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(rstd),
+                                        _ptr(scale), _ptr(shift), None, _stream()))
+    else:
+        scratch = torch.empty(lib().surs_groupnorm_scratch_bytes(), dtype=torch.uint8, device=dev)
+        check(lib().surs_groupnorm_fold(None, x.ptr(), x.h * x.w, x.c, x.ld, eps, _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(rstd),
+                                        _ptr(scale), _ptr(shift), _ptr(scratch), _stream()))
+    return mean, rstd, scale, shift
+
+
+def groupnorm_relu_grad(g, x, coeffs, gamma, dx=None, add=False, dgamma=None, dbeta=None, accumulate=False, workspace=None):
+    """surs_groupnorm_relu_grad: the backward of relu(GroupNorm32(x; gamma, beta)) from g = d L / d (its output) and the site's
+    groupnorm_fold() vectors `coeffs`.  Returns (dx Img, dgamma, dbeta); add: dx is added to; accumulate: dgamma / dbeta are."""
+    dev = g.buf.device
+    if (g.h, g.w, g.c) != (x.h, x.w, x.c):
+        raise ValueError("groupnorm_relu_grad: g %s against x %s" % ((g.h, g.w, g.c), (x.h, x.w, x.c)))
+    if dx is None:
+        if add:
+            raise ValueError("add needs the dx to add to")
+        dx = Img(x.h, x.w, x.c, device=dev)
+    if dgamma is None:
+        if accumulate:
+            raise ValueError("accumulate needs the dgamma / dbeta to add to")
+        dgamma, dbeta = torch.empty(x.c, dtype=torch.float32, device=dev), torch.empty(x.c, dtype=torch.float32, device=dev)
+    need = lib().surs_groupnorm_relu_grad_workspace_bytes(x.h * x.w, x.c)
+    if need == 0:
+        raise ValueError("surs_groupnorm_relu_grad_workspace_bytes refused %d pixels of %d channels" % (x.h * x.w, x.c))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    mean, rstd, scale, shift = coeffs
+    check(lib().surs_groupnorm_relu_grad(g.ptr(), g.ld, x.ptr(), x.ld, x.h * x.w, x.c, _ptr(mean), _ptr(rstd), _ptr(scale), _ptr(shift),
+                                         _ptr(_f32c(gamma)), dx.ptr(), dx.ld, 1 if add else 0, _ptr(_f32c(dgamma)), _ptr(_f32c(dbeta)),
+                                         1 if accumulate else 0, _ptr(workspace), workspace.numel() * workspace.element_size(), _stream()))
+    return dx, dgamma, dbeta
+
+
+def avgpool2_grad(g, dx=None, add=False):
+    """surs_avgpool2_grad: Img g [h,w,c] -> Img dx [2h,2w,c] (+)= 0.25 g[y // 2][x // 2]."""
+    if dx is None:
+        if add:
+            raise ValueError("add needs the dx to add to")
+        dx = Img(2 * g.h, 2 * g.w, g.c, device=g.buf.device)
+    elif (dx.h, dx.w, dx.c) != (2 * g.h, 2 * g.w, g.c):
+        raise ValueError("avgpool2_grad: dx %s against g %s" % ((dx.h, dx.w, dx.c), (g.h, g.w, g.c)))
+    check(lib().surs_avgpool2_grad(g.ptr(), g.h, g.w, g.c, g.ld, dx.ptr(), dx.ld, 1 if add else 0, _stream()))
+    return dx
+
+
+def bicubic_up2_grad(g, dx=None, add=False):
+    """surs_bicubic_up2_grad: Img g [2h,2w,c] -> Img dx [h,w,c], the transpose of bicubic_up2(align_corners=True)."""
+    if g.h % 2 or g.w % 2:
+        raise ValueError("bicubic_up2_grad: g %s must have an even size" % ((g.h, g.w, g.c),))
+    if dx is None:
+        if add:
+            raise ValueError("add needs the dx to add to")
+        dx = Img(g.h // 2, g.w // 2, g.c, device=g.buf.device)
+    elif (2 * dx.h, 2 * dx.w, dx.c) != (g.h, g.w, g.c):
+        raise ValueError("bicubic_up2_grad: dx %s against g %s" % ((dx.h, dx.w, dx.c), (g.h, g.w, g.c)))
+    check(lib().surs_bicubic_up2_grad(g.ptr(), dx.h, dx.w, g.c, g.ld, dx.ptr(), dx.ld, 1 if add else 0, _stream()))
+    return dx
+
+
+HG = "image_filter_lr."
+_BLOCK_FIELDS = (("weight", ("conv1.weight", "conv2.weight", "conv3.weight")), ("gamma", ("bn1.weight", "bn2.weight", "bn3.weight")),
+                 ("beta", ("bn1.bias", "bn2.bias", "bn3.bias")))
+
+
+def hg_block_prefixes(stack, depth):
+    """The ConvBlocks of image_filter_lr.m{stack} in module order (SursEncoderNet.hg's): b1_d, b2_d, [level d - 1], b2_plus_1, b3_1, ..."""
+    out = []
+
+    def gen(level):
+        out.append(HG + "m%d.b1_%d." % (stack, level))
+        out.append(HG + "m%d.b2_%d." % (stack, level))
+        if level > 1:
+            gen(level - 1)
+        else:
+            out.append(HG + "m%d.b2_plus_%d." % (stack, level))
+        out.append(HG + "m%d.b3_%d." % (stack, level))
+    gen(depth)
+    return out
+
+
+def hg_block_keys(prefix):
+    """The nine tensors of a ConvBlock the forward reads (bn4 belongs to the downsample path in_planes == out_planes never takes)."""
+    return [prefix + k for k in ("conv1.weight", "conv2.weight", "conv3.weight", "bn1.weight", "bn1.bias", "bn2.weight", "bn2.bias",
+                                 "bn3.weight", "bn3.bias")]
+
+
+def hg_param_keys(sd, num_stack, depth):
+    """Every image_filter_lr.* key the forward reads, in sd's order: the ConvBlocks' nine tensors each and the stacks' 1 x 1 tails."""
+    want = set(hg_block_keys(HG + "conv2."))
+    for s in range(num_stack):
+        for p in hg_block_prefixes(s, depth) + [HG + "top_m_%d." % s]:
+            want |= set(hg_block_keys(p))
+        tails = ["conv_last%d" % s, "bn_end%d" % s, "l%d" % s] + (["bl%d" % s, "al%d" % s] if s < num_stack - 1 else [])
+        want |= {HG + t + e for t in tails for e in (".weight", ".bias")}
+    return [k for k in sd if k in want]
+
+
+class HgParams:
+    """The plain fp32 device copies of hg_param_keys(): what the hourglass backward reads (the forward runs on packed copies)."""
+
+    def __init__(self, sd, num_stack, depth, device):
+        self.num_stack, self.depth = int(num_stack), int(depth)
+        self.keys = hg_param_keys(sd, self.num_stack, self.depth)
+        self.tensors = OrderedDict()
+        for k in self.keys:
+            v = sd[k]
+            v = v.detach() if torch.is_tensor(v) else torch.from_numpy(np.asarray(v, np.float32))
+            self.tensors[k] = v.to(device, torch.float32).contiguous()
+
+    @staticmethod
+    def struct(prefixes, tensors):
+        """(ctypes array of SursHgBlockParams for the blocks `prefixes`, over `tensors`: key -> contiguous float32 device tensor)."""
+        arr = (_lib.HgBlockParams * len(prefixes))()
+        for i, p in enumerate(prefixes):
+            for field, names in _BLOCK_FIELDS:
+                for k, n in enumerate(names):
+                    getattr(arr[i], field)[k] = _f32c(tensors[p + n]).data_ptr()
+        return arr
+
+
+def hg_block_of(net, prefix, depth):
+    """The SursConvBlock of _lib.EncoderNet `net` behind a state-dict prefix (image_filter_lr.conv2. / .top_m_{s}. / .m{s}.b*_{l}.)."""
+    name = prefix[len(HG):].rstrip(".") if prefix.startswith(HG) else None
+    if name == "conv2":
+        return net.conv2
+    if name and name.startswith("top_m_") and name[6:].isdigit() and int(name[6:]) < net.num_stack:
+        return net.top_m[int(name[6:])]
+    if name and name.startswith("m") and "." in name and name[1:name.index(".")].isdigit():
+        s = int(name[1:name.index(".")])
+        pre = hg_block_prefixes(s, depth)
+        if s < net.num_stack and prefix in pre:
+            return net.hg[s * len(pre) + pre.index(prefix)]
+    raise ValueError("%r is no ConvBlock of image_filter_lr" % (prefix,))
+
+
+def _hg_size(what, net, h, w):
+    n = getattr(lib(), what)(C.byref(net), h, w)
+    if n == 0:
+        raise ValueError("%s refused a %dx%d map: %s" % (what, h, w, lib().surs_last_error().decode()))
+    return n
+
+
+def hg_tape_bytes(net, h, w, hourglass):
+    """surs_encoder_hourglass_tape_bytes / surs_encoder_convblock_tape_bytes."""
+    what = "surs_encoder_%s_tape_bytes" % ("hourglass" if hourglass else "convblock")
+    return _hg_size(what, net, h, w)
+
+
+def hg_backward_workspace_bytes(net, h, w, hourglass):
+    what = "surs_encoder_%s_backward_workspace_bytes" % ("hourglass" if hourglass else "convblock")
+    return _hg_size(what, net, h, w)
+
+
+def _hg_buffer(t, need, dev, what):
+    if t is None:
+        return torch.empty(need, dtype=torch.uint8, device=dev)
+    if t.numel() * t.element_size() < need or t.device != dev or t.data_ptr() % 256:
+        raise ValueError("%s: %d bytes needed on %s, 256-byte aligned" % (what, need, dev))
+    return t
+
+
+def hg_train_forward(net, which, x, tape=None):
+    """surs_encoder_convblock_train (which: a _lib.ConvBlock of net) / surs_encoder_hourglass_train (which: the stack's index) of Img x
+    [h,w,256].  Returns (out Img - encoder.conv_block's / encoder.hourglass's bits on the same statistics-free x -, tape)."""
+    dev = x.buf.device
+    hourglass = isinstance(which, int)
+    if x.c != 256:
+        raise ValueError("a map of 256 channels is expected, not %d" % x.c)
+    tape = _hg_buffer(tape, hg_tape_bytes(net, x.h, x.w, hourglass), dev, "tape")
+    out = Img(x.h, x.w, 256, device=dev)
+    tb = tape.numel() * tape.element_size()
+    if hourglass:
+        check(lib().surs_encoder_hourglass_train(C.byref(net), which, x.ptr(), x.h, x.w, x.ld, out.ptr(), _ptr(tape), tb, _stream()))
+    else:
+        check(lib().surs_encoder_convblock_train(C.byref(net), C.byref(which), x.ptr(), x.h, x.w, x.ld, out.ptr(), _ptr(tape), tb, _stream()))
+    return out, tape
+
+
+def hg_backward(net, which, prefixes, params, tape, h, w, g, grads=None, accumulate=False, workspace=None):
+    """surs_encoder_convblock_backward / surs_encoder_hourglass_backward for ONE image: g = d L / d out, a contiguous float32 NHWC device
+    tensor [h,w,256]; prefixes: the module's ConvBlock prefixes in its order (one for a block, hg_block_prefixes for an hourglass);
+    params: key -> plain fp32 device tensor (HgParams.tensors).  grads: an OrderedDict as returned, to overwrite or (accumulate) add
+    to.  Returns (dx [h,w,256] tensor, grads: the module's keys in prefix order)."""
+    dev = tape.device
+    hourglass = isinstance(which, int)
+    keys = [k for p in prefixes for k in hg_block_keys(p)]
+    if accumulate and grads is None:
+        raise ValueError("accumulate needs the grads to add to")
+    if grads is None:
+        grads = OrderedDict((k, torch.empty_like(params[k])) for k in keys)
+    else:
+        for k in keys:
+            if k not in grads or tuple(grads[k].shape) != tuple(params[k].shape) or grads[k].dtype != torch.float32 \
+                    or not grads[k].is_contiguous() or grads[k].device != dev:
+                raise ValueError("grads[%r] must be a contiguous float32 tensor %s on %s" % (k, tuple(params[k].shape), dev))
+    if tuple(g.shape[-3:]) != (h, w, 256) or g.numel() != h * w * 256 or g.dtype != torch.float32 or not g.is_contiguous() or g.device != dev:
+        raise ValueError("g must be a contiguous float32 NHWC tensor %s on %s, not %s" % ((h, w, 256), dev, tuple(g.shape)))
+    if tape.numel() * tape.element_size() < hg_tape_bytes(net, h, w, hourglass):
+        raise ValueError("tape: %d bytes needed for a %dx%d map" % (hg_tape_bytes(net, h, w, hourglass), h, w))
+    workspace = _hg_buffer(workspace, hg_backward_workspace_bytes(net, h, w, hourglass), dev, "workspace")
+    ps, gs = HgParams.struct(prefixes, params), HgParams.struct(prefixes, grads)
+    dx = torch.empty((h, w, 256), dtype=torch.float32, device=dev)
+    wb = workspace.numel() * workspace.element_size()
+    if hourglass:
+        check(lib().surs_encoder_hourglass_backward(C.byref(net), which, ps, _ptr(tape), h, w, _ptr(g), _ptr(dx), gs, 1 if accumulate else 0,
+                                                    _ptr(workspace), wb, _stream()))
+    else:
+        check(lib().surs_encoder_convblock_backward(C.byref(net), C.byref(which), ps, _ptr(tape), h, w, _ptr(g), _ptr(dx), gs,
+                                                    1 if accumulate else 0, _ptr(workspace), wb, _stream()))
+    return dx, grads
+
+
 def query_points_views(points, calibs, projection, zmul, zdiv, feat_lr, feat_hr, blob, ws, want_logits=False):
     """Multi-view / perspective query.  points [V,3,N] f32 device tensor; calibs [V,12] (host); feat_lr [V,hl,wl,256] and
     feat_hr [V,hh,wh,64] contiguous NHWC device tensors; projection 'orthogonal' | 'perspective'.
