@@ -1,6 +1,6 @@
 // The image encoder sequenced in C: surs_encoder_super_res / _filter_lr / _filter_hr / _forward (include/surs.h).
 //
-// Replaces, as ONE call each, what the reference runs as nn.Module graphs (/root/reference):
+// Replaces, as ONE call each, what the reference runs as nn.Module graphs:
 //   SuRSSR_v3.forward          lib/model/SuRSSR_v3.py:143-181   (ResBlock: lib/model/common.py:14-33)
 //   HGFilter.forward low_res   lib/model/HGFilters.py:183-206   (ConvBlock :57-74, HourGlass :96-117)
 //   HGFilter.forward high_res  lib/model/HGFilters.py:179-181
@@ -13,6 +13,11 @@
 // Memory plan: a bump allocator over the workspace.  The super-resolution net reuses three buffers per stage for its residual
 // blocks (one stream: reuse is ordered); filter_lr alternates between two arenas per stack (stack s + 2 starts after every
 // kernel of stack s has been joined).  surs_encoder_workspace_bytes() runs the same sequencing with a counting allocator.
+//
+// ONE sequencing per network.  super_res() (over a plan of buffers), conv_block() and hourglass() (with an optional tape) are the
+// only launch lists of their networks: the inference calls, the train forwards of the gradient entry points further down and - run
+// without launches - every size query and the backwards' address computation all go through them.  The layout of a tape is the
+// order of the allocator's takes of that sequencing; the backwards walk the same plan / the same level table in reverse.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -31,6 +36,13 @@ struct Map {   // NHWC fp32 view with channel pitch + the GroupNorm(32) statisti
     void set_stats(double *sums, int slots) { st = SursGnStats{sums, slots, 0, 0, {slots, slots, slots}}; }
     Map slice(int c0, int n) const { Map m = *this; m.p = p + c0; m.c = n; m.set_stats(nullptr, 0); return m; }
 };
+
+// a map over memory the arena did not hand out: a caller's buffer, or a view of another size into a shared one
+Map input_map(const float *x, int h, int w, int c, int ld) {
+    Map m;
+    m.p = const_cast<float *>(x); m.h = h; m.w = w; m.c = c; m.ld = ld;
+    return m;
+}
 
 struct Arena {
     char *base = nullptr;
@@ -69,6 +81,29 @@ struct Run {
         return rc != 0;
     }
 };
+
+struct Dry {   // a run without launches over a counting arena of its own: sizes, and the addresses of a layout
+    Arena a;
+    Run r;
+    explicit Dry(const SursEncoderNet *net) : r{net, &a, nullptr, net->parts, true} { a.dry = true; }
+    Dry(const Dry &) = delete;
+};
+
+Arena tape_arena(const void *tape, size_t bytes) {   // (a tape is 256-byte aligned: the entry points check)
+    Arena a;
+    a.base = (char *)const_cast<void *>(tape);
+    a.cap = bytes;
+    return a;
+}
+
+// a: the caller's workspace from its first 256-byte boundary on; false: fewer than `need` bytes are left behind it
+bool workspace_arena(void *workspace, size_t workspace_bytes, size_t need, Arena &a) {
+    a.base = (char *)align_up((size_t)workspace, 256);
+    const size_t lead = (size_t)(a.base - (char *)workspace);
+    if (need + lead > workspace_bytes) return false;
+    a.cap = workspace_bytes - lead;
+    return true;
+}
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<size_t>(p) & 15) == 0; }
 
@@ -184,67 +219,124 @@ constexpr int ACT = 1;
 constexpr float LRELU = 0.2f, RELU = 0.0f;
 
 // ---------------------------------------------------------------- SuRSSR_v3.forward (lib/model/SuRSSR_v3.py:143-181)
-// H2 x W2: the enlarged image (sr_scale times x; a dry run reads nothing else of x)
-void super_res(Run &r, const Map &x, int H2, int W2, bool want_image, float *img_sr, float *feature_lr, float *feature_hr) {
+// ONE sequencing, super_res(), over a plan of buffers.  The inference plan keeps what nothing reads again in shared storage; the
+// tape plan gives every layer a buffer of its own, for surs_encoder_super_res_backward to read.
+struct SrStage {   // a stride-2 stage's maps in the order it writes them, all h x w x c
+    int h, w, c, nb;   // nb: the residual blocks that run
+    float *buf[2 * 64 + 2];
+    Map at(int j) const { return input_map(buf[j], h, w, c, c); }
+    Map a(int b) const { return at(2 * b); }        // a(0): down's output, a(b + 1): block b's output
+    Map t(int b) const { return at(2 * b + 1); }    // block b's inner map (ReLU)
+    Map u() const { return at(2 * nb + 1); }        // tail.0's output
+};
+struct SrPlan {
+    Map up, fin, new3, new2, new1, new_fin;
+    Map t_last;          // last.0's output (p null: the image is not wanted)
+    Map shuffle_in[3];   // the convolutions in front of the shuffles: bott2's, ups2's, ups3's output
+    SrStage st[3];
+};
+
+void sr_stage_shapes(const SursEncoderNet &n, int H2, int W2, SrPlan &m) {
+    int hs = H2, ws = W2;
+    for (int i = 0; i < 3; ++i) {
+        hs = (hs + 2 - 3) / 2 + 1; ws = (ws + 2 - 3) / 2 + 1;
+        m.st[i].h = hs; m.st[i].w = ws; m.st[i].c = n.down[i].cout;
+        m.st[i].nb = n.residual ? n.n_block[i] : 0;
+    }
+}
+
+// Inference: three rotating buffers per stage (one stream: reuse is ordered), a temporary of its own per shuffle, feature_lr /
+// feature_hr written where the caller wants them.
+void sr_inference_maps(Run &r, int H2, int W2, bool want_image, float *feature_lr, float *feature_hr, SrPlan &m) {
     const SursEncoderNet &n = *r.net;
-    Map fin = r.map(H2, W2, 64);               // cat(h, up3)
-    Map new3 = r.map(H2 / 2, W2 / 2, 128);     // cat(d1_f, up2)
-    Map new2;                                  // cat(d2_f, up1) -> feature_lr: the caller's buffer
-    new2.p = feature_lr; new2.h = H2 / 4; new2.w = W2 / 4; new2.c = new2.ld = 256;
-    Map new1 = r.map(H2 / 8, W2 / 8, 512);     // cat(d3_f, bo)
-    Map up = r.map(H2, W2, 3);
+    m.fin = r.map(H2, W2, 64);                                  // cat(h, up3)
+    m.new3 = r.map(H2 / 2, W2 / 2, 128);                        // cat(d1_f, up2)
+    m.new2 = input_map(feature_lr, H2 / 4, W2 / 4, 256, 256);   // cat(d2_f, up1): the caller's buffer
+    m.new1 = r.map(H2 / 8, W2 / 8, 512);                        // cat(d3_f, bo)
+    m.up = r.map(H2, W2, 3);
+    sr_stage_shapes(n, H2, W2, m);
+    for (SrStage &s : m.st) {
+        float *three[3];
+        for (float *&b : three) b = r.map(s.h, s.w, s.c).p;
+        for (int j = 0; j < 2 * s.nb + 2; ++j) s.buf[j] = three[j % 3];   // (block b reads j = 2 b, writes 2 b + 1, then 2 b + 2)
+    }
+    m.shuffle_in[0] = r.map(m.new1.h, m.new1.w, n.bott2.cout);
+    m.shuffle_in[1] = r.map(m.new2.h, m.new2.w, n.ups2.cout);
+    m.shuffle_in[2] = r.map(m.new3.h, m.new3.w, n.ups3.cout);
+    m.new_fin = input_map(feature_hr, H2, W2, 64, 64);
+    m.t_last = want_image ? r.map(H2, W2, n.last0.cout) : Map();
+}
+
+// The tape: one buffer per layer.  THE LAYOUT OF THE TAPE IS THE ORDER OF THE TAKES BELOW - a function of the net and the image size
+// alone, so the forward and the backward find the same addresses by running this function.
+void sr_tape_maps(Run &r, int H2, int W2, SrPlan &m) {
+    const SursEncoderNet &n = *r.net;
+    m.up = r.map(H2, W2, 3);
+    m.fin = r.map(H2, W2, 64);
+    m.new3 = r.map(H2 / 2, W2 / 2, 128);
+    m.new2 = r.map(H2 / 4, W2 / 4, 256);       // = feature_lr
+    m.new1 = r.map(H2 / 8, W2 / 8, 512);
+    m.new_fin = r.map(H2, W2, 64);             // = feature_hr
+    m.t_last = r.map(H2, W2, n.last0.cout);
+    const Map shared = r.map(H2 / 2, W2 / 2, 128);   // the shuffles' inputs share one buffer (ups3's is the largest); nothing reads it back
+    m.shuffle_in[0] = input_map(shared.p, m.new1.h, m.new1.w, n.bott2.cout, n.bott2.cout);
+    m.shuffle_in[1] = input_map(shared.p, m.new2.h, m.new2.w, n.ups2.cout, n.ups2.cout);
+    m.shuffle_in[2] = input_map(shared.p, m.new3.h, m.new3.w, n.ups3.cout, n.ups3.cout);
+    sr_stage_shapes(n, H2, W2, m);
+    for (SrStage &s : m.st)
+        for (int j = 0; j < 2 * s.nb + 2; ++j) s.buf[j] = r.map(s.h, s.w, s.c).p;
+}
+
+// stage's block b, convolution `which` (0: in front of the ReLU, 1: behind it) in SursEncoderNet.body / SursSrParams.body
+inline int sr_body_index(const SursEncoderNet &n, int stage, int b, int which) {
+    int b0 = 0;
+    for (int i = 0; i < stage; ++i) b0 += n.n_block[i];
+    return 2 * (b0 + b) + which;
+}
+inline const SursConv *sr_body(const SursEncoderNet &n, int stage, int b, int which) { return &n.body[sr_body_index(n, stage, b, which)]; }
+inline const SursSrParam *sr_body(const SursEncoderNet &n, const SursSrParams *p, int stage, int b, int which) {
+    return &p->body[sr_body_index(n, stage, b, which)];
+}
+
+// x: the image; m.up's size is sr_scale times x's (a dry run reads nothing of x)
+void super_res(Run &r, const Map &x, const SrPlan &m, float *img_sr) {
+    const SursEncoderNet &n = *r.net;
+    Map up = m.up;
     if (sr_scale(&n) == 2) bicubic_up2(r, x, false, nullptr, up, false);
     else bicubic_up(r, x, sr_scale(&n), up);
-    Map h = fin.slice(0, 32);
+    Map h = m.fin.slice(0, 32);
     conv(r, up, n.head, h, 1, ACT, LRELU, nullptr);
-
-    int body0 = 0;
     auto stage = [&](int i, const Map &src, Map dst) {
-        const int ho = (src.h + 2 - 3) / 2 + 1, wo = (src.w + 2 - 3) / 2 + 1, c = n.down[i].cout;
-        Map buf[3] = {r.map(ho, wo, c), r.map(ho, wo, c), r.map(ho, wo, c)};
-        int d = 0;
-        conv(r, src, n.down[i], buf[d], 2, ACT, LRELU, nullptr);
-        if (n.residual) {
-            for (int b = 0; b < n.n_block[i]; ++b) {
-                const int t = (d + 1) % 3, d2 = (d + 2) % 3;
-                conv(r, buf[d], n.body[2 * (body0 + b)], buf[t], 1, ACT, RELU, nullptr);
-                conv(r, buf[t], n.body[2 * (body0 + b) + 1], buf[d2], 1, 0, 0.0f, &buf[d]);
-                d = d2;
-            }
+        const SrStage &s = m.st[i];
+        Map a = s.a(0), u = s.u();
+        conv(r, src, n.down[i], a, 2, ACT, LRELU, nullptr);
+        for (int b = 0; b < s.nb; ++b) {
+            Map t = s.t(b), a2 = s.a(b + 1);
+            conv(r, a, *sr_body(n, i, b, 0), t, 1, ACT, RELU, nullptr);
+            conv(r, t, *sr_body(n, i, b, 1), a2, 1, 0, 0.0f, &a);
+            a = a2;
         }
-        body0 += n.n_block[i];
-        const int t = (d + 1) % 3;
-        conv(r, buf[d], n.tail0[i], buf[t], 1, ACT, LRELU, nullptr);
-        conv(r, buf[t], n.tail2[i], dst, 1, ACT, LRELU, nullptr);
+        conv(r, a, n.tail0[i], u, 1, ACT, LRELU, nullptr);
+        conv(r, u, n.tail2[i], dst, 1, ACT, LRELU, nullptr);
         return dst;
     };
-    Map d1_f = stage(0, h, new3.slice(0, 64));
-    Map d2_f = stage(1, d1_f, new2.slice(0, 128));
-    Map d3_f = stage(2, d2_f, new1.slice(0, 256));
-    Map bo = new1.slice(256, 256);
+    Map d1_f = stage(0, h, m.new3.slice(0, 64));
+    Map d2_f = stage(1, d1_f, m.new2.slice(0, 128));
+    Map d3_f = stage(2, d2_f, m.new1.slice(0, 256));
+    Map bo = m.new1.slice(256, 256);
     conv(r, d3_f, n.bottleneck, bo, 1, ACT, LRELU, nullptr);
     // conv -> LeakyReLU -> PixelShuffle -> LeakyReLU (the second LeakyReLU is fused into the shuffle)
-    {
-        Map t = r.map(new1.h, new1.w, n.bott2.cout), o = new2.slice(128, 128);
-        conv(r, new1, n.bott2, t, 1, ACT, LRELU, nullptr);
-        pixel_shuffle2(r, t, 0.2f, o);
-    }
-    {
-        Map t = r.map(new2.h, new2.w, n.ups2.cout), o = new3.slice(64, 64);
-        conv(r, new2, n.ups2, t, 1, ACT, LRELU, nullptr);
-        pixel_shuffle2(r, t, 0.2f, o);
-    }
-    {
-        Map t = r.map(new3.h, new3.w, n.ups3.cout), o = fin.slice(32, 32);
-        conv(r, new3, n.ups3, t, 1, ACT, LRELU, nullptr);
-        pixel_shuffle2(r, t, 0.2f, o);
-    }
-    Map new_fin;
-    new_fin.p = feature_hr; new_fin.h = H2; new_fin.w = W2; new_fin.c = new_fin.ld = 64;
-    conv(r, fin, n.ups4, new_fin, 1, ACT, LRELU, nullptr);
-    if (want_image) {
-        Map t = r.map(H2, W2, n.last0.cout), o;
-        o.p = img_sr; o.h = H2; o.w = W2; o.c = o.ld = 3;
+    auto shuffle = [&](const Map &src, const SursConv &cw, Map t, Map dst) {
+        conv(r, src, cw, t, 1, ACT, LRELU, nullptr);
+        pixel_shuffle2(r, t, 0.2f, dst);
+    };
+    shuffle(m.new1, n.bott2, m.shuffle_in[0], m.new2.slice(128, 128));
+    shuffle(m.new2, n.ups2, m.shuffle_in[1], m.new3.slice(64, 64));
+    shuffle(m.new3, n.ups3, m.shuffle_in[2], m.fin.slice(32, 32));
+    Map new_fin = m.new_fin;
+    conv(r, m.fin, n.ups4, new_fin, 1, ACT, LRELU, nullptr);
+    if (m.t_last.p) {
+        Map t = m.t_last, o = input_map(img_sr, new_fin.h, new_fin.w, 3, 3);
         conv(r, new_fin, n.last0, t, 1, ACT, LRELU, nullptr);
         conv(r, t, n.last2, o, 1, 0, 0.0f, nullptr);
     }
@@ -267,23 +359,34 @@ const SursBatchNorm *batchnorm_of(const Run &r, const SursConvBlock *b) {
     return n.bn_top_m + 3 * (b - n.top_m);
 }
 
-Map conv_block(Run &r, const SursConvBlock &b, const Map &x, bool want_stats) {
+// What a ConvBlock leaves for its backward (surs_encoder_convblock_backward): its input, the raw cat(o1, o2, o3), the sum in a map
+// of its own and, per norm site, the coefficient vectors surs_groupnorm_fold forms from what the forward's kernels folded themselves.
+struct NormTape { float *mean, *rstd, *scale, *shift; };
+struct BlockTape {
+    Map x, cat, out;
+    NormTape nt[3];
+};
+
+// t: record the block - the separate-sum forms only (the launches of the host mirror, encoder.py), the sum into a map of its own;
+// a GroupNorm net's (the gradient entry points refuse --norm batch)
+Map conv_block(Run &r, const SursConvBlock &b, const Map &x, bool want_stats, BlockTape *t = nullptr) {
     const int c = x.c;
-    Map out = r.map(x.h, x.w, c);
-    Map o1 = out.slice(0, c / 2), o2 = out.slice(c / 2, c / 4), o3 = out.slice(3 * c / 4, c / 4);
-    auto eligible = [&](const Map &t, const SursConv &cw) {
-        return (cw.ksize == 1 || cw.ksize == 3) && cw.w_split && t.c % 32 == 0 && t.ld % 4 == 0 && aligned16(t.p);
+    Map cat = r.map(x.h, x.w, c);
+    Map out = t ? r.map(x.h, x.w, c) : cat;   // (without a tape the sum overwrites the slices)
+    Map o1 = cat.slice(0, c / 2), o2 = cat.slice(c / 2, c / 4), o3 = cat.slice(3 * c / 4, c / 4);
+    auto eligible = [&](const Map &m, const SursConv &cw) {
+        return (cw.ksize == 1 || cw.ksize == 3) && cw.w_split && m.c % 32 == 0 && m.ld % 4 == 0 && aligned16(m.p);
     };
     const bool fused = c % 128 == 0 && eligible(x, b.conv[0]) && eligible(o1, b.conv[1]) && eligible(o2, b.conv[2]);
-    auto coeffs = [&](const Map &t, const SursGroupNorm &g, float *&sc, float *&sh) {
-        sc = (float *)r.a->take(sizeof(float) * t.c);
-        sh = (float *)r.a->take(sizeof(float) * t.c);
+    auto coeffs = [&](const Map &m, const SursGroupNorm &g, float *&sc, float *&sh) {
+        sc = (float *)r.a->take(sizeof(float) * m.c);
+        sh = (float *)r.a->take(sizeof(float) * m.c);
         void *scratch = r.a->take(surs_groupnorm_scratch_bytes());
-        if (!r.dry && !r.rc) r.fail(surs_groupnorm_coeffs_ws(t.p, t.h * t.w, t.c, t.ld, 32, 1e-5f, g.gamma, g.beta, sc, sh, scratch, r.st));
+        if (!r.dry && !r.rc) r.fail(surs_groupnorm_coeffs_ws(m.p, m.h * m.w, m.c, m.ld, 32, 1e-5f, g.gamma, g.beta, sc, sh, scratch, r.st));
     };
     // (the second output is made by the kernels' whole-tile epilogue: maps of whole 8-row x 32-column x 64-channel tiles - every map
     //  of a 512 x 512 image's hourglass; smaller ones take the separate sum)
-    const bool sum_in_conv = fused && !(r.net->flags & SURS_ENC_SEPARATE_SUM) && b.conv[0].ksize == 3 && b.conv[1].ksize == 3 &&
+    const bool sum_in_conv = !t && fused && !(r.net->flags & SURS_ENC_SEPARATE_SUM) && b.conv[0].ksize == 3 && b.conv[1].ksize == 3 &&
                              b.conv[2].ksize == 3 && x.w % 32 == 0 && x.h % 8 == 0 && c % 256 == 0;
     if (const SursBatchNorm *bn = batchnorm_of(r, &b)) {
         // BatchNorm in eval mode: the three normalisations are the caller's constants in the convolutions' staging, the same launches
@@ -333,21 +436,44 @@ Map conv_block(Run &r, const SursConvBlock &b, const Map &x, bool want_stats) {
         if (!S) out.set_stats(nullptr, 0);
         return out;
     }
+    Map ins[3] = {x, o1, o2}, outs[3] = {o1, o2, o3};
+    if (t) {
+        t->x = x; t->cat = cat; t->out = out;
+        for (int k = 0; k < 3; ++k) {
+            NormTape &v = t->nt[k];
+            v.mean = (float *)r.a->take(sizeof(float) * 32);
+            v.rstd = (float *)r.a->take(sizeof(float) * 32);
+            v.scale = (float *)r.a->take(sizeof(float) * ins[k].c);
+            v.shift = (float *)r.a->take(sizeof(float) * ins[k].c);
+        }
+    }
+    auto fold = [&](int k, const SursGnStats *st, void *scratch) {   // the tape's vectors of norm k: from statistics, or from the map
+        if (r.dry || r.rc) return;
+        const NormTape &v = t->nt[k];
+        r.fail(surs_groupnorm_fold(st, st ? nullptr : ins[k].p, x.h * x.w, ins[k].c, ins[k].ld, 1e-5f, b.bn[k].gamma, b.bn[k].beta, v.mean, v.rstd,
+                                   v.scale, v.shift, scratch, r.st));
+    };
     if (fused && x.st.sums && x.st.g1 == 0) {
-        conv_gn(r, x, b.conv[0], o1, &b.bn[0], true);
-        conv_gn(r, o1, b.conv[1], o2, &b.bn[1], true);
-        conv_gn(r, o2, b.conv[2], o3, &b.bn[2], false);
-        add3(r, out, x, out, want_stats);
+        for (int k = 0; k < 3; ++k) {
+            conv_gn(r, ins[k], b.conv[k], outs[k], &b.bn[k], k < 2);
+            if (k < 2) ins[k + 1].st = outs[k].st;   // (the slice the next convolution reads, with the statistics this one left)
+            if (t) fold(k, &ins[k].st, nullptr);
+        }
+        add3(r, cat, x, out, want_stats);
         return out;
     }
-    const Map ins[3] = {x, o1, o2};
-    Map outs[3] = {o1, o2, o3};
+    void *scratch = t ? r.a->take(surs_groupnorm_scratch_bytes()) : nullptr;
     for (int k = 0; k < 3; ++k) {
         float *sc, *sh;
-        coeffs(ins[k], b.bn[k], sc, sh);
+        if (t) {
+            fold(k, nullptr, scratch);
+            sc = t->nt[k].scale; sh = t->nt[k].shift;
+        } else {
+            coeffs(ins[k], b.bn[k], sc, sh);
+        }
         conv(r, ins[k], b.conv[k], outs[k], 1, 0, 0.0f, nullptr, sc, sh);
     }
-    add3(r, out, x, out, want_stats && fused);
+    add3(r, cat, x, out, want_stats && fused);
     return out;
 }
 
@@ -362,45 +488,38 @@ struct Events {   // per host thread: the events of the hourglass forks (created
 };
 thread_local Events t_events;
 
+// Where the blocks of an hourglass's levels are in the stack's block array: the module order of HourGlass._generate_network
+// (lib/model/HGFilters.py:85-94; encoder.EncoderWeights, include/surs.h), b1_d, b2_d, [level d - 1 ...], b2_plus_1, b3_1, ..., b3_d.
+// The forward, its tape and the backward all walk this one table.
+struct HgLevel { int b1, b2, b2_plus, b3; };   // b2_plus: level 1 only
+constexpr int HG_MAX_DEPTH = 4, HG_MAX_BLOCKS = 3 * HG_MAX_DEPTH + 1;
+void hg_levels(int depth, HgLevel lv[HG_MAX_DEPTH + 1]) {   // lv[1 .. depth]
+    for (int level = depth; level >= 1; --level) lv[level] = HgLevel{2 * (depth - level), 2 * (depth - level) + 1, -1, 2 * depth + level};
+    lv[1].b2_plus = 2 * depth;
+}
+
 // HourGlass._forward (lib/model/HGFilters.py:96-117).  The two branches of a level are independent until their sum: with side
 // streams lent by the caller the low-resolution one (pool -> ConvBlock -> [next level] -> ConvBlock) runs beside the
-// full-resolution ConvBlock, ordered by events at the fork and the join.
-Map hourglass(Run &r, const SursConvBlock *blocks, int depth, const Map &x, const SursEncoderStreams *ss) {
-    // block order (encoder.EncoderWeights / include/surs.h): b1_d, b2_d, [level d - 1 ...], b2_plus_1, b3_1, ..., b3_d
-    int next_block = 0;
-    struct Level { const SursConvBlock *b1, *b2, *b2_plus, *b3; };
-    Level lv[8];
-    {
-        // gen(level): b1, b2, then gen(level - 1) or b2_plus, then b3
-        struct Gen {
-            const SursConvBlock *blocks; int *next; Level *lv;
-            void run(int level) {
-                lv[level].b1 = blocks + (*next)++;
-                lv[level].b2 = blocks + (*next)++;
-                lv[level].b2_plus = nullptr;
-                if (level > 1) run(level - 1); else lv[level].b2_plus = blocks + (*next)++;
-                lv[level].b3 = blocks + (*next)++;
-            }
-        } g{blocks, &next_block, lv};
-        g.run(depth);
-    }
-    int ev = 0;
+// full-resolution ConvBlock, ordered by events at the fork and the join.  tape (one stream only): where block i records itself,
+// [3 depth + 1] in the order of `blocks`.
+Map hourglass(Run &r, const SursConvBlock *blocks, int depth, const Map &x, const SursEncoderStreams *ss, BlockTape *tape = nullptr) {
     struct Fwd {
-        Run &r; Level *lv; const SursEncoderStreams *ss; int *ev;
+        Run &r; const SursConvBlock *blocks; const SursEncoderStreams *ss; BlockTape *tape;
+        HgLevel lv[HG_MAX_DEPTH + 1];
+        int ev = 0;
+        Map block(int i, const Map &inp, bool want_stats) { return conv_block(r, blocks[i], inp, want_stats, tape ? tape + i : nullptr); }
         Map low_branch(int level, const Map &inp) {
             Map pooled = avgpool2(r, inp, !r.bn());
-            Map low1 = conv_block(r, *lv[level].b2, pooled, true);
-            Map low2;
-            if (level > 1) low2 = run(level - 1, low1);
-            else low2 = conv_block(r, *lv[level].b2_plus, low1, true);
-            return conv_block(r, *lv[level].b3, low2, false);
+            Map low1 = block(lv[level].b2, pooled, true);
+            Map low2 = level > 1 ? run(level - 1, low1) : block(lv[level].b2_plus, low1, true);
+            return block(lv[level].b3, low2, false);
         }
         Map run(int level, const Map &inp) {
             hipStream_t side = (ss && level <= 4) ? (hipStream_t)ss->side[level - 1] : nullptr;
             hipEvent_t e_fork = nullptr, e_join = nullptr;
             if (side && !r.dry) {
-                e_fork = t_events.get((*ev)++);
-                e_join = t_events.get((*ev)++);
+                e_fork = t_events.get(ev++);
+                e_join = t_events.get(ev++);
                 if (!e_fork || !e_join) side = nullptr;
             }
             Map up1, low3;
@@ -411,11 +530,11 @@ Map hourglass(Run &r, const SursConvBlock *blocks, int depth, const Map &x, cons
                 r.st = side;
                 low3 = low_branch(level, inp);
                 r.st = cur;
-                up1 = conv_block(r, *lv[level].b1, inp, false);
+                up1 = block(lv[level].b1, inp, false);
                 if (hipEventRecord(e_join, side) != hipSuccess || hipStreamWaitEvent(cur, e_join, 0) != hipSuccess)
                     r.fail(fail(SURS_E_HIP, "encoder: join of the hourglass streams failed"));
             } else {
-                up1 = conv_block(r, *lv[level].b1, inp, false);
+                up1 = block(lv[level].b1, inp, false);
                 low3 = low_branch(level, inp);
             }
             Map out = r.map(2 * low3.h, 2 * low3.w, low3.c);
@@ -423,7 +542,8 @@ Map hourglass(Run &r, const SursConvBlock *blocks, int depth, const Map &x, cons
             else bicubic_up2(r, low3, true, &up1, out, true);   // up1 + up2
             return out;
         }
-    } f{r, lv, ss, &ev};
+    } f{r, blocks, ss, tape};
+    hg_levels(depth, f.lv);
     return f.run(depth, x);
 }
 
@@ -447,8 +567,7 @@ void filter_lr(Run &r, const Map &feature_lr, float *const *outs, const SursEnco
             const SursBatchNorm &be = n.bn_end_bn[s];
             conv(r, ll, n.conv_last[s], t, 1, 0, 0.0f, nullptr);
             if (outs[s]) {
-                Map o;
-                o.p = outs[s]; o.h = t.h; o.w = t.w; o.c = o.ld = n.l[s].cout;
+                Map o = input_map(outs[s], t.h, t.w, n.l[s].cout, n.l[s].cout);
                 conv(r, t, n.l[s], o, 1, 0, 0.0f, nullptr, be.scale, be.shift);
             }
             if (!last) {
@@ -460,8 +579,7 @@ void filter_lr(Run &r, const Map &feature_lr, float *const *outs, const SursEnco
         }
         conv_gn(r, ll, n.conv_last[s], t, nullptr, true);
         if (outs[s]) {
-            Map o;
-            o.p = outs[s]; o.h = t.h; o.w = t.w; o.c = o.ld = n.l[s].cout;
+            Map o = input_map(outs[s], t.h, t.w, n.l[s].cout, n.l[s].cout);
             conv_gn(r, t, n.l[s], o, &n.bn_end[s], false);
         }
         if (!last) {
@@ -508,10 +626,23 @@ int check_image_size(const SursEncoderNet *n, int h, int w) {
     return 0;
 }
 
-Map input_map(const float *x, int h, int w, int c, int ld) {
-    Map m;
-    m.p = const_cast<float *>(x); m.h = h; m.w = w; m.c = c; m.ld = ld;
-    return m;
+float *const NOWHERE = reinterpret_cast<float *>(4096);   // a pointer for runs without launches
+
+// the bytes super_res() takes from its workspace
+size_t sr_inference_need(const SursEncoderNet *net, int eh, int ew, bool want_image) {
+    Dry d(net);
+    SrPlan m;
+    sr_inference_maps(d.r, eh, ew, want_image, NOWHERE, NOWHERE, m);
+    return d.a.peak;
+}
+
+// the bytes of each of filter_lr()'s two arenas: the same sequencing, counted
+size_t filter_lr_half(const SursEncoderNet *net, int h, int w, int ld, float *const *outs) {
+    Arena ar[2];
+    ar[0].dry = ar[1].dry = true;
+    Run r{net, &ar[0], nullptr, net->parts, true};
+    filter_lr(r, input_map(NOWHERE, h, w, 256, ld), outs, nullptr, ar);
+    return align_up(ar[0].peak > ar[1].peak ? ar[0].peak : ar[1].peak, 256);
 }
 
 }  // namespace
@@ -519,18 +650,10 @@ Map input_map(const float *x, int h, int w, int c, int ld) {
 extern "C" size_t surs_encoder_workspace_bytes_enlarged(const SursEncoderNet *net, int eh, int ew) {
     if (!net || eh <= 0 || ew <= 0 || check_net(net)) return 0;
     // the stages run one after the other on one workspace: the largest of them; filter_lr = two arenas
-    Arena a;
-    a.dry = true;
-    Run r{net, &a, nullptr, net->parts, true};
-    super_res(r, input_map(nullptr, 0, 0, 3, 3), eh, ew, true, nullptr, reinterpret_cast<float *>(4096), reinterpret_cast<float *>(4096));
-    const size_t sr = align_up(a.peak, 256);
-    Arena ar[2];
-    ar[0].dry = ar[1].dry = true;
-    Run r2{net, &ar[0], nullptr, net->parts, true};
+    const size_t sr = align_up(sr_inference_need(net, eh, ew, true), 256);
     float *outs[16];
-    for (int s = 0; s < 16; ++s) outs[s] = reinterpret_cast<float *>(4096);
-    filter_lr(r2, input_map(reinterpret_cast<const float *>(4096), eh / 4, ew / 4, 256, 256), outs, nullptr, ar);
-    const size_t half = align_up(ar[0].peak > ar[1].peak ? ar[0].peak : ar[1].peak, 256);
+    for (int s = 0; s < 16; ++s) outs[s] = NOWHERE;
+    const size_t half = filter_lr_half(net, eh / 4, ew / 4, 256, outs);
     return (sr > 2 * half ? sr : 2 * half) + 256;
 }
 
@@ -546,18 +669,13 @@ extern "C" int surs_encoder_super_res(const SursEncoderNet *net, const float *x,
     if (int rc = check_image_size(net, h, w)) return rc;
     SURS_REQUIRE(x_ld >= 3, "input image: three channels");
     const int eh = sr_scale(net) * h, ew = sr_scale(net) * w;
+    const size_t need = sr_inference_need(net, eh, ew, want_image != 0);
     Arena a;
-    a.base = (char *)align_up((size_t)workspace, 256);
-    a.cap = workspace_bytes - (size_t)(a.base - (char *)workspace);
-    {   // enough room?  (the same sequencing, counted)
-        Arena d;
-        d.dry = true;
-        Run rd{net, &d, nullptr, net->parts, true};
-        super_res(rd, input_map(nullptr, h, w, 3, 3), eh, ew, want_image != 0, nullptr, reinterpret_cast<float *>(4096), reinterpret_cast<float *>(4096));
-        SURS_REQUIRE(d.peak <= a.cap, "workspace too small: %zu bytes needed", d.peak + 256);
-    }
+    SURS_REQUIRE(workspace_arena(workspace, workspace_bytes, need, a), "workspace too small: %zu bytes needed", need + 256);
     Run r{net, &a, as_stream(stream), net->parts, false};
-    super_res(r, input_map(x, h, w, 3, x_ld), eh, ew, want_image != 0, img_sr, feature_lr, feature_hr);
+    SrPlan m;
+    sr_inference_maps(r, eh, ew, want_image != 0, feature_lr, feature_hr, m);
+    super_res(r, input_map(x, h, w, 3, x_ld), m, img_sr);
     return r.rc;
 }
 
@@ -571,18 +689,11 @@ extern "C" int surs_encoder_filter_lr(const SursEncoderNet *net, const float *fe
         const int d = net->l[s].cout;
         SURS_REQUIRE(d >= 16 && d <= 512 && d % 16 == 0, "hg_dim %d: the supported values are the multiples of 16 from 16 to 512", d);
     }
-    Arena dr[2];
-    dr[0].dry = dr[1].dry = true;
-    {
-        Run rd{net, &dr[0], nullptr, net->parts, true};
-        filter_lr(rd, input_map(reinterpret_cast<const float *>(4096), h, w, 256, ld), outs, nullptr, dr);
-    }
-    const size_t half = align_up(dr[0].peak > dr[1].peak ? dr[0].peak : dr[1].peak, 256);
-    char *base = (char *)align_up((size_t)workspace, 256);
-    SURS_REQUIRE(2 * half + (size_t)(base - (char *)workspace) <= workspace_bytes, "workspace too small: %zu bytes needed", 2 * half + 256);
+    const size_t half = filter_lr_half(net, h, w, ld, outs);
     Arena ar[2];
-    ar[0].base = base; ar[0].cap = half;
-    ar[1].base = base + half; ar[1].cap = half;
+    SURS_REQUIRE(workspace_arena(workspace, workspace_bytes, 2 * half, ar[0]), "workspace too small: %zu bytes needed", 2 * half + 256);
+    ar[0].cap = ar[1].cap = half;
+    ar[1].base = ar[0].base + half;
     Run r{net, &ar[0], as_stream(stream), net->parts, false};
     filter_lr(r, input_map(feature_lr, h, w, 256, ld), outs, streams, ar);
     return r.rc;
@@ -593,8 +704,7 @@ extern "C" int surs_encoder_filter_hr(const SursEncoderNet *net, const float *fe
     SURS_REQUIRE(feature_hr && out && h > 0 && w > 0, "null argument");
     Arena a;
     Run r{net, &a, as_stream(stream), net->parts, false};
-    Map o;
-    o.p = out; o.h = h; o.w = w; o.c = o.ld = net->conv5.cout;
+    Map o = input_map(out, h, w, net->conv5.cout, net->conv5.cout);
     conv(r, input_map(feature_hr, h, w, net->conv5.cin, ld), net->conv5, o, 1, 0, 0.0f, nullptr);
     return r.rc;
 }
@@ -614,57 +724,9 @@ extern "C" int surs_encoder_forward(const SursEncoderNet *net, const float *imag
 }
 
 // ---------------------------------------------------------------- super-resolution gradients (include/surs.h)
-// surs_encoder_super_res_train is super_res() + conv5 on ONE buffer per layer (the tape); surs_encoder_super_res_backward walks the
-// same maps in reverse on the primitives of surs_sr_grad.hip.  Both lay the tape out with sr_tape_maps(): the map addresses are a
-// function of the net and the image size alone.
-#include <vector>
-
+// surs_encoder_super_res_train is super_res() over the tape plan (sr_tape_maps(): ONE buffer per layer) + conv5;
+// surs_encoder_super_res_backward walks the same maps in reverse on the primitives of surs_sr_grad.hip.
 namespace {
-
-struct SrStage {
-    std::vector<Map> a, t;   // a[0]: down's output, a[b + 1]: block b's output; t[b]: block b's inner map (ReLU)
-    Map u;                   // tail.0's output
-};
-struct SrTape {
-    Map up, fin, new3, new2, new1, new_fin, t_last, shuffle_in;
-    SrStage st[3];
-};
-
-void sr_tape_maps(Run &r, int H2, int W2, SrTape &m) {
-    const SursEncoderNet &n = *r.net;
-    m.up = r.map(H2, W2, 3);
-    m.fin = r.map(H2, W2, 64);                 // cat(h, up3)
-    m.new3 = r.map(H2 / 2, W2 / 2, 128);       // cat(d1_f, up2)
-    m.new2 = r.map(H2 / 4, W2 / 4, 256);       // cat(d2_f, up1) = feature_lr
-    m.new1 = r.map(H2 / 8, W2 / 8, 512);       // cat(d3_f, bo)
-    m.new_fin = r.map(H2, W2, 64);             // feature_hr
-    m.t_last = r.map(H2, W2, n.last0.cout);
-    m.shuffle_in = r.map(H2 / 2, W2 / 2, 128); // the convolution in front of a shuffle (ups3's is the largest); nothing reads it back
-    int hs = H2, ws = W2;
-    for (int i = 0; i < 3; ++i) {
-        hs = (hs + 2 - 3) / 2 + 1; ws = (ws + 2 - 3) / 2 + 1;
-        const int c = n.down[i].cout, nb = n.residual ? n.n_block[i] : 0;
-        SrStage &s = m.st[i];
-        s.a.clear(); s.t.clear();
-        s.a.push_back(r.map(hs, ws, c));
-        for (int b = 0; b < nb; ++b) {
-            s.t.push_back(r.map(hs, ws, c));
-            s.a.push_back(r.map(hs, ws, c));
-        }
-        s.u = r.map(hs, ws, c);
-    }
-}
-
-inline const SursConv *sr_body(const SursEncoderNet &n, int stage, int b, int which) {
-    int b0 = 0;
-    for (int i = 0; i < stage; ++i) b0 += n.n_block[i];
-    return &n.body[2 * (b0 + b) + which];
-}
-inline const SursSrParam *sr_body(const SursEncoderNet &n, const SursSrParams *p, int stage, int b, int which) {
-    int b0 = 0;
-    for (int i = 0; i < stage; ++i) b0 += n.n_block[i];
-    return &p->body[2 * (b0 + b) + which];
-}
 
 // the shapes the backward's fixed channel slices rest on (the released SuRSSR_v3; the forward's cat() buffers assume the same)
 int check_sr_shapes(const SursEncoderNet *n) {
@@ -690,60 +752,18 @@ int check_sr_train(const SursEncoderNet *net, int h, int w) {
     return check_image_size(net, h, w);
 }
 
-void sr_train_forward(Run &r, const Map &x, SrTape &m, float *img_sr, float *im_feat_hr) {
-    const SursEncoderNet &n = *r.net;
-    if (sr_scale(&n) == 2) bicubic_up2(r, x, false, nullptr, m.up, false);
-    else bicubic_up(r, x, sr_scale(&n), m.up);
-    Map h = m.fin.slice(0, 32);
-    conv(r, m.up, n.head, h, 1, ACT, LRELU, nullptr);
-    auto stage = [&](int i, const Map &src, Map dst) {
-        SrStage &s = m.st[i];
-        conv(r, src, n.down[i], s.a[0], 2, ACT, LRELU, nullptr);
-        const int nb = (int)s.t.size();
-        for (int b = 0; b < nb; ++b) {
-            conv(r, s.a[b], *sr_body(n, i, b, 0), s.t[b], 1, ACT, RELU, nullptr);
-            conv(r, s.t[b], *sr_body(n, i, b, 1), s.a[b + 1], 1, 0, 0.0f, &s.a[b]);
-        }
-        conv(r, s.a[nb], n.tail0[i], s.u, 1, ACT, LRELU, nullptr);
-        conv(r, s.u, n.tail2[i], dst, 1, ACT, LRELU, nullptr);
-        return dst;
-    };
-    Map d1_f = stage(0, h, m.new3.slice(0, 64));
-    Map d2_f = stage(1, d1_f, m.new2.slice(0, 128));
-    Map d3_f = stage(2, d2_f, m.new1.slice(0, 256));
-    Map bo = m.new1.slice(256, 256);
-    conv(r, d3_f, n.bottleneck, bo, 1, ACT, LRELU, nullptr);
-    auto shuffle = [&](const Map &src, const SursConv &cw, Map dst) {
-        Map t = m.shuffle_in;
-        t.h = src.h; t.w = src.w; t.c = t.ld = cw.cout;
-        conv(r, src, cw, t, 1, ACT, LRELU, nullptr);
-        pixel_shuffle2(r, t, 0.2f, dst);
-    };
-    shuffle(m.new1, n.bott2, m.new2.slice(128, 128));
-    shuffle(m.new2, n.ups2, m.new3.slice(64, 64));
-    shuffle(m.new3, n.ups3, m.fin.slice(32, 32));
-    conv(r, m.fin, n.ups4, m.new_fin, 1, ACT, LRELU, nullptr);
-    Map o;
-    o.p = img_sr; o.h = m.fin.h; o.w = m.fin.w; o.c = o.ld = 3;
-    conv(r, m.new_fin, n.last0, m.t_last, 1, ACT, LRELU, nullptr);
-    conv(r, m.t_last, n.last2, o, 1, 0, 0.0f, nullptr);
-    Map f;
-    f.p = im_feat_hr; f.h = m.fin.h; f.w = m.fin.w; f.c = f.ld = n.conv5.cout;
-    conv(r, m.new_fin, n.conv5, f, 1, 0, 0.0f, nullptr);
-}
-
-size_t sr_wgrad_bytes(const Map &out, const SursConv &cw) { return surs_conv_grad_weight_workspace_bytes(out.h, out.w, cw.cin, cw.cout, cw.ksize); }
+constexpr float LRELU2 = 0.2f * 0.2f;   // LeakyReLU(LeakyReLU(z)) below zero
 
 struct SrBack {
     Run &r;
     const SursSrParams *P, *G;
     int acc;
     void *wws = nullptr;        // the weight gradient's slabs
-    size_t wws_bytes = 0, wws_need = 0;
+    size_t wws_bytes = 0, wws_need = 0;   // wws_need: the largest slab any wgrad() so far asked for
 
     // dW, db of the convolution x -> (pre-activation of) y from g = d L / d y
     void wgrad(const Map &g, const Map *y, float slope, const Map &x, const SursConv &cw, int stride, const SursSrParam &gp) {
-        const size_t need = sr_wgrad_bytes(g, cw);
+        const size_t need = surs_conv_grad_weight_workspace_bytes(g.h, g.w, cw.cin, cw.cout, cw.ksize);
         if (need > wws_need) wws_need = need;
         if (r.dry || r.rc) return;
         r.fail(surs_conv_grad_weight(g.p, g.h, g.w, cw.cout, g.ld, y ? y->p : nullptr, y ? y->ld : 0, slope, x.p, x.h, x.w, cw.cin, x.ld, cw.ksize,
@@ -766,140 +786,129 @@ struct SrBack {
         if (hipMemcpyAsync(dst.p, src, sizeof(float) * dst.h * dst.w * dst.c, hipMemcpyDeviceToDevice, r.st) != hipSuccess)
             r.fail(fail(SURS_E_HIP, "super-resolution gradients: hipMemcpyAsync failed"));
     }
+    void unshuffle(const Map &g_o, const Map &y, const Map &t) {   // g of a shuffle's output (stored: y) -> g of its input
+        if (r.dry || r.rc) return;
+        r.fail(surs_pixel_unshuffle2_grad(g_o.p, t.h, t.w, g_o.c, g_o.ld, y.p, y.ld, LRELU2, t.p, t.ld, r.st));
+    }
+    void add(const Map &g, const Map &into) {   // into += g
+        if (r.dry || r.rc) return;
+        r.fail(surs_add3(into.p, into.ld, g.p, g.ld, nullptr, 0, into.h * into.w, into.c, into.p, into.ld, r.st));
+    }
 };
 
-constexpr float LRELU2 = 0.2f * 0.2f;   // LeakyReLU(LeakyReLU(z)) below zero
-
 // r.a: the workspace arena (the gradient maps, then the weight gradient's slabs)
-void sr_backward(SrBack &k, const SrTape &m, const float *g_img, const float *g_lr, const float *g_hr) {
-    Run &r = k.r;
+void sr_backward(SrBack &run, const SrPlan &m, const float *g_img_sr, const float *g_feature_lr, const float *g_im_feat_hr) {
+    Run &r = run.r;
     const SursEncoderNet &n = *r.net;
     const int H2 = m.fin.h, W2 = m.fin.w;
     Map g_newfin = r.map(H2, W2, 64), g_tlast = r.map(H2, W2, n.last0.cout), g_fin = r.map(H2, W2, 64);
     Map g_new3 = r.map(H2 / 2, W2 / 2, 128), g_new2 = r.map(H2 / 4, W2 / 4, 256), g_new1 = r.map(H2 / 8, W2 / 8, 512);
     Map dzt = r.map(H2 / 2, W2 / 2, 128);   // the gradient in front of a shuffle (ups3's is the largest)
     Map pq[2] = {r.map(H2 / 2, W2 / 2, 32), r.map(H2 / 2, W2 / 2, 32)};   // the two gradient maps a stage alternates between
-    {   // the slabs: the largest any layer needs (a dry pass over the same calls below finds it)
-        SrBack d{r, k.P, k.G, k.acc};
-        const bool was_dry = r.dry;
-        r.dry = true;
-        auto need = [&](int hh, int ww, const SursConv &cw) {
-            Map o; o.h = hh; o.w = ww;
-            const size_t b = sr_wgrad_bytes(o, cw);
-            if (b > d.wws_need) d.wws_need = b;
-        };
-        need(H2, W2, n.last2); need(H2, W2, n.last0); need(H2, W2, n.conv5); need(H2, W2, n.ups4); need(H2, W2, n.head);
-        need(H2 / 2, W2 / 2, n.ups3); need(H2 / 4, W2 / 4, n.ups2); need(H2 / 8, W2 / 8, n.bott2); need(H2 / 8, W2 / 8, n.bottleneck);
-        for (int i = 0; i < 3; ++i) {
-            need(m.st[i].u.h, m.st[i].u.w, n.down[i]);
-            need(m.st[i].u.h, m.st[i].u.w, n.tail0[i]);   // (the blocks: the same shape)
-            need(m.st[i].u.h, m.st[i].u.w, n.tail2[i]);
+    auto walk = [&](SrBack &k, const float *g_img, const float *g_lr, const float *g_hr) {
+        const bool top = g_img || g_hr;   // does any gradient reach feature_hr?
+        if (g_img) {
+            const Map gi = input_map(g_img, H2, W2, 3, 3);
+            k.wgrad(gi, nullptr, 1.0f, m.t_last, n.last2, 1, k.G->last2);
+            k.dgrad(gi, nullptr, 1.0f, n.last2, k.P->last2, 1, g_tlast, false);
+            k.wgrad(g_tlast, &m.t_last, LRELU, m.new_fin, n.last0, 1, k.G->last0);
+            k.dgrad(g_tlast, &m.t_last, LRELU, n.last0, k.P->last0, 1, g_newfin, false);
+        } else {
+            k.zero(n.last2, k.G->last2);
+            k.zero(n.last0, k.G->last0);
         }
-        r.dry = was_dry;
-        k.wws_bytes = d.wws_need;
-        k.wws = r.a->take(k.wws_bytes);
+        if (g_hr) {
+            const Map gh = input_map(g_hr, H2, W2, n.conv5.cout, n.conv5.cout);
+            k.wgrad(gh, nullptr, 1.0f, m.new_fin, n.conv5, 1, k.G->conv5);
+            k.dgrad(gh, nullptr, 1.0f, n.conv5, k.P->conv5, 1, g_newfin, g_img != nullptr);
+        } else {
+            k.zero(n.conv5, k.G->conv5);
+        }
+        // a shuffle level: g of the shuffled slice `o` (stored output `y`) -> the convolution cw on src; the gradient of src replaces g_src
+        auto unshuffle = [&](const Map &g_o, const Map &y, const Map &src, const SursConv &cw, const SursSrParam &p, const SursSrParam &gp,
+                             const Map &g_src) {
+            const Map t = input_map(dzt.p, src.h, src.w, cw.cout, cw.cout);
+            k.unshuffle(g_o, y, t);
+            k.wgrad(t, nullptr, 1.0f, src, cw, 1, gp);
+            k.dgrad(t, nullptr, 1.0f, cw, p, 1, g_src, false);
+        };
+        if (top) {
+            k.wgrad(g_newfin, &m.new_fin, LRELU, m.fin, n.ups4, 1, k.G->ups4);
+            k.dgrad(g_newfin, &m.new_fin, LRELU, n.ups4, k.P->ups4, 1, g_fin, false);
+            unshuffle(g_fin.slice(32, 32), m.fin.slice(32, 32), m.new3, n.ups3, k.P->ups3, k.G->ups3, g_new3);
+            unshuffle(g_new3.slice(64, 64), m.new3.slice(64, 64), m.new2, n.ups2, k.P->ups2, k.G->ups2, g_new2);
+            if (g_lr) k.add(input_map(g_lr, g_new2.h, g_new2.w, 256, 256), g_new2);   // feature_lr's own gradient joins ups2's
+        } else {
+            k.zero(n.ups4, k.G->ups4);
+            k.zero(n.ups3, k.G->ups3);
+            k.zero(n.ups2, k.G->ups2);
+            k.copy(g_lr, g_new2);
+        }
+        unshuffle(g_new2.slice(128, 128), m.new2.slice(128, 128), m.new1, n.bott2, k.P->bott2, k.G->bott2, g_new1);
+        {
+            Map g_bo = g_new1.slice(256, 256), bo = m.new1.slice(256, 256), d3_f = m.new1.slice(0, 256);
+            k.wgrad(g_bo, &bo, LRELU, d3_f, n.bottleneck, 1, k.G->bottleneck);
+            k.dgrad(g_bo, &bo, LRELU, n.bottleneck, k.P->bottleneck, 1, g_new1.slice(0, 256), true);
+        }
+        // a stage in reverse: g_dst = d L / d dst (all consumers added), its input's gradient is added to (or, live == false, replaces) g_src
+        auto stage = [&](int i, const Map &src, const Map &dst, const Map &g_dst, const Map &g_src, bool live) {
+            const SrStage &s = m.st[i];
+            const Map P = input_map(pq[0].p, s.h, s.w, s.c, s.c), Q = input_map(pq[1].p, s.h, s.w, s.c, s.c), u = s.u(), a0 = s.a(0);
+            k.wgrad(g_dst, &dst, LRELU, u, n.tail2[i], 1, k.G->tail2[i]);
+            k.dgrad(g_dst, &dst, LRELU, n.tail2[i], k.P->tail2[i], 1, P, false);
+            k.wgrad(P, &u, LRELU, s.a(s.nb), n.tail0[i], 1, k.G->tail0[i]);
+            k.dgrad(P, &u, LRELU, n.tail0[i], k.P->tail0[i], 1, Q, false);
+            for (int b = s.nb - 1; b >= 0; --b) {   // a(b + 1) = body.2(relu(body.0(a(b)))) + a(b);  Q = d L / d a(b + 1) -> d L / d a(b)
+                const SursConv &c0 = *sr_body(n, i, b, 0), &c2 = *sr_body(n, i, b, 1);
+                const Map t = s.t(b);
+                k.wgrad(Q, nullptr, 1.0f, t, c2, 1, *sr_body(n, k.G, i, b, 1));
+                k.dgrad(Q, nullptr, 1.0f, c2, *sr_body(n, k.P, i, b, 1), 1, P, false);
+                k.wgrad(P, &t, RELU, s.a(b), c0, 1, *sr_body(n, k.G, i, b, 0));
+                k.dgrad(P, &t, RELU, c0, *sr_body(n, k.P, i, b, 0), 1, Q, true);
+            }
+            k.wgrad(Q, &a0, LRELU, src, n.down[i], 2, k.G->down[i]);
+            if (g_src.p) k.dgrad(Q, &a0, LRELU, n.down[i], k.P->down[i], 2, g_src, live);
+            if (!n.residual)
+                for (int b = 0; b < n.n_block[i]; ++b) {   // blocks the forward does not run
+                    k.zero(*sr_body(n, i, b, 0), *sr_body(n, k.G, i, b, 0));
+                    k.zero(*sr_body(n, i, b, 1), *sr_body(n, k.G, i, b, 1));
+                }
+        };
+        stage(2, m.new2.slice(0, 128), m.new1.slice(0, 256), g_new1.slice(0, 256), g_new2.slice(0, 128), true);
+        stage(1, m.new3.slice(0, 64), m.new2.slice(0, 128), g_new2.slice(0, 128), g_new3.slice(0, 64), top);
+        stage(0, m.fin.slice(0, 32), m.new3.slice(0, 64), g_new3.slice(0, 64), g_fin.slice(0, 32), top);
+        Map h = m.fin.slice(0, 32);
+        k.wgrad(g_fin.slice(0, 32), &h, LRELU, m.up, n.head, 1, k.G->head);
+    };
+    {   // the slabs: the largest any layer asks for - the walk itself without launches, every upstream gradient present
+        Run rd = r;
+        rd.dry = true;
+        SrBack d{rd, run.P, run.G, run.acc};
+        walk(d, NOWHERE, NOWHERE, NOWHERE);
+        run.wws_bytes = d.wws_need;
+        run.wws = r.a->take(run.wws_bytes);
     }
     if (r.dry || r.rc || !r.a->ok()) return;
-
-    const bool top = g_img || g_hr;   // does any gradient reach feature_hr?
-    if (g_img) {
-        Map gi; gi.p = const_cast<float *>(g_img); gi.h = H2; gi.w = W2; gi.c = gi.ld = 3;
-        k.wgrad(gi, nullptr, 1.0f, m.t_last, n.last2, 1, k.G->last2);
-        k.dgrad(gi, nullptr, 1.0f, n.last2, k.P->last2, 1, g_tlast, false);
-        k.wgrad(g_tlast, &m.t_last, LRELU, m.new_fin, n.last0, 1, k.G->last0);
-        k.dgrad(g_tlast, &m.t_last, LRELU, n.last0, k.P->last0, 1, g_newfin, false);
-    } else {
-        k.zero(n.last2, k.G->last2);
-        k.zero(n.last0, k.G->last0);
-    }
-    if (g_hr) {
-        Map gh; gh.p = const_cast<float *>(g_hr); gh.h = H2; gh.w = W2; gh.c = gh.ld = n.conv5.cout;
-        k.wgrad(gh, nullptr, 1.0f, m.new_fin, n.conv5, 1, k.G->conv5);
-        k.dgrad(gh, nullptr, 1.0f, n.conv5, k.P->conv5, 1, g_newfin, g_img != nullptr);
-    } else {
-        k.zero(n.conv5, k.G->conv5);
-    }
-    // a shuffle level: g of the shuffled slice `o` (stored output `y`) -> the convolution cw on src; the gradient of src replaces g_src
-    auto unshuffle = [&](const Map &g_o, const Map &y, const Map &src, const SursConv &cw, const SursSrParam &p, const SursSrParam &gp,
-                         const Map &g_src) {
-        Map t = dzt;
-        t.h = src.h; t.w = src.w; t.c = t.ld = cw.cout;
-        if (!r.rc) r.fail(surs_pixel_unshuffle2_grad(g_o.p, t.h, t.w, g_o.c, g_o.ld, y.p, y.ld, LRELU2, t.p, t.ld, r.st));
-        k.wgrad(t, nullptr, 1.0f, src, cw, 1, gp);
-        k.dgrad(t, nullptr, 1.0f, cw, p, 1, g_src, false);
-    };
-    if (top) {
-        k.wgrad(g_newfin, &m.new_fin, LRELU, m.fin, n.ups4, 1, k.G->ups4);
-        k.dgrad(g_newfin, &m.new_fin, LRELU, n.ups4, k.P->ups4, 1, g_fin, false);
-        unshuffle(g_fin.slice(32, 32), m.fin.slice(32, 32), m.new3, n.ups3, k.P->ups3, k.G->ups3, g_new3);
-        unshuffle(g_new3.slice(64, 64), m.new3.slice(64, 64), m.new2, n.ups2, k.P->ups2, k.G->ups2, g_new2);
-        if (g_lr) {   // feature_lr's own gradient joins the one that came down through ups2
-            Map gl; gl.p = const_cast<float *>(g_lr); gl.h = g_new2.h; gl.w = g_new2.w; gl.c = gl.ld = 256;
-            if (!r.rc) r.fail(surs_add3(g_new2.p, g_new2.ld, gl.p, gl.ld, nullptr, 0, g_new2.h * g_new2.w, 256, g_new2.p, g_new2.ld, r.st));
-        }
-    } else {
-        k.zero(n.ups4, k.G->ups4);
-        k.zero(n.ups3, k.G->ups3);
-        k.zero(n.ups2, k.G->ups2);
-        k.copy(g_lr, g_new2);
-    }
-    unshuffle(g_new2.slice(128, 128), m.new2.slice(128, 128), m.new1, n.bott2, k.P->bott2, k.G->bott2, g_new1);
-    {
-        Map g_bo = g_new1.slice(256, 256), bo = m.new1.slice(256, 256), d3_f = m.new1.slice(0, 256);
-        k.wgrad(g_bo, &bo, LRELU, d3_f, n.bottleneck, 1, k.G->bottleneck);
-        k.dgrad(g_bo, &bo, LRELU, n.bottleneck, k.P->bottleneck, 1, g_new1.slice(0, 256), true);
-    }
-    // a stage in reverse: g_dst = d L / d dst (all consumers added), its input's gradient is added to (or, live == false, replaces) g_src
-    auto stage = [&](int i, const Map &src, const Map &dst, const Map &g_dst, const Map &g_src, bool live) {
-        const SrStage &s = m.st[i];
-        const int nb = (int)s.t.size();
-        Map P = pq[0], Q = pq[1];
-        P.h = Q.h = s.u.h; P.w = Q.w = s.u.w; P.c = P.ld = Q.c = Q.ld = s.u.c;
-        k.wgrad(g_dst, &dst, LRELU, s.u, n.tail2[i], 1, k.G->tail2[i]);
-        k.dgrad(g_dst, &dst, LRELU, n.tail2[i], k.P->tail2[i], 1, P, false);
-        k.wgrad(P, &s.u, LRELU, s.a[nb], n.tail0[i], 1, k.G->tail0[i]);
-        k.dgrad(P, &s.u, LRELU, n.tail0[i], k.P->tail0[i], 1, Q, false);
-        for (int b = nb - 1; b >= 0; --b) {   // a[b + 1] = body.2(relu(body.0(a[b]))) + a[b];  Q = d L / d a[b + 1] -> d L / d a[b]
-            const SursConv &c0 = *sr_body(n, i, b, 0), &c2 = *sr_body(n, i, b, 1);
-            k.wgrad(Q, nullptr, 1.0f, s.t[b], c2, 1, *sr_body(n, k.G, i, b, 1));
-            k.dgrad(Q, nullptr, 1.0f, c2, *sr_body(n, k.P, i, b, 1), 1, P, false);
-            k.wgrad(P, &s.t[b], RELU, s.a[b], c0, 1, *sr_body(n, k.G, i, b, 0));
-            k.dgrad(P, &s.t[b], RELU, c0, *sr_body(n, k.P, i, b, 0), 1, Q, true);
-        }
-        k.wgrad(Q, &s.a[0], LRELU, src, n.down[i], 2, k.G->down[i]);
-        if (g_src.p) k.dgrad(Q, &s.a[0], LRELU, n.down[i], k.P->down[i], 2, g_src, live);
-        if (!n.residual)
-            for (int b = 0; b < n.n_block[i]; ++b) {   // blocks the forward does not run
-                k.zero(*sr_body(n, i, b, 0), *sr_body(n, k.G, i, b, 0));
-                k.zero(*sr_body(n, i, b, 1), *sr_body(n, k.G, i, b, 1));
-            }
-    };
-    stage(2, m.new2.slice(0, 128), m.new1.slice(0, 256), g_new1.slice(0, 256), g_new2.slice(0, 128), true);
-    stage(1, m.new3.slice(0, 64), m.new2.slice(0, 128), g_new2.slice(0, 128), g_new3.slice(0, 64), top);
-    stage(0, m.fin.slice(0, 32), m.new3.slice(0, 64), g_new3.slice(0, 64), g_fin.slice(0, 32), top);
-    Map h = m.fin.slice(0, 32);
-    k.wgrad(g_fin.slice(0, 32), &h, LRELU, m.up, n.head, 1, k.G->head);
+    walk(run, g_img_sr, g_feature_lr, g_im_feat_hr);
 }
 
 size_t sr_tape_need(const SursEncoderNet *net, int eh, int ew) {
-    Arena d;
-    d.dry = true;
-    Run rd{net, &d, nullptr, net->parts, true};
-    SrTape m;
-    sr_tape_maps(rd, eh, ew, m);
-    return align_up(d.peak, 256);
+    Dry d(net);
+    SrPlan m;
+    sr_tape_maps(d.r, eh, ew, m);
+    return align_up(d.a.peak, 256);
 }
 
 size_t sr_backward_need(const SursEncoderNet *net, int eh, int ew) {
-    Arena t, d;
-    t.dry = d.dry = true;
-    Run rt{net, &t, nullptr, net->parts, true};
-    SrTape m;
-    sr_tape_maps(rt, eh, ew, m);
-    Run rd{net, &d, nullptr, net->parts, true};
-    SrBack k{rd, nullptr, nullptr, 0};
+    Dry t(net), d(net);
+    SrPlan m;
+    sr_tape_maps(t.r, eh, ew, m);
+    static const SursSrParam no_body[2 * 3 * 64] = {};   // (a run without launches reads no parameter; it forms their addresses)
+    SursSrParams none = {};
+    none.body = no_body;
+    SrBack k{d.r, &none, &none, 0};
     sr_backward(k, m, nullptr, nullptr, nullptr);
-    return align_up(d.peak, 256) + 256;
+    return align_up(d.a.peak, 256) + 256;
 }
 
 bool sr_params_filled(const SursEncoderNet *n, const SursSrParams *p) {
@@ -939,13 +948,13 @@ extern "C" int surs_encoder_super_res_train(const SursEncoderNet *net, const flo
     const int eh = sr_scale(net) * h, ew = sr_scale(net) * w;
     const size_t need = sr_tape_need(net, eh, ew);
     SURS_REQUIRE(need <= tape_bytes, "super_res_train: tape too small: %zu bytes needed", need);
-    Arena a;
-    a.base = (char *)tape;
-    a.cap = tape_bytes;
+    Arena a = tape_arena(tape, tape_bytes);
     Run r{net, &a, as_stream(stream), net->parts, false};
-    SrTape m;
+    SrPlan m;
     sr_tape_maps(r, eh, ew, m);
-    sr_train_forward(r, input_map(x, h, w, 3, x_ld), m, img_sr, im_feat_hr);
+    super_res(r, input_map(x, h, w, 3, x_ld), m, img_sr);
+    Map f = input_map(im_feat_hr, eh, ew, net->conv5.cout, net->conv5.cout);
+    conv(r, m.new_fin, net->conv5, f, 1, 0, 0.0f, nullptr);
     if (r.rc) return r.rc;
     SURS_HIP_CHECK(hipMemcpyAsync(feature_lr, m.new2.p, sizeof(float) * m.new2.h * m.new2.w * 256, hipMemcpyDeviceToDevice, r.st));
     SURS_HIP_CHECK(hipMemcpyAsync(feature_hr, m.new_fin.p, sizeof(float) * m.new_fin.h * m.new_fin.w * 64, hipMemcpyDeviceToDevice, r.st));
@@ -963,18 +972,13 @@ extern "C" int surs_encoder_super_res_backward(const SursEncoderNet *net, const 
     SURS_REQUIRE(sr_params_filled(net, params) && sr_params_filled(net, grads), "super_res_backward: a null weight or bias pointer in params / grads");
     SURS_REQUIRE(((size_t)tape & 255) == 0, "super_res_backward: the tape must be 256-byte aligned");
     const int eh = sr_scale(net) * h, ew = sr_scale(net) * w;
-    Arena t;
-    t.base = (char *)const_cast<void *>(tape);
-    t.cap = sr_tape_need(net, eh, ew);
+    Arena t = tape_arena(tape, sr_tape_need(net, eh, ew));
     Run rt{net, &t, nullptr, net->parts, false};
-    SrTape m;
+    SrPlan m;
     sr_tape_maps(rt, eh, ew, m);
     Arena a;
-    a.base = (char *)align_up((size_t)workspace, 256);
-    const size_t lead = (size_t)(a.base - (char *)workspace);
     const size_t need = sr_backward_need(net, eh, ew);
-    SURS_REQUIRE(need - 256 + lead <= workspace_bytes, "super_res_backward: workspace too small: %zu bytes needed", need);
-    a.cap = workspace_bytes - lead;
+    SURS_REQUIRE(workspace_arena(workspace, workspace_bytes, need - 256, a), "super_res_backward: workspace too small: %zu bytes needed", need);
     Run r{net, &a, as_stream(stream), net->parts, false};
     SrBack k{r, params, grads, accumulate ? 1 : 0};
     sr_backward(k, m, g_img_sr, g_feature_lr, g_im_feat_hr);
@@ -982,93 +986,11 @@ extern "C" int surs_encoder_super_res_backward(const SursEncoderNet *net, const 
 }
 
 // ---------------------------------------------------------------- hourglass gradients (include/surs.h)
-// surs_encoder_convblock_train / surs_encoder_hourglass_train run conv_block() / hourglass() above in the separate-sum form - the
-// launches of the host mirror (encoder.py) for an input without statistics - with EVERY map in the tape: the block's input, the
-// raw cat(o1, o2, o3) (the closing sum goes to a map of its own instead of overwriting the slices) and, per norm site, the four
-// coefficient vectors surs_groupnorm_fold forms from what the forward's kernels folded themselves.  The backward lays the tape out
-// by running the same sequencing without launches: the addresses are a function of the net and the size alone.
+// surs_encoder_convblock_train / surs_encoder_hourglass_train run conv_block() / hourglass() above with a tape: the separate-sum
+// form - the launches of the host mirror (encoder.py) for an input without statistics - with EVERY map kept (BlockTape).  THE
+// LAYOUT OF THE TAPE IS THE ORDER OF THE ARENA TAKES OF THAT ONE SEQUENCING: the backward finds the addresses by running it without
+// launches (hg_layout()), a function of the net and the size alone.
 namespace {
-
-struct NormTape { float *mean, *rstd, *scale, *shift; };
-struct BlockTape {
-    Map x, cat, out;
-    NormTape nt[3];
-};
-struct HgTape {
-    std::vector<BlockTape> blocks;   // in the order of the net's block array
-};
-
-NormTape norm_vectors(Run &r, int c) {
-    NormTape t;
-    t.mean = (float *)r.a->take(sizeof(float) * 32);
-    t.rstd = (float *)r.a->take(sizeof(float) * 32);
-    t.scale = (float *)r.a->take(sizeof(float) * c);
-    t.shift = (float *)r.a->take(sizeof(float) * c);
-    return t;
-}
-
-// conv_block() in the separate-sum form, on the tape
-Map conv_block_train(Run &r, const SursConvBlock &b, const Map &x, bool want_stats, BlockTape &t) {
-    const int c = x.c;
-    t.x = x;
-    t.cat = r.map(x.h, x.w, c);
-    t.out = r.map(x.h, x.w, c);
-    Map o1 = t.cat.slice(0, c / 2), o2 = t.cat.slice(c / 2, c / 4), o3 = t.cat.slice(3 * c / 4, c / 4);
-    auto eligible = [&](const Map &m, const SursConv &cw) {
-        return (cw.ksize == 1 || cw.ksize == 3) && cw.w_split && m.c % 32 == 0 && m.ld % 4 == 0 && aligned16(m.p);
-    };
-    const bool fused = c % 128 == 0 && eligible(x, b.conv[0]) && eligible(o1, b.conv[1]) && eligible(o2, b.conv[2]);
-    Map ins[3] = {x, o1, o2};
-    Map outs[3] = {o1, o2, o3};
-    for (int k = 0; k < 3; ++k) t.nt[k] = norm_vectors(r, ins[k].c);
-    if (fused && x.st.sums && x.st.g1 == 0) {
-        for (int k = 0; k < 3; ++k) {
-            conv_gn(r, ins[k], b.conv[k], outs[k], &b.bn[k], k < 2);
-            if (k < 2) ins[k + 1].st = outs[k].st;   // (the slice the next convolution reads, with the statistics this one left)
-            if (!r.dry && !r.rc)
-                r.fail(surs_groupnorm_fold(&ins[k].st, nullptr, x.h * x.w, ins[k].c, ins[k].ld, 1e-5f, b.bn[k].gamma, b.bn[k].beta, t.nt[k].mean,
-                                           t.nt[k].rstd, t.nt[k].scale, t.nt[k].shift, nullptr, r.st));
-        }
-        add3(r, t.cat, x, t.out, want_stats);
-        return t.out;
-    }
-    void *scratch = r.a->take(surs_groupnorm_scratch_bytes());
-    for (int k = 0; k < 3; ++k) {
-        if (!r.dry && !r.rc)
-            r.fail(surs_groupnorm_fold(nullptr, ins[k].p, x.h * x.w, ins[k].c, ins[k].ld, 1e-5f, b.bn[k].gamma, b.bn[k].beta, t.nt[k].mean,
-                                       t.nt[k].rstd, t.nt[k].scale, t.nt[k].shift, scratch, r.st));
-        conv(r, ins[k], b.conv[k], outs[k], 1, 0, 0.0f, nullptr, t.nt[k].scale, t.nt[k].shift);
-    }
-    add3(r, t.cat, x, t.out, want_stats && fused);
-    return t.out;
-}
-
-// hourglass() on one stream, on the tape; blocks: the stack's 3 depth + 1 blocks in module order
-Map hourglass_train(Run &r, const SursConvBlock *blocks, int depth, const Map &x, HgTape &m) {
-    m.blocks.assign(3 * depth + 1, BlockTape());
-    struct Fwd {
-        Run &r; const SursConvBlock *blocks; HgTape &m; int next;
-        Map run(int level, const Map &inp) {
-            const int i1 = next++, i2 = next++;
-            Map up1 = conv_block_train(r, blocks[i1], inp, false, m.blocks[i1]);
-            Map pooled = avgpool2(r, inp, true);
-            Map low1 = conv_block_train(r, blocks[i2], pooled, true, m.blocks[i2]);
-            Map low2;
-            if (level > 1) {
-                low2 = run(level - 1, low1);
-            } else {
-                const int ip = next++;
-                low2 = conv_block_train(r, blocks[ip], low1, true, m.blocks[ip]);
-            }
-            const int i3 = next++;
-            Map low3 = conv_block_train(r, blocks[i3], low2, false, m.blocks[i3]);
-            Map out = r.map(2 * low3.h, 2 * low3.w, low3.c);
-            bicubic_up2(r, low3, true, &up1, out, true);
-            return out;
-        }
-    } f{r, blocks, m, 0};
-    return f.run(depth, x);
-}
 
 struct HgBack {
     Run &r;
@@ -1095,16 +1017,14 @@ struct HgBack {
     void block(const BlockTape &t, const SursHgBlockParams &P, const SursHgBlockParams &D, const Map &g, const Map &dx) {
         if (r.dry || r.rc) return;
         const int h = t.x.h, w = t.x.w, hw = h * w;
-        Map Gm = G, Am = A, Tm = T;
-        Gm.h = Am.h = Tm.h = h; Gm.w = Am.w = Tm.w = w;
+        const Map Gm = input_map(G.p, h, w, 256, 256);
         copy(g, dx);    // the identity path
         copy(g, Gm);
         const Map ins[3] = {t.x, t.cat.slice(0, 128), t.cat.slice(128, 64)};
         const int c0[3] = {0, 128, 192}, cout[3] = {128, 64, 64};
         for (int k = 2; k >= 0 && !r.rc; --k) {
             const int cin = ins[k].c;
-            Map a = Am, d = Tm;
-            a.c = a.ld = d.c = d.ld = cin;
+            const Map a = input_map(A.p, h, w, cin, cin), d = input_map(T.p, h, w, cin, cin);
             const Map gk = Gm.slice(c0[k], cout[k]);
             r.fail(surs_scale_shift_act(ins[k].p, hw, cin, ins[k].ld, t.nt[k].scale, t.nt[k].shift, 1, a.p, a.ld, r.st));
             if (!r.rc)
@@ -1121,34 +1041,27 @@ struct HgBack {
     }
 };
 
-void hourglass_backward(HgBack &k, const HgTape &m, int depth, const SursHgBlockParams *P, const SursHgBlockParams *D, const Map &g,
+// hourglass() in reverse; tape: the stack's blocks as the forward recorded them
+void hourglass_backward(HgBack &k, const BlockTape *tape, int depth, const SursHgBlockParams *P, const SursHgBlockParams *D, const Map &g,
                         const Map &dx) {
     struct Bwd {
-        HgBack &k; const HgTape &m; const SursHgBlockParams *P, *D; int next;
+        HgBack &k; const BlockTape *tape; const SursHgBlockParams *P, *D;
+        HgLevel lv[HG_MAX_DEPTH + 1];
+        void block(int i, const Map &g, const Map &dinp) { k.block(tape[i], P[i], D[i], g, dinp); }
         void run(int level, const Map &g, const Map &dinp) {
             Run &r = k.r;
-            const int i1 = next++, i2 = next++;
+            const HgLevel &l = lv[level];
             Map p = r.map(g.h / 2, g.w / 2, 256), q = r.map(g.h / 2, g.w / 2, 256);
-            // the forward's block indices below this level, taken in the forward's order; the launches run in reverse
-            const int below = next;
-            int ip = -1;
-            if (level > 1) next += 3 * (level - 1) + 1; else ip = next++;
-            const int i3 = next++;
-            k.block(m.blocks[i1], P[i1], D[i1], g, dinp);
+            block(l.b1, g, dinp);
             if (!r.dry && !r.rc) r.fail(surs_bicubic_up2_grad(g.p, p.h, p.w, 256, g.ld, p.p, p.ld, 0, r.st));
-            k.block(m.blocks[i3], P[i3], D[i3], p, q);
-            if (level > 1) {
-                const int keep = next;
-                next = below;
-                run(level - 1, q, p);
-                next = keep;
-            } else {
-                k.block(m.blocks[ip], P[ip], D[ip], q, p);
-            }
-            k.block(m.blocks[i2], P[i2], D[i2], p, q);
+            block(l.b3, p, q);
+            if (level > 1) run(level - 1, q, p);
+            else block(l.b2_plus, q, p);
+            block(l.b2, p, q);
             if (!r.dry && !r.rc) r.fail(surs_avgpool2_grad(q.p, q.h, q.w, 256, q.ld, dinp.p, dinp.ld, 1, r.st));
         }
-    } b{k, m, P, D, 0};
+    } b{k, tape, P, D};
+    hg_levels(depth, b.lv);
     b.run(depth, g, dx);
 }
 
@@ -1178,10 +1091,8 @@ bool hg_params_filled(const SursHgBlockParams *p, int count) {
 
 // the tape of a block (depth 0) or of a stack's hourglass: the input's copy, then the sequencing's maps
 struct HgLayout {
-    Map x;
-    BlockTape bt;
-    HgTape ht;
-    Map out;
+    Map x, out;
+    BlockTape blocks[HG_MAX_BLOCKS];   // in the order of the net's block array
 };
 
 // x (pitch ld): the input, copied into the tape in front of the launches; a run without launches lays the tape out
@@ -1190,36 +1101,31 @@ void hg_layout(Run &r, const SursConvBlock *blocks, int depth, int h, int w, HgL
     if (!r.dry && hipMemcpy2DAsync(L.x.p, sizeof(float) * 256, x, sizeof(float) * ld, sizeof(float) * 256, (size_t)h * w,
                                    hipMemcpyDeviceToDevice, r.st) != hipSuccess)
         r.fail(fail(SURS_E_HIP, "hourglass gradients: hipMemcpy2DAsync failed"));
-    if (depth == 0) L.out = conv_block_train(r, blocks[0], L.x, false, L.bt);
-    else L.out = hourglass_train(r, blocks, depth, L.x, L.ht);
+    if (depth == 0) L.out = conv_block(r, blocks[0], L.x, false, &L.blocks[0]);
+    else L.out = hourglass(r, blocks, depth, L.x, nullptr, L.blocks);
 }
 
 size_t hg_tape_need(const SursEncoderNet *net, const SursConvBlock *blocks, int depth, int h, int w) {
-    Arena d;
-    d.dry = true;
-    Run rd{net, &d, nullptr, net->parts, true};
+    Dry d(net);
     HgLayout L;
-    hg_layout(rd, blocks, depth, h, w, L);
-    return align_up(d.peak, 256);
+    hg_layout(d.r, blocks, depth, h, w, L);
+    return align_up(d.a.peak, 256);
 }
 
 void hg_back_all(HgBack &k, const HgLayout &L, int depth, const SursHgBlockParams *P, const SursHgBlockParams *D, const Map &g, const Map &dx) {
     k.alloc(dx.h, dx.w);
-    if (depth == 0) k.block(L.bt, P[0], D[0], g, dx);
-    else hourglass_backward(k, L.ht, depth, P, D, g, dx);
+    if (depth == 0) k.block(L.blocks[0], P[0], D[0], g, dx);
+    else hourglass_backward(k, L.blocks, depth, P, D, g, dx);
 }
 
 size_t hg_backward_need(const SursEncoderNet *net, int depth, int h, int w) {
-    Arena d;
-    d.dry = true;
-    Run rd{net, &d, nullptr, net->parts, true};
-    HgBack k{rd, 0};
+    Dry d(net);
+    HgBack k{d.r, 0};
     HgLayout L;
-    if (depth > 0) L.ht.blocks.assign(3 * depth + 1, BlockTape());
-    Map g = input_map(nullptr, h, w, 256, 256);
-    const std::vector<SursHgBlockParams> none(3 * depth + 1);   // (a dry run reads no parameter)
-    hg_back_all(k, L, depth, none.data(), none.data(), g, g);
-    return align_up(d.peak, 256) + 256;
+    const SursHgBlockParams none[HG_MAX_BLOCKS] = {};   // (a run without launches reads no tape and no parameter)
+    const Map g = input_map(nullptr, h, w, 256, 256);
+    hg_back_all(k, L, depth, none, none, g, g);
+    return align_up(d.a.peak, 256) + 256;
 }
 
 int hg_train(const SursEncoderNet *net, const SursConvBlock *blocks, int depth, const float *x, int h, int w, int ld, float *out, void *tape,
@@ -1231,9 +1137,7 @@ int hg_train(const SursEncoderNet *net, const SursConvBlock *blocks, int depth, 
     SURS_REQUIRE(((size_t)tape & 255) == 0, "%s: the tape must be 256-byte aligned", what);
     const size_t need = hg_tape_need(net, blocks, depth, h, w);
     SURS_REQUIRE(need <= tape_bytes, "%s: tape too small: %zu bytes needed", what, need);
-    Arena a;
-    a.base = (char *)tape;
-    a.cap = tape_bytes;
+    Arena a = tape_arena(tape, tape_bytes);
     Run r{net, &a, as_stream(stream), net->parts, false};
     HgLayout L;
     hg_layout(r, blocks, depth, h, w, L, x, ld);
@@ -1251,18 +1155,13 @@ int hg_backward(const SursEncoderNet *net, const SursConvBlock *blocks, int dept
     SURS_REQUIRE(params && grads && tape && g && dx && workspace, "%s: null argument", what);
     SURS_REQUIRE(hg_params_filled(params, count) && hg_params_filled(grads, count), "%s: a null pointer in params / grads", what);
     SURS_REQUIRE(((size_t)tape & 255) == 0 && aligned16(g) && aligned16(dx), "%s: the tape must be 256-byte aligned, the maps 16-byte", what);
-    Arena t;
-    t.base = (char *)const_cast<void *>(tape);
-    t.cap = hg_tape_need(net, blocks, depth, h, w);
+    Arena t = tape_arena(tape, hg_tape_need(net, blocks, depth, h, w));
     Run rt{net, &t, nullptr, net->parts, true};   // (no launches: the addresses)
     HgLayout L;
     hg_layout(rt, blocks, depth, h, w, L);
     Arena a;
-    a.base = (char *)align_up((size_t)workspace, 256);
-    const size_t lead = (size_t)(a.base - (char *)workspace);
     const size_t need = hg_backward_need(net, depth, h, w);
-    SURS_REQUIRE(need - 256 + lead <= workspace_bytes, "%s: workspace too small: %zu bytes needed", what, need);
-    a.cap = workspace_bytes - lead;
+    SURS_REQUIRE(workspace_arena(workspace, workspace_bytes, need - 256, a), "%s: workspace too small: %zu bytes needed", what, need);
     Run r{net, &a, as_stream(stream), net->parts, false};
     HgBack k{r, accumulate ? 1 : 0};
     hg_back_all(k, L, depth, params, grads, input_map(g, h, w, 256, 256), input_map(dx, h, w, 256, 256));
