@@ -92,8 +92,8 @@ def test_conv_with_the_sum_in_its_epilogue_against_conv_then_add(monkeypatch):
     """surs_conv2d_nhwc_gn_sum on its own: value, value + residual, both sets of statistics - against surs_conv2d_nhwc_gn followed by
     surs_add3_gn (the same tiles: equal bits for the maps; the statistics are sums in another order: 1e-12 relative)."""
     from surs_amd import native, prng
-    from surs_amd import _lib
     import gpu_common as g
+    from conv_tiles import ConvSum
     h, w, cin, cout, ctot = 40, 96, 64, 32, 128    # whole tiles of 4 rows x 32 columns; channels [64, 96) of a 128-channel sum
     x = g.upload_nhwc(prng.uniform("sx", 1, (cin, h, w), -1, 1))
     xin = g.upload_nhwc(prng.uniform("sr", 2, (ctot, h, w), -1, 1))
@@ -105,18 +105,11 @@ def test_conv_with_the_sum_in_its_epilogue_against_conv_then_add(monkeypatch):
     ref_sum = native.add3(ref_raw, xin.slice(64, cout), want_stats=False)
     cap = ((w + 31) // 32) * ((h + 3) // 4)
     raw, out = native.Img(h, w, cout), native.Img(h, w, ctot)
-    s_in = _lib.GnStats(x0.stats.buf.data_ptr(), x0.stats.slots, 0, 0, (C.c_int * 3)(x0.stats.slots, 0, 0))
-    sb1 = torch.zeros(32 * cap * 2, dtype=torch.float64, device="cuda:0")
-    sb2 = torch.zeros(32 * cap * 2, dtype=torch.float64, device="cuda:0")
-    s_out = _lib.GnStats(sb1.data_ptr(), cap, 0, 0, (C.c_int * 3)(0, 0, 0))
-    slots = C.c_int(0)
-    native.check(native.lib().surs_conv2d_nhwc_gn_sum(2, x0.ptr(), h, w, cin, x0.ld, native._ptr(cw.w3), None, C.byref(s_in), None, None,
-                                                      native._ptr(gam), native._ptr(bet), 1e-5, raw.ptr(), cout, raw.ld, C.byref(s_out),
-                                                      xin.slice(64, cout).ptr(), xin.ld, out.slice(64, cout).ptr(), out.ld, native._ptr(sb2), cap,
-                                                      64 // 4, 4, C.byref(slots), native._stream()))
+    call = ConvSum(x0, cw, gam, bet, cap)
+    sb1, sb2, s_out = call.sb1, call.sb2, call.s_out
+    n = call(raw, xin.slice(64, cout), out.slice(64, cout), 64 // 4, 4)
     assert torch.equal(_hwc(raw), _hwc(ref_raw))
     assert torch.equal(_hwc(out.slice(64, cout)), _hwc(ref_sum))
-    n = slots.value
     assert n == s_out.slots[0] == ref_raw.stats.slots and s_out.pitch == n
     got1 = sb1[:32 * n * 2].view(32, n, 2).sum(1).cpu().numpy()
     ref1 = ref_raw.stats.buf[:32 * n * 2].view(32, n, 2).sum(1).cpu().numpy()
@@ -130,10 +123,7 @@ def test_conv_with_the_sum_in_its_epilogue_against_conv_then_add(monkeypatch):
     # ragged tiles are refused (the second output is made by the whole-tile epilogue): callers take conv + add there
     from surs_amd._lib import SursError
     with pytest.raises(SursError, match="whole tiles"):
-        native.check(native.lib().surs_conv2d_nhwc_gn_sum(2, x0.ptr(), h - 1, w, cin, x0.ld, native._ptr(cw.w3), None, C.byref(s_in), None, None,
-                                                          native._ptr(gam), native._ptr(bet), 1e-5, raw.ptr(), cout, raw.ld, C.byref(s_out),
-                                                          xin.slice(64, cout).ptr(), xin.ld, out.slice(64, cout).ptr(), out.ld, native._ptr(sb2),
-                                                          cap, 64 // 4, 4, C.byref(slots), native._stream()))
+        call(raw, xin.slice(64, cout), out.slice(64, cout), 64 // 4, 4, h=h - 1)
 
 
 def test_facade_takes_the_native_encoder_and_falls_back_where_it_does_not_apply(monkeypatch):

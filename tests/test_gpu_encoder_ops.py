@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import common
+from conv_tiles import force_tile, tile_of  # noqa: F401  (force_tile: the fixture that forces the 3x3 kernel's tile)
 from surs_amd import prng
 
 pytestmark = pytest.mark.gpu
@@ -158,21 +159,36 @@ def _fold(st):
     return st.buf[:64 * st.slots].view(32, st.slots, 2).sum(dim=1).cpu().numpy()
 
 
+_block_refs = {}
+
+
+def _block_case(orc, c, h, w):
+    """The ConvBlock test's seeded operands and the oracle's ConvBlock on them (computed once per size)."""
+    if (c, h, w) not in _block_refs:
+        x = prng.uniform("bx", 1, (c, h, w), -2, 3)
+        wts = [prng.uniform("bw", i, s, -0.08, 0.08) for i, s in enumerate(((c // 2, c, 3, 3), (c // 4, c // 2, 3, 3), (c // 4, c // 4, 3, 3)))]
+        gns = [(prng.uniform("bg", i, (n,), 0.5, 1.5), prng.uniform("bb", i, (n,), -0.3, 0.3)) for i, n in enumerate((c, c // 2, c // 4))]
+        o1 = orc.conv2d(orc.relu(orc.group_norm(x, *gns[0])), wts[0])
+        o2 = orc.conv2d(orc.relu(orc.group_norm(o1, *gns[1])), wts[1])
+        o3 = orc.conv2d(orc.relu(orc.group_norm(o2, *gns[2])), wts[2])
+        _block_refs[c, h, w] = x, wts, gns, np.concatenate([o1, o2, o3]) + x
+    return _block_refs[c, h, w]
+
+
 @pytest.mark.parametrize("reduced", [False, True])
-def test_conv_block_with_groupnorm_statistics_handed_between_kernels(env, reduced):
+@pytest.mark.parametrize("tile,h", [("4x32", 44), ("4x32", 42), ("8x32", 44), ("8x32", 42), ("8x64", 44), ("8x64", 42)])
+def test_conv_block_with_groupnorm_statistics_handed_between_kernels(env, force_tile, tile, h, reduced):
     """ConvBlock (lib/model/HGFilters.py:57-74) in four launches - every kernel leaves the GroupNorm statistics of the map it
     writes, the next 3x3 convolution folds them itself (surs_conv2d_nhwc_gn, surs_add3_gn) - against the oracle's ConvBlock and
     against the ten-launch form (surs_groupnorm_coeffs in front of each convolution); the statistics themselves against float64
-    sums of the stored values; two runs give the same bits (no atomics)."""
+    sums of the stored values; two runs give the same bits (no atomics).  On each tile of the 3x3 kernel (left to itself a map of
+    this size - 72 workgroups at most - takes 4 rows x 32 channels, on which 44 rows are whole tiles)."""
     nat, orc, dev = env["native"], env["oracle"], env["dev"]
-    c, h, w = 256, 44, 72                     # ragged tiles in both directions (44 = 5.5 x 8 rows, 72 = 2.25 x 32 columns)
-    x = prng.uniform("bx", 1, (c, h, w), -2, 3)
-    wts = [prng.uniform("bw", i, s, -0.08, 0.08) for i, s in enumerate(((c // 2, c, 3, 3), (c // 4, c // 2, 3, 3), (c // 4, c // 4, 3, 3)))]
-    gns = [(prng.uniform("bg", i, (n,), 0.5, 1.5), prng.uniform("bb", i, (n,), -0.3, 0.3)) for i, n in enumerate((c, c // 2, c // 4))]
-    o1 = orc.conv2d(orc.relu(orc.group_norm(x, *gns[0])), wts[0])
-    o2 = orc.conv2d(orc.relu(orc.group_norm(o1, *gns[1])), wts[1])
-    o3 = orc.conv2d(orc.relu(orc.group_norm(o2, *gns[2])), wts[2])
-    ref = np.concatenate([o1, o2, o3]) + x
+    # ragged tiles in both directions: 72 = 2.25 x 32 columns; 44 = 5.5 x 8 rows (11 whole tiles of 4 rows), 42 = 10.5 x 4 = 5.25 x 8 rows
+    c, w = 256, 72
+    x, wts, gns, ref = _block_case(orc, c, h, w)
+    force_tile(tile)
+    rows = tile_of(tile, 1 if reduced else 2)[0]
     cws = [nat.ConvWeights(wt, None, dev, reduced=reduced) for wt in wts]
     G = [(torch.from_numpy(g).to(dev), torch.from_numpy(b).to(dev)) for g, b in gns]
 
@@ -187,6 +203,7 @@ def test_conv_block_with_groupnorm_statistics_handed_between_kernels(env, reduce
         return X, a, b_, pre, nat.add3(out, X, out=out, want_stats=True)
 
     X, a, b_, pre, out = fused()
+    assert a.stats.slots == b_.stats.slots == ((w + 31) // 32) * ((h + rows - 1) // rows)
     y = _chw(out)
     tol = 2e-3 if reduced else 2e-5          # (one f16 product per MAC: 11 significant bits)
     assert common.rel_err(y, ref) < tol
