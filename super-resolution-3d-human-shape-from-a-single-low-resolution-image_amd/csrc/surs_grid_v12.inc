@@ -23,11 +23,18 @@
 //     the listed channels' constants which the classification leaves compacted in LDS (six ds_read_b128 per fragment instead of
 //     v10's 24 dependent ds_read_b32), the first V12_KR = 4 k-steps' kept in registers, the rest (up to V12_KCAP) in a wave-private
 //     LDS area; no barrier between generation and use;
-//   * the affine part's A fragment of the chunk's row tile, built from the column's R vectors one chunk ahead.
+//   * the affine part's A fragment of the chunk's row tile: ONE 16-byte load per lane, one chunk ahead, from the workgroup's fragment
+//     image in global memory.  The fragment depends on column, classifier and chunk only, so the per-column part builds the column's
+//     32 fragments ONCE from the R vectors and b1 (v12_affine_build: 8 fragment lanes per thread, v10's expressions and slot order)
+//     instead of every wave in every z tile (16 times per column and classifier: 794 vector instructions and 80 loads per tile).  The
+//     image (32 KiB per workgroup) lies in the g-scaled split image of the workspace, dead since the R GEMMs, behind the overflow list;
+//     it is written and read by waves of ONE workgroup on one CU, published by the barrier that ends the per-column part.
 // LDS per workgroup: ring 16 KiB + slices 2 x 8 KiB + residual fragments 4 x 4 KiB + compacted constants 1.5 KiB, overlaid by y2
 // (64 KiB) once layer 2 is done; + 6.1 KiB of small tables = 71 808 B: two workgroups per CU, whose phases drift apart - one's
 // vector / LDS phases run under the other's MFMAs.  256 registers per wave, none spilled: every per-lane value that is needed at
-// the END of an item (or in the per-column part) is made there from fresh_lane() instead of living through the item (NOTES R6.5).  The layer-0 constants (a0, w0z, w0p) are no longer copied to LDS: the classification reads them from
+// the END of an item (or in the per-column part) is made there from fresh_lane() instead of living through the item (NOTES R6.5).
+// As shipped (hipcc -O3 -ffp-contract=off, gfx950): bf16 66 688 B of code, 251 registers, no scratch; fp16 66 424 B, 249, none -
+// 4 674 vector instructions per tile without the 928 MFMAs (NOTES "affine fragments once per column").  The layer-0 constants (a0, w0z, w0p) are no longer copied to LDS: the classification reads them from
 // L2 (they are only needed there and, compacted, for the listed channels).
 //
 // Same list order (v7's), same k order in every layer, same four layer-4 partial sums: v12 reproduces v10's bits
@@ -39,10 +46,12 @@ constexpr int V12_THREADS = 256;
 #ifndef SURS_V12_KR
 #define SURS_V12_KR 4   // (per 128-plane slab, round 5 - with 16 - 38 spilled registers -: 0 -> 27.3 ms, 3 -> 27.6, 6 -> 30.4; round 6, once nothing
                         //  was spilled any more: 0 -> 27.15, 2 -> 26.85; and with the item's lane index made per item: 2 -> 26.32, 4 -> 26.13,
-                        //  5 / 6 the same as 4 (6 spills two registers): the LDS pipe is as busy as the matrix pipe)
+                        //  5 / 6 the same as 4 (6 spills two registers): the LDS pipe is as busy as the matrix pipe;
+                        //  with the affine fragments read from the per-column image: 4 -> 25.40, 25.29, 5 -> 25.24, 25.30, 6 -> 25.25, 25.22: within the spread)
 #endif
 #ifndef SURS_V12_KCAP
-#define SURS_V12_KCAP 8   // (round 6, 128-plane slab, same box, same hash: 9 -> 28.80 ms, 8 -> 28.55, 7 -> 28.7; 16 spilled registers against 23)
+#define SURS_V12_KCAP 8   // (round 6, 128-plane slab, same box, same hash: 9 -> 28.80 ms, 8 -> 28.55, 7 -> 28.7; 16 spilled registers against 23;
+                          //  with the per-column fragment image: 9 -> 25.50, 25.36, 8 -> 25.40, 25.29)
 #endif
 constexpr int V12_KR = SURS_V12_KR, V12_KCAP = SURS_V12_KCAP;
 static_assert(V12_KR <= V12_KCAP, "register-resident k-steps are a prefix of the staged ones");
@@ -86,6 +95,60 @@ __device__ unsigned long long g_v12_acc[2][16];
 #define V12_STAMP(i) do { } while (0)
 #endif
 
+// ---- the affine part's A fragments of a column: the workgroup's image in global memory [classifier 2][chunk 16][lane 64][16 B]
+constexpr int V12_AIMG_MLP = 16 * 64 * 16;         // one classifier's 16 chunks
+constexpr int V12_AIMG_BYTES = 2 * V12_AIMG_MLP;   // 32 KiB per workgroup
+
+// The A fragment of one 32-row chunk for fragment lane (row = lane & 31, half hh = lane >> 5), v10's slot order, from the column's
+// vectors R and b1: raw = {RA[row], RB[row], RC[row] (hr), b1[row]}.
+template <int DT, int M>
+__device__ __forceinline__ typename HalfT<DT>::vec8 v12_affine_frag(const float (&raw)[4], unsigned hh) {
+    typedef typename HalfT<DT>::vec8 vec8;
+    typedef typename HalfT<DT>::elem elem;
+    const elem zero = (elem)0.0f;
+    elem pa[3], pb[3], pc[3] = {zero, zero, zero};
+    split3_elem<DT>(raw[0] + raw[3], pa);
+    split3_elem<DT>(raw[1], pb);
+    if (M) split3_elem<DT>(raw[2], pc);
+    const vec8 flo = {pa[0], pa[1], pa[2], pb[0], pb[0], pb[1], pb[0], pb[1]};
+    const vec8 fhi = {pb[2], pc[0], pc[0], pc[1], pc[0], pc[1], pc[2], zero};
+    const vec8 r = hh ? fhi : flo;
+    return r;
+}
+
+// The column's 32 fragments, built by the workgroup's 256 threads: wave w the chunks w, w + 4, w + 8, w + 12 of both classifiers,
+// lane = fragment lane.  Called between the two barriers of the per-column part: every wave's loads of the previous column's image
+// have returned (the last one is consumed in stage 15 of the column's last item), and the barrier that ends the per-column part
+// publishes the stores to the workgroup's other waves (one CU, one L1: workgroup scope).  All loads first: the image may alias R for
+// all the compiler knows, and a load behind a store would wait for one more trip to L2 per fragment.
+template <int DT>
+__device__ __forceinline__ void v12_affine_build(const float *rv_lr /* [2][512] */, const float *rv_hr /* [3][512] */, const float *zvec,
+                                                 char *img, int wave, unsigned fl) {
+    typedef typename HalfT<DT>::vec8 vec8;
+    const unsigned o = 128u * (unsigned)wave + (fl & 31u) * 4u;   // + 512 i: row 32 (w + 4 i) + (lane & 31)
+    const char *rl = reinterpret_cast<const char *>(rv_lr) + o, *rh = reinterpret_cast<const char *>(rv_hr) + o;
+    const char *bl = reinterpret_cast<const char *>(zvec + ZV_B1_LR) + o, *bh = reinterpret_cast<const char *>(zvec + ZV_B1_HR) + o;
+    auto f = [](const char *p, int imm) { return *reinterpret_cast<const float *>(p + imm); };
+    float raw[2][4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        raw[0][i][0] = f(rl, 512 * i);
+        raw[0][i][1] = f(rl, 4 * D2 + 512 * i);
+        raw[0][i][2] = 0.0f;
+        raw[0][i][3] = f(bl, 512 * i);
+        raw[1][i][0] = f(rh, 512 * i);
+        raw[1][i][1] = f(rh, 4 * D2 + 512 * i);
+        raw[1][i][2] = f(rh, 8 * D2 + 512 * i);
+        raw[1][i][3] = f(bh, 512 * i);
+    }
+    char *dst = img + 1024u * (unsigned)wave + 16u * fl;   // + M * V12_AIMG_MLP + 4096 i
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        *reinterpret_cast<vec8 *>(dst + 4096 * i) = v12_affine_frag<DT, 0>(raw[0][i], fl >> 5);
+        *reinterpret_cast<vec8 *>(dst + V12_AIMG_MLP + 4096 * i) = v12_affine_frag<DT, 1>(raw[1][i], fl >> 5);
+    }
+}
+
 // Every per-lane offset below is a 32-bit value derived, inside the item, from ONE opaque copy of the lane index: hipcc hoists
 // whatever depends on the lane index alone out of the tile and column loops (hundreds of values: fragment addresses, list positions,
 // 64-bit pointers) and then spills them - kernel-long live ranges for what is one VALU instruction away.  Global loads are
@@ -95,7 +158,7 @@ __device__ __forceinline__ bool grid_mlp_v12(const char *__restrict__ wbase /* t
                                              const float *__restrict__ gcc /* this column's constants (global) */,
                                              const float *__restrict__ gzv /* z-vectors (global) */,
                                              const unsigned short *__restrict__ w1t /* this MLP's W1t [1024][512] */,
-                                             const float *__restrict__ rvec /* this column's and MLP's vectors RA, RB[, RC]: [2 | 3][512] */,
+                                             const char *aimg /* this column's and MLP's affine A fragments: [16 chunks][64 lanes][16 B] */,
                                              float zmid, float zlo, float zhi, float plo, float phi, char *smem, int wave, int lane_in,
                                              float (&logit)[4], unsigned &ksteps) {
     typedef HalfT<DT> H;
@@ -107,8 +170,8 @@ __device__ __forceinline__ bool grid_mlp_v12(const char *__restrict__ wbase /* t
     gzv += lz;
     wbase += lz;
     w1t += lz;
-    rvec += lz;
-    constexpr int GA0 = M ? CC_A0_HR : CC_A0_LR, GW0Z = M ? ZV_W0Z_HR : ZV_W0Z_LR, GW0P = ZV_W0P_HR, GB1 = M ? ZV_B1_HR : ZV_B1_LR;
+    aimg += lz;
+    constexpr int GA0 = M ? CC_A0_HR : CC_A0_LR, GW0Z = M ? ZV_W0Z_HR : ZV_W0Z_LR, GW0P = ZV_W0P_HR;
     constexpr int W4C = V12_W4C + 512 * M;
     constexpr int GA2 = M ? CC_A2_HR : CC_A2_LR, GA3 = M ? CC_A3_HR : CC_A3_LR;
     constexpr int GW2Z = M ? ZV_W2Z_HR : ZV_W2Z_LR, GW2P = ZV_W2P_HR,
@@ -119,7 +182,6 @@ __device__ __forceinline__ bool grid_mlp_v12(const char *__restrict__ wbase /* t
     const unsigned lane16 = ol * 16u;
     // global loads: uniform base + 32-bit per-lane byte offset + immediate
     auto gld4 = [&](const void *base, unsigned voff, int imm) { return *reinterpret_cast<const f32x4 *>(reinterpret_cast<const char *>(base) + (size_t)voff + imm); };
-    auto gld1 = [&](const void *base, unsigned voff, int imm) { return *reinterpret_cast<const float *>(reinterpret_cast<const char *>(base) + (size_t)voff + imm); };
     auto gldw = [&](unsigned voff, int imm) { return *reinterpret_cast<const vec8 *>(wbase + (size_t)voff + imm); };
     auto lds4 = [&](unsigned off, int imm) { return *reinterpret_cast<const f32x4 *>(smem + off + imm); };
     auto ldsB = [&](unsigned off, int imm) { return *reinterpret_cast<const vec8 *>(smem + off + imm); };
@@ -343,30 +405,21 @@ __device__ __forceinline__ bool grid_mlp_v12(const char *__restrict__ wbase /* t
     __builtin_amdgcn_sched_barrier(0);
     acc2_init(1);
     __builtin_amdgcn_sched_barrier(0);
-    // ---- the affine part's A fragment of a chunk's row tile (v10's slot order), from the column's vectors R
-    const unsigned l4 = (ol & 31u) * 4u;
-    const float *rvec2 = rvec + 2 * D2;   // (uniform bases keep every immediate inside the instruction's 12 bits)
-    const float *gb1 = gzv + GB1;
-    float raw[4];
+    // ---- the affine part's A fragment of a chunk's row tile: ONE 16-byte load per lane from the image the per-column part built
+    //      (v12_affine_build): (a UNIFORM base stepped by the chunk's 1 KiB, in scalar registers) + (32-bit per-lane offset), no
+    //      immediate and no vector instruction (NOTES "affine fragments once per column": the forms hipcc made of the others).
+    vec8 anext;
+    unsigned al16 = lane16;   // (a copy of its own, re-made opaque in place in front of every load: the 64-bit extension of a value made
+                              //  once per item is hoisted into a register PAIR, and the load then takes a 64-bit vector add per chunk)
     auto affine_load = [&](int j) {
-        raw[0] = gld1(rvec, l4, 128 * j);
-        raw[1] = gld1(rvec, l4, 4 * D2 + 128 * j);
-        raw[2] = M ? gld1(rvec2, l4, 128 * j) : 0.0f;
-        raw[3] = gld1(gb1, l4, 128 * j);
-    };
-    auto affine_frag = [&]() {
-        const elem zero = (elem)0.0f;
-        elem pa[3], pb[3], pc[3] = {zero, zero, zero};
-        split3_elem<DT>(raw[0] + raw[3], pa);
-        split3_elem<DT>(raw[1], pb);
-        if (M) split3_elem<DT>(raw[2], pc);
-        const vec8 flo = {pa[0], pa[1], pa[2], pb[0], pb[0], pb[1], pb[0], pb[1]};
-        const vec8 fhi = {pb[2], pc[0], pc[0], pc[1], pc[0], pc[1], pc[2], zero};
-        const vec8 r = hh ? fhi : flo;
-        return r;
+        const char *cb = aimg + 1024 * j;
+        asm volatile("" : "+s"(cb), "+v"(al16));
+        typedef const __attribute__((address_space(1))) char global_char;   // (behind the asm the pointer's address space is unknown: a FLAT load otherwise)
+        typedef const __attribute__((address_space(1))) vec8 global_vec8;
+        anext = *(global_vec8 *)((global_char *)cb + (size_t)al16);
     };
     affine_load(0);
-    vec8 ai = affine_frag();
+    vec8 ai = anext;
     // ---- layer 2's weights: per k-step the fragments of row tiles 2 w, 2 w + 1 (2 KiB of the k-step's 8 KiB); each fragment is
     //      reloaded in place, for the next stage, right after its last MFMA of this stage
     vec8 a2[2][2];   // [k-step of the stage][row tile]
@@ -470,7 +523,7 @@ __device__ __forceinline__ bool grid_mlp_v12(const char *__restrict__ wbase /* t
 #pragma unroll
             for (int u = 0; u < 2; ++u) *reinterpret_cast<vec8 *>(smem + yw + V12_RING + (j & 1) * 8192 + u * 4096) = cvt8(acc1, u);
         }
-        if (j + 1 <= 15) ai = affine_frag();
+        if (j + 1 <= 15) ai = anext;
         __builtin_amdgcn_sched_barrier(0);
         if (j <= 15) __syncthreads();   // chunk j in the ring; everyone is done with ring[(j - 1) & 1] and slice buffer j & 1
 #ifdef SURS_V3_TRACE
@@ -665,7 +718,13 @@ __global__ __launch_bounds__(V12_THREADS, 2) void grid_mlp_kernel_v12(GridArgs a
         const float *rv_lr = a.rvec_lr + (size_t)col * (2 * D2), *rv_hr = a.rvec_hr + (size_t)col * (3 * D2);
         const int cnt = a.kcount ? __builtin_amdgcn_readfirstlane(a.kcount[col]) : a.rz;
         const unsigned short *kl = a.klist ? a.klist + (size_t)col * a.rz : nullptr;
-        __syncthreads();
+        // the column's affine A fragments, once for its z tiles and waves (a column without items builds none)
+        char *aimg = a.aimg + (size_t)blockIdx.x * V12_AIMG_BYTES;
+        if (cnt > 0) {
+            const unsigned fl = fresh_lane();
+            v12_affine_build<DT>(rv_lr, rv_hr, a.zvec, aimg, wave, fl);
+        }
+        __syncthreads();   // the column's constants and its fragment image are there
         for (int zc = 0; zc < nzc; ++zc) {
             if (zc * 128 >= cnt) break;
 #ifdef SURS_V3_TRACE
@@ -695,7 +754,7 @@ __global__ __launch_bounds__(V12_THREADS, 2) void grid_mlp_kernel_v12(GridArgs a
             // a tile that lists more channels than the stream stages (either classifier) is handed, whole, to kernel v10's tile
             // mode, which runs behind this launch on the tiles listed here: same bits, and no slow path in this kernel
             unsigned kst = 0;
-            bool done = grid_mlp_v12<DT, 0>(w_lr, src, a.zvec, w1t, rv_lr, a.zmid, zlo, zhi, 0.0f, 0.0f, smem, wave, (int)fresh_lane(), l, kst);
+            bool done = grid_mlp_v12<DT, 0>(w_lr, src, a.zvec, w1t, aimg, a.zmid, zlo, zhi, 0.0f, 0.0f, smem, wave, (int)fresh_lane(), l, kst);
             if (!done) {
                 if (tid == 0) {
                     const unsigned t = atomicAdd(a.ovf_count, 1u);
@@ -740,7 +799,7 @@ __global__ __launch_bounds__(V12_THREADS, 2) void grid_mlp_kernel_v12(GridArgs a
                 plo = fminf(l0, l1);
                 phi = fmaxf(h0, h1);
             }
-            done = grid_mlp_v12<DT, 1>(w_hr, src, a.zvec, w1t + (size_t)D1 * D2, rv_hr, a.zmid, zlo, zhi, plo, phi, smem, wave, (int)fresh_lane(), l, kst);
+            done = grid_mlp_v12<DT, 1>(w_hr, src, a.zvec, w1t + (size_t)D1 * D2, aimg + V12_AIMG_MLP, a.zmid, zlo, zhi, plo, phi, smem, wave, (int)fresh_lane(), l, kst);
             if (!done) {
                 if (tid == 0) {
                     const unsigned t = atomicAdd(a.ovf_count, 1u);

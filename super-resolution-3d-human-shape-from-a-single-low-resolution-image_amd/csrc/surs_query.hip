@@ -571,6 +571,9 @@ struct GridArgs {
     // with tile_list set walks those instead of whole columns
     unsigned *ovf_count;
     int *ovf_list;
+    // kernel v12: the affine layer-1 A fragments of the column each workgroup is on, [workgroup][V12_AIMG_BYTES] (written and read
+    // by that workgroup alone)
+    char *aimg;
     const int *tile_list;
     const unsigned *tile_count;
     double z0, dz;  // world z of voxel k = (float)(dz*k + z0)
@@ -1257,6 +1260,7 @@ static int run_column_batch(const ColumnSweep &cs, const PointSource &src, long 
     a.klist = klist;
     a.ovf_count = nullptr;
     a.ovf_list = nullptr;
+    a.aimg = nullptr;
     a.tile_list = cs.run_tiles;
     a.tile_count = cs.run_ntiles;
     a.colstart = cs.run_colstart;
@@ -1378,6 +1382,11 @@ static int run_column_batch(const ColumnSweep &cs, const PointSource &src, long 
 #endif
         a.ovf_count = a.colctr + 1;
         a.ovf_list = (int *)((char *)workspace + col_base_bytes(COL_BATCH));
+        // (and behind the room that list can need - every z tile of every column -, the workgroups' fragment images)
+        const size_t ovf_room = ((size_t)nc * ((items + 127) / 128) * 2 * sizeof(int) + 4095) / 4096 * 4096;
+        SURS_REQUIRE(ovf_room + (size_t)grid12 * V12_AIMG_BYTES <= col_v7_image_bytes(COL_BATCH),
+                     "kernel v12's overflow list and fragment images do not fit the g-scaled split image");
+        a.aimg = (char *)a.ovf_list + ovf_room;
         const int lds12 = GRID12_LDS_BYTES;
         if (dtype == SURS_BF16)
             hipLaunchKernelGGL(grid_mlp_kernel_v12<SURS_BF16>, dim3(grid12), dim3(V12_THREADS), lds12, st, a);
