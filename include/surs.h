@@ -830,6 +830,58 @@ int surs_mc_slab_fixup(int32_t *faces, long long n_faces, int own_offset, const 
  * matrix): the vertex transform of lib/mesh_util.py:42-43,47-48.  verts fp32 [n][3], out fp64 [n][3]. */
 int surs_transform_points(const float *verts, int n, const double *mat, double *out, void *stream);
 
+/* ---------------------------------------------------------------- training samples
+ * What TrainDataset_LR_v2.select_sampling_method (lib/data/TrainDataset_LR_v2.py:357-438) makes per item, on the device:
+ * the pool of jittered surface samples and box points, the inside / outside test of the pool against the HR and the LR mesh,
+ * the truncated selection and the displacement labels.  A mesh is verts [nv][3] fp32 and faces [nf][3] int32 (indices are
+ * clamped to [0, nv): a bad index reads a wrong vertex, never out of bounds).  Every call returns the same bits for the same
+ * arguments (no atomics, fixed summation orders). */
+
+/* Triangles per face part of surs_mesh_contains, and the pool entries surs_sample_select's workgroup takes per round. */
+#define SURS_MESH_FACES_PER_PART 4096
+#define SURS_SAMPLE_SELECT_CHUNK 1024
+
+/* inside[i] = |w(p_i)| > 0.5, w the generalized winding number of the mesh around p_i = points[i * ld .. + 3] (ld >= 3):
+ *     w(p) = 1/(4 pi) sum_f 2 atan2(a.(b x c), |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|),   a, b, c = v - p,
+ * summed by brute force over all faces (no acceleration structure).  The absolute value makes a consistently inward-oriented
+ * mesh answer like a parity test.  A zero-area triangle and a triangle with a vertex at p contribute 0: the result is finite
+ * for finite input.  winding (nullable) receives w.  The faces are split into surs_mesh_contains_parts(nf) parts of
+ * SURS_MESH_FACES_PER_PART - a function of nf alone -, each part's sum goes to workspace [parts][n] floats and the parts are
+ * added in index order: a point's bits do not depend on n or on the other points of the call. */
+int surs_mesh_contains_parts(int nf);
+size_t surs_mesh_contains_workspace_bytes(int n, int nf);
+int surs_mesh_contains(const float *points, int n, int ld, const float *verts, int nv, const int32_t *faces, int nf,
+                       void *workspace, size_t workspace_bytes, unsigned char *inside, float *winding, void *stream);
+
+/* cdf[f] = sum of the areas of faces 0 .. f, float64 [nf]; the area 0.5 |(v1 - v0) x (v2 - v0)| in float64 from the fp32
+ * vertices. */
+int surs_mesh_area_cdf(const float *verts, int nv, const int32_t *faces, int nf, double *cdf, void *stream);
+
+/* One item's pool: points [n_surface + n_box][3] fp32, surface samples first, in generation order.  Every random number is
+ * value i of a named stream of the package's counter PRNG (prng.py: splitmix64(fnv1a64(name) ^ seed * GOLDEN + i), top 24
+ * bits / 2^24; the names are "train_samples_" + face, r1, r2, jitter_radius, jitter_angle, box, shuffle).
+ * Surface sample i: the first face f with cdf[f] > u_face[i] * cdf[nf - 1]; (r1, r2) = (u_r1[i], u_r2[i]), reflected to
+ * (1 - r1, 1 - r2) if r1 + r2 > 1; p = v0 + r1 (v1 - v0) + r2 (v2 - v0); coordinate c gains sigma * sqrt(-2 ln((k + 1) / 2^24))
+ * cos(2 pi u_angle[3 i + c]), k the 24 bits of jitter_radius[3 i + c].  Box sample j: b_min + u_box[3 j + c] * (b_max - b_min).
+ * b_min / b_max: HOST [3].  sort_keys [n_surface + n_box] int64 receives the shuffle stream's raw 64-bit value with the top bit
+ * flipped: sorting them as signed integers (ties by index) is the shuffle.  face_index (nullable, int32 [n_surface]) receives
+ * each surface sample's face. */
+int surs_mesh_sample_pool(const float *verts, int nv, const int32_t *faces, int nf, const double *cdf, unsigned long long seed,
+                          int n_surface, int n_box, float sigma, const float *b_min, const float *b_max, float *points,
+                          long long *sort_keys, int32_t *face_index, void *stream);
+
+/* The selection of lines 390-423 on the shuffled pool [n_pool] (row pitch ld >= 3) and its two flag arrays, n =
+ * num_sample_inout (even).  Per mesh: more than n / 2 points inside -> the first n / 2 inside, then the first n / 2 outside;
+ * otherwise all inside points, then the first n - nin outside; pool order kept.  samples_hr [3][n], labels_hr [n] (1 inside),
+ * samples_lr [3][n]; labels_disp [n] = n / 2 ones then n / 2 zeros, entry i of each half overwritten for i < len(inside_LR)
+ * with the HR flag of the i-th selected inside / outside LR point (the reference's `p in outside_points_HR` / `in
+ * inside_points_HR`).  Where the pool has fewer outside points than the rule takes, the reference returns shorter arrays (or
+ * fails in its loop); here the columns behind the selection are zero and counts (nullable, DEVICE int32 [4]) receives the
+ * selected (inside HR, outside HR, inside LR, outside LR).  One launch, no host synchronisation. */
+int surs_sample_select(const float *pool, int ld, int n_pool, const unsigned char *inside_hr, const unsigned char *inside_lr,
+                       int n, float *samples_hr, float *labels_hr, float *samples_lr, float *labels_disp, int32_t *counts,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

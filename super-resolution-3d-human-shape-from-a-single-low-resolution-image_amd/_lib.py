@@ -253,7 +253,15 @@ _SIGS = {
     "surs_mc_slab_top_ids": (C.c_int, [_vp, _sz, _i, _i, _i, _vp, _vp]),
     "surs_mc_slab_fixup": (C.c_int, [_vp, C.c_longlong, _i, _vp, _i, _vp]),
     "surs_mc_lewiner": (C.c_int, [_vp, _i, _i, _i, C.c_double, _vp, _sz, _vp, _vp, _vp, _i, _vp, _i, C.POINTER(McCounts), _vp]),
+    "surs_mesh_contains_parts": (C.c_int, [_i]),
+    "surs_mesh_contains_workspace_bytes": (_sz, [_i, _i]),
+    "surs_mesh_contains": (C.c_int, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp]),
+    "surs_mesh_area_cdf": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp]),
+    "surs_mesh_sample_pool": (C.c_int, [_vp, _i, _vp, _i, _vp, C.c_ulonglong, _i, _i, _f, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                        _vp, _vp, _vp, _vp]),
+    "surs_sample_select": (C.c_int, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
+MESH_FACES_PER_PART, SAMPLE_SELECT_CHUNK = 4096, 1024     # SURS_MESH_FACES_PER_PART, SURS_SAMPLE_SELECT_CHUNK of include/surs.h
 EXPORTS = sorted(_SIGS)
 
 

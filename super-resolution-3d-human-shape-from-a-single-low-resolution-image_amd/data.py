@@ -139,3 +139,205 @@ class SyntheticDataset:
         return {"name": ("synthetic_%04d" % i, ".png"), "b_min": np.array(self.opt.b_min, dtype=float),
                 "b_max": np.array(self.opt.b_max, dtype=float),
                 "img_LR": torch.from_numpy(self._w.synthetic_image(self.size, seed=1 + i)), "calib": torch.from_numpy(calib[None])}
+
+
+class TrainDataset:
+    """The item contract of the reference's TrainDataset_LR_v2 (lib/data/TrainDataset_LR_v2.py):
+
+        dataroot/RENDER/<subject>/<yaw>_<pitch>_00.{jpg,png}   dataroot/MASK/<subject>/<yaw>_<pitch>_00.{png,jpg}
+        dataroot/PARAM/<subject>/<yaw>_<pitch>_00.npy          {'ortho_ratio', 'scale', 'center', 'R'}
+        dataroot/GEO/OBJ/<subject>_HR.obj, <subject>_LR.obj     dataroot/val.txt
+        item = {'name', 'mesh_path_HR', 'mesh_path_LR', 'sid', 'yid', 'pid', 'b_min', 'b_max',
+                'img_LR' [V,3,H/2,W/2], 'img_HR' [V,3,H,W], 'calib' [V,4,4], 'extrinsic' [V,4,4]            (host tensors)
+                'samples_HR' [3,N], 'samples_LR' [3,N], 'labels_HR' [1,N], 'labels_disp' [1,N]}              (DEVICE tensors)
+
+    get_render is PIL and numpy on the host and draws from `random` / `np.random` exactly where the reference does (lines
+    194-355); torchvision's ColorJitter is not available: a non-zero --aug_bri / --aug_con / --aug_sat / --aug_hue raises.
+    select_sampling_method runs on the device (native.mesh_sample_pool, two native.mesh_contains, native.sample_select): the
+    pool comes from the package's counter PRNG, not from numpy's generator, and inside / outside is the winding number's
+    answer.  Meshes are parsed and uploaded once per subject, at their first use.  Phase 'test' draws every item's samples
+    from seed 1991 (the reference re-seeds with 1991 before each item); phase 'train' derives the seed from (seed, index, how
+    many items this object has drawn).  The samples are made on the GPU of the calling process, so the dataset refuses to run
+    in a DataLoader worker: use --num_threads 0.  get_color_sampling is not built (SuRS trains with --num_sample_color 0)."""
+
+    _JITTER = ("aug_bri", "aug_con", "aug_sat", "aug_hue")
+    TEST_SEED = 1991
+
+    def __init__(self, opt, phase="train", seed=0):
+        for k in self._JITTER:
+            if float(getattr(opt, k, 0.0)) != 0.0:
+                raise NotImplementedError("--%s %g: colour jitter (torchvision ColorJitter) is not built; only 0 is accepted"
+                                          % (k, getattr(opt, k)))
+        self.opt = opt
+        self.projection_mode = "orthogonal"
+        self.root = opt.dataroot
+        self.RENDER = os.path.join(self.root, "RENDER")
+        self.MASK = os.path.join(self.root, "MASK")
+        self.PARAM = os.path.join(self.root, "PARAM")
+        self.OBJ = os.path.join(self.root, "GEO", "OBJ")
+        self.B_MIN = np.array(opt.b_min, dtype=float)
+        self.B_MAX = np.array(opt.b_max, dtype=float)
+        self.is_train = phase == "train"
+        self.load_size = opt.loadSize
+        self.num_views = opt.num_views
+        self.num_sample_inout = opt.num_sample_inout
+        self.num_sample_color = opt.num_sample_color
+        self.yaw_list = list(range(0, 360, 1))
+        self.pitch_list = [0]
+        self.subjects = self.get_subjects()
+        self.seed = int(seed)
+        self.draws = 0
+        self._meshes = {}
+
+    def get_subjects(self):
+        all_subjects = os.listdir(self.RENDER)
+        var_subjects = np.atleast_1d(np.loadtxt(os.path.join(self.root, "val.txt"), dtype=str))
+        if len(var_subjects) == 0:
+            return all_subjects
+        if self.is_train:
+            return sorted(list(set(all_subjects) - set(var_subjects)))
+        return sorted(list(var_subjects))
+
+    def __len__(self):
+        return len(self.subjects) * len(self.yaw_list) * len(self.pitch_list)
+
+    @staticmethod
+    def _to_tensor(img):
+        """transforms.ToTensor: [C,H,W] float32 in [0, 1]."""
+        a = np.asarray(img, np.uint8)
+        a = a[None] if a.ndim == 2 else a.transpose(2, 0, 1)
+        return np.ascontiguousarray(a).astype(np.float32) / np.float32(255.0)
+
+    def get_render(self, subject, num_views, yid=0, pid=0, random_sample=False):
+        import random
+        from PIL import Image, ImageOps
+        from PIL.ImageFilter import GaussianBlur
+        pitch = self.pitch_list[pid]
+        view_ids = [self.yaw_list[(yid + len(self.yaw_list) // num_views * offset) % len(self.yaw_list)] for offset in range(num_views)]
+        if random_sample:
+            view_ids = np.random.choice(self.yaw_list, num_views, replace=False)
+        half = float(self.opt.loadSize // 2)
+        out = {"img_LR": [], "img_HR": [], "calib": [], "extrinsic": []}
+        for vid in view_ids:
+            stem = "%d_%d_%02d" % (vid, pitch, 0)
+            param_path = os.path.join(self.PARAM, subject, stem + ".npy")
+            render_path = EvalDataset._first_existing(os.path.join(self.RENDER, subject, stem + ".jpg"),
+                                                      os.path.join(self.RENDER, subject, stem + ".png"))
+            mask_path = EvalDataset._first_existing(os.path.join(self.MASK, subject, stem + ".png"),
+                                                    os.path.join(self.MASK, subject, stem + ".jpg"))
+            param = np.load(param_path, allow_pickle=True).item()
+            ortho_ratio, scale, center, R = param.get("ortho_ratio"), param.get("scale"), param.get("center"), param.get("R")
+            translate = -np.matmul(R, center).reshape(3, 1)
+            extrinsic = np.concatenate([R, translate], axis=1)
+            extrinsic = np.concatenate([extrinsic, np.array([0, 0, 0, 1]).reshape(1, 4)], 0)
+            scale_intrinsic = np.identity(4)            # camera space -> image pixel space
+            scale_intrinsic[0, 0] = scale / ortho_ratio
+            scale_intrinsic[1, 1] = -scale / ortho_ratio
+            scale_intrinsic[2, 2] = scale / ortho_ratio
+            uv_intrinsic = np.identity(4)               # image pixel space -> uv space
+            uv_intrinsic[0, 0] = uv_intrinsic[1, 1] = uv_intrinsic[2, 2] = 1.0 / half
+            trans_intrinsic = np.identity(4)
+            mask_HR = Image.open(mask_path).convert("L")
+            render_HR = Image.open(render_path).convert("RGB")
+            if self.is_train:
+                pad_size = int(0.1 * self.load_size)
+                render_HR = ImageOps.expand(render_HR, pad_size, fill=0)
+                mask_HR = ImageOps.expand(mask_HR, pad_size, fill=0)
+                w, h = render_HR.size
+                th, tw = self.load_size, self.load_size
+                if self.opt.random_flip and np.random.rand() > 0.5:
+                    scale_intrinsic[0, 0] *= -1
+                    render_HR = render_HR.transpose(Image.FLIP_LEFT_RIGHT)
+                    mask_HR = mask_HR.transpose(Image.FLIP_LEFT_RIGHT)
+                if self.opt.random_scale:
+                    rand_scale = random.uniform(0.9, 1.1)
+                    w = int(rand_scale * w)
+                    h = int(rand_scale * h)
+                    render_HR = render_HR.resize((w, h), Image.BILINEAR)
+                    mask_HR = mask_HR.resize((w, h), Image.NEAREST)
+                    scale_intrinsic *= rand_scale
+                    scale_intrinsic[3, 3] = 1
+                if self.opt.random_trans:
+                    dx = random.randint(-int(round((w - tw) / 10.)), int(round((w - tw) / 10.)))
+                    dy = random.randint(-int(round((h - th) / 10.)), int(round((h - th) / 10.)))
+                else:
+                    dx = dy = 0
+                trans_intrinsic[0, 3] = -dx / half
+                trans_intrinsic[1, 3] = -dy / half
+                x1 = int(round((w - tw) / 2.)) + dx
+                y1 = int(round((h - th) / 2.)) + dy
+                render_HR = render_HR.crop((x1, y1, x1 + tw, y1 + th))
+                mask_HR = mask_HR.crop((x1, y1, x1 + tw, y1 + th))
+                # (aug_trans: ColorJitter with all four amounts 0 is the identity; anything else was refused in __init__)
+                if self.opt.aug_blur > 0.00001:
+                    render_HR = render_HR.filter(GaussianBlur(np.random.uniform(0, self.opt.aug_blur)))
+            intrinsic = np.matmul(trans_intrinsic, np.matmul(uv_intrinsic, scale_intrinsic))
+            calib = np.matmul(intrinsic, extrinsic).astype(np.float32)
+            mask_LR = mask_HR.resize([x // 2 for x in mask_HR.size], Image.NEAREST)
+            render_LR = render_HR.resize([x // 2 for x in render_HR.size], Image.BICUBIC)
+            pair = []
+            for mask, render in ((mask_LR, render_LR), (mask_HR, render_HR)):
+                m = self._to_tensor(mask)
+                r = (self._to_tensor(render) - np.float32(0.5)) / np.float32(0.5)     # Normalize(0.5, 0.5)
+                pair.append(torch.from_numpy(np.ascontiguousarray(m * r)))
+            out["img_LR"].append(pair[0])
+            out["img_HR"].append(pair[1])
+            out["calib"].append(torch.from_numpy(calib))
+            out["extrinsic"].append(torch.from_numpy(extrinsic.astype(np.float32)))
+        return {k: torch.stack(v, dim=0) for k, v in out.items()}
+
+    def item_seed(self, index=0):
+        """The counter PRNG's seed of the next item's samples."""
+        if not self.is_train:
+            return self.TEST_SEED
+        from . import prng
+        return int(prng.bits64("train_item_%d_%d" % (self.seed, int(index)), self.draws, 1)[0] >> np.uint64(1))
+
+    def _mesh(self, name):
+        """native.Mesh of GEO/OBJ/<name>, parsed and uploaded at its first use."""
+        if name not in self._meshes:
+            from . import mesh_util, native
+            v, f = mesh_util.load_obj_mesh(os.path.join(self.OBJ, name))
+            self._meshes[name] = native.Mesh(v, f)
+        return self._meshes[name]
+
+    def select_sampling_method(self, subject, index=0):
+        from . import native
+        self._refuse_worker()
+        name = subject[0] if isinstance(subject, (tuple, list)) else subject
+        mesh_HR, mesh_LR = self._mesh(name + "_HR.obj"), self._mesh(name + "_LR.obj")
+        n = self.num_sample_inout
+        seed = self.item_seed(index)
+        self.draws += 1
+        pool, _ = native.mesh_sample_pool(mesh_HR, 4 * n, n // 4, self.opt.sigma, self.B_MIN, self.B_MAX, seed)
+        inside_HR = native.mesh_contains(pool, mesh_HR)
+        inside_LR = native.mesh_contains(pool, mesh_LR)
+        s_hr, l_hr, s_lr, l_disp, _ = native.sample_select(pool, inside_HR, inside_LR, n)
+        return {"samples_HR": s_hr, "samples_LR": s_lr, "labels_HR": l_hr, "labels_disp": l_disp}
+
+    @staticmethod
+    def _refuse_worker():
+        import torch.utils.data
+        if torch.utils.data.get_worker_info() is not None:
+            raise RuntimeError("TrainDataset makes its samples on the GPU of the calling process and cannot run in a DataLoader "
+                               "worker: use --num_threads 0")
+
+    def get_item(self, index):
+        self._refuse_worker()
+        sid = index % len(self.subjects)
+        tmp = index // len(self.subjects)
+        yid = tmp % len(self.yaw_list)
+        pid = tmp // len(self.yaw_list)
+        subject = os.path.splitext(self.subjects[sid])
+        res = {"name": subject, "mesh_path_HR": os.path.join(self.OBJ, subject[0] + "_HR.obj"),
+               "mesh_path_LR": os.path.join(self.OBJ, subject[0] + "_LR.obj"), "sid": sid, "yid": yid, "pid": pid,
+               "b_min": self.B_MIN, "b_max": self.B_MAX}
+        res.update(self.get_render(subject[0], num_views=self.num_views, yid=yid, pid=pid, random_sample=self.opt.random_multiview))
+        if self.opt.num_sample_inout:
+            res.update(self.select_sampling_method(subject, index))
+        if self.num_sample_color:
+            raise NotImplementedError("--num_sample_color %d: get_color_sampling is not built" % self.num_sample_color)
+        return res
+
+    def __getitem__(self, index):
+        return self.get_item(index)

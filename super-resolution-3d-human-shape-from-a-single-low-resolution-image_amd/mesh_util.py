@@ -398,3 +398,33 @@ def save_obj_mesh_with_color(mesh_path, verts, faces, colors):
             fh.write("v %.4f %.4f %.4f %.4f %.4f %.4f\n" % (v[0], v[1], v[2], c[0], c[1], c[2]))
         for f in np.asarray(faces, np.int64) + 1:
             fh.write("f %d %d %d\n" % (f[0], f[2], f[1]))
+
+
+def load_obj_mesh(path):
+    """(verts float64 [nv,3], faces int32 [nf,3], 0-based) of a Wavefront OBJ file: `v x y z [...]` and `f` records; a face
+    entry may be `a`, `a/b`, `a//c` or `a/b/c` (the vertex index is the first field), a negative index counts back from the
+    vertices read so far, and a polygon of k corners becomes the fan (0, i, i + 1), i = 1 .. k - 2.  Every other record is
+    skipped.  Plain numpy: what the training dataset needs of trimesh.load."""
+    verts, faces = [], []
+    with open(path) as fh:
+        for no, line in enumerate(fh, 1):
+            rec = line.split()
+            if not rec:
+                continue
+            if rec[0] == "v":
+                if len(rec) < 4:
+                    raise ValueError("%s:%d: a vertex needs three coordinates" % (path, no))
+                verts.append((float(rec[1]), float(rec[2]), float(rec[3])))
+            elif rec[0] == "f":
+                idx = []
+                for entry in rec[1:]:
+                    i = int(entry.split("/")[0])
+                    i = i - 1 if i > 0 else len(verts) + i
+                    if i < 0 or i >= len(verts) or entry.split("/")[0] == "0":
+                        raise ValueError("%s:%d: vertex index %s out of range" % (path, no, entry))
+                    idx.append(i)
+                if len(idx) < 3:
+                    raise ValueError("%s:%d: a face needs three corners" % (path, no))
+                for k in range(1, len(idx) - 1):
+                    faces.append((idx[0], idx[k], idx[k + 1]))
+    return np.asarray(verts, np.float64).reshape(-1, 3), np.asarray(faces, np.int32).reshape(-1, 3)

@@ -1987,3 +1987,94 @@ def f64_to_f32(a):
     out = torch.empty(a.shape, dtype=torch.float32, device=a.device)
     check(lib().surs_f64_to_f32(_ptr(a), _ptr(out), a.numel(), _stream()))
     return out
+
+
+# ------------------------------------------------------------------ training samples (include/surs.h "training samples")
+
+class Mesh:
+    """A triangle mesh on the device: verts [nv,3] float32, faces [nf,3] int32 and the float64 area cdf [nf] (surs_mesh_area_cdf),
+    uploaded and computed once.  Indices are checked on the host here; the kernels clamp them."""
+
+    def __init__(self, verts, faces, device=None):
+        device = device or require_gpu()
+        v = np.ascontiguousarray(np.asarray(verts, np.float32).reshape(-1, 3))
+        f = np.ascontiguousarray(np.asarray(faces, np.int64).reshape(-1, 3))
+        if len(v) == 0 or len(f) == 0:
+            raise ValueError("a mesh needs vertices and faces")
+        if f.min() < 0 or f.max() >= len(v):
+            raise ValueError("face index out of range: [%d, %d] with %d vertices" % (f.min(), f.max(), len(v)))
+        if not np.isfinite(v).all():
+            raise ValueError("mesh vertices must be finite")
+        self.verts = torch.from_numpy(v).to(device)
+        self.faces = torch.from_numpy(f.astype(np.int32)).to(device)
+        self.nv, self.nf = len(v), len(f)
+        self.cdf = mesh_area_cdf(self.verts, self.faces)
+
+
+def mesh_area_cdf(verts, faces):
+    """float64 [nf]: inclusive prefix sum of the face areas."""
+    assert verts.dtype == torch.float32 and faces.dtype == torch.int32 and verts.is_contiguous() and faces.is_contiguous()
+    cdf = torch.empty(faces.shape[0], dtype=torch.float64, device=verts.device)
+    check(lib().surs_mesh_area_cdf(_ptr(verts), verts.shape[0], _ptr(faces), faces.shape[0], _ptr(cdf), _stream()))
+    return cdf
+
+
+def mesh_contains_parts(nf):
+    return lib().surs_mesh_contains_parts(int(nf))
+
+
+def mesh_contains(points, mesh, want_winding=False):
+    """points [n, >= 3] float32 (rows may be wider than 3: the row stride is the kernel's ld) -> uint8 [n], 1 where the
+    generalized winding number's magnitude exceeds 0.5; with want_winding also the winding numbers, float32 [n]."""
+    assert points.dtype == torch.float32 and points.dim() == 2 and points.shape[1] >= 3
+    n = points.shape[0]
+    assert n == 0 or points.stride(1) == 1, "points: unit stride along a row"
+    ld = points.stride(0) if n > 1 else max(3, points.shape[1])
+    assert ld >= 3
+    inside = torch.empty(n, dtype=torch.uint8, device=points.device)
+    winding = torch.empty(n, dtype=torch.float32, device=points.device) if want_winding else None
+    if n:
+        nbytes = lib().surs_mesh_contains_workspace_bytes(n, mesh.nf)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=points.device)
+        check(lib().surs_mesh_contains(_ptr(points), n, ld, _ptr(mesh.verts), mesh.nv, _ptr(mesh.faces), mesh.nf, _ptr(ws), nbytes,
+                                       _ptr(inside), _ptr(winding), _stream()))
+    return (inside, winding) if want_winding else inside
+
+
+def mesh_sample_pool(mesh, n_surface, n_box, sigma, b_min, b_max, seed, want_faces=False, shuffle=True):
+    """One item's pool [n_surface + n_box, 3] float32 from the counter PRNG's streams of `seed`: jittered surface samples,
+    then box points, then - shuffle - reordered by the shuffle stream's keys (torch.sort, stable: ties by index).  Returns
+    (points, order); order is None without the shuffle; with want_faces also the surface samples' faces (generation order)."""
+    n = n_surface + n_box
+    dev = mesh.verts.device
+    pts = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    fidx = torch.empty(n_surface, dtype=torch.int32, device=dev) if want_faces else None
+    lo, hi = (C.c_float * 3)(*[float(x) for x in b_min]), (C.c_float * 3)(*[float(x) for x in b_max])
+    check(lib().surs_mesh_sample_pool(_ptr(mesh.verts), mesh.nv, _ptr(mesh.faces), mesh.nf, _ptr(mesh.cdf), int(seed) & (2 ** 64 - 1),
+                                      n_surface, n_box, float(sigma), lo, hi, _ptr(pts), _ptr(keys), _ptr(fidx), _stream()))
+    order = None
+    if shuffle:
+        order = torch.sort(keys, stable=True)[1]
+        pts = pts[order]
+    return (pts, order, fidx) if want_faces else (pts, order)
+
+
+def sample_select(pool, inside_hr, inside_lr, n):
+    """The reference's selection on the shuffled pool [P, 3] and its flags (uint8 [P]): samples_HR [3,n], labels_HR [1,n],
+    samples_LR [3,n], labels_disp [1,n] and the selected counts (int32 [4], device: inside HR, outside HR, inside LR, outside LR).
+    No host synchronisation."""
+    assert pool.dtype == torch.float32 and pool.dim() == 2 and pool.shape[1] >= 3 and (pool.shape[0] == 0 or pool.stride(1) == 1)
+    assert inside_hr.dtype == torch.uint8 and inside_lr.dtype == torch.uint8
+    P = pool.shape[0]
+    assert inside_hr.numel() == P and inside_lr.numel() == P and inside_hr.is_contiguous() and inside_lr.is_contiguous()
+    dev = pool.device
+    s_hr = torch.empty((3, n), dtype=torch.float32, device=dev)
+    s_lr = torch.empty((3, n), dtype=torch.float32, device=dev)
+    l_hr = torch.empty((1, n), dtype=torch.float32, device=dev)
+    l_disp = torch.empty((1, n), dtype=torch.float32, device=dev)
+    counts = torch.empty(4, dtype=torch.int32, device=dev)
+    ld = pool.stride(0) if P > 1 else max(3, pool.shape[1])
+    check(lib().surs_sample_select(_ptr(pool), ld, P, _ptr(inside_hr), _ptr(inside_lr), int(n), _ptr(s_hr), _ptr(l_hr), _ptr(s_lr),
+                                   _ptr(l_disp), _ptr(counts), _stream()))
+    return s_hr, l_hr, s_lr, l_disp, counts

@@ -4,6 +4,7 @@ Same flag names and defaults as the reference's argparse set
 (/root/reference/lib/options.py:5-214) so that a reference command line such as
 README.md:41-44 parses unchanged.  Flags that only the reference's training or
 dataset-rendering code reads are accepted and ignored (listed in `_IGNORED`);
+the training dataset's are in `_TRAIN_DATA`;
 the four loss weights are read by the validation forward (`_LOSS_WEIGHTS`).
 Table-driven instead of one add_argument call per line.
 """
@@ -52,8 +53,7 @@ _IGNORED = [
     ("gpu_ids", str, "0"), ("num_threads", int, 1), ("batch_size", int, 2), ("learning_rate", float, 1e-3),
     ("learning_rateC", float, 1e-3), ("num_epoch", int, 100), ("freq_plot", int, 10), ("freq_save", int, 50),
     ("freq_save_ply", int, 100), ("resume_epoch", int, -1), ("continue_train", int, -1),
-    ("test_folder_path", str, None), ("sigma", float, 5), ("num_sample_inout", int, 6000),
-    ("num_sample_color", int, 0), ("norm_color", str, "instance"), ("num_hourglass", int, 2),
+    ("test_folder_path", str, None), ("norm_color", str, "instance"), ("num_hourglass", int, 2),
     ("hg_down", str, "ave_pool"), ("hourglass_dim", int, 256), ("mlp_norm", str, "group"),
     ("scale_pifu", float, 0.01), ("gamma", float, 0.1), ("color_loss_type", str, "l1"), ("losses", str, "l1"),
     ("disp_error", int, 1), ("n_train", int, 300), ("n_val", int, 60), ("optimizer", str, "ADAM"),
@@ -61,8 +61,12 @@ _IGNORED = [
     ("ams", float, False), ("weight_decay", float, 0), ("num_gen_mesh_test", int, 1), ("n_colors", int, 3),
     ("checkpoints_path", str, "./checkpoints"), ("load_netC_checkpoint_path", str, None),
     ("load_checkpoint_path", str, None), ("single", str, ""), ("mask_path", str, None), ("img_path", str, None),
-    ("aug_alstd", float, 0.0), ("aug_bri", float, 0.0), ("aug_con", float, 0.0), ("aug_sat", float, 0.0),
-    ("aug_hue", float, 0.0), ("aug_blur", float, 0.0),
+    ("aug_alstd", float, 0.0),
+]
+# read by data.TrainDataset (with --random_flip / --random_scale / --random_trans / --random_multiview of _BOOL_FLAGS)
+_TRAIN_DATA = [
+    ("sigma", float, 5), ("num_sample_inout", int, 6000), ("num_sample_color", int, 0), ("aug_bri", float, 0.0),
+    ("aug_con", float, 0.0), ("aug_sat", float, 0.0), ("aug_hue", float, 0.0), ("aug_blur", float, 0.0),
 ]
 # the weights of SuRSNet.forward's four loss terms (lib/model/SuRSNet.py:265): get_error_lr, get_error_hr, get_errorSR, get_error_disp_1
 _LOSS_WEIGHTS = [("mlp1", float, 1.0), ("mlp2", float, 1.0), ("srweight", float, 1.0), ("dispweight", float, 1.0)]
@@ -90,7 +94,7 @@ class BaseOptions:
         self.initialized = False
 
     def initialize(self, parser):
-        for name, typ, default in _PATH_FLAGS + _IGNORED + _LOSS_WEIGHTS:
+        for name, typ, default in _PATH_FLAGS + _IGNORED + _TRAIN_DATA + _LOSS_WEIGHTS:
             parser.add_argument("--" + name, type=typ, default=default)
         for name, typ, default in _LIST_FLAGS:
             parser.add_argument("--" + name, type=typ, nargs="+", default=list(default))

@@ -29,12 +29,17 @@ def _splitmix64(x: np.ndarray) -> np.ndarray:
     return z
 
 
-def uniform01(name: str, seed: int, n: int) -> np.ndarray:
-    """n float32 values in [0,1), a pure function of (name, seed, index)."""
+def bits64(name: str, seed: int, n: int) -> np.ndarray:
+    """n raw uint64 values, a pure function of (name, seed, index): what uniform01 takes its top 24 bits from."""
     key = (fnv1a64(name) ^ ((seed * _GOLDEN) & _MASK)) & _MASK
     with np.errstate(over="ignore"):
         ctr = np.uint64(key) + np.arange(n, dtype=np.uint64)
-    bits = _splitmix64(ctr) >> np.uint64(40)
+    return _splitmix64(ctr)
+
+
+def uniform01(name: str, seed: int, n: int) -> np.ndarray:
+    """n float32 values in [0,1), a pure function of (name, seed, index)."""
+    bits = bits64(name, seed, n) >> np.uint64(40)
     return (bits.astype(np.float32) * np.float32(1.0 / (1 << 24))).astype(np.float32)
 
 
