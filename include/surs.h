@@ -882,6 +882,55 @@ int surs_sample_select(const float *pool, int ld, int n_pool, const unsigned cha
                        int n, float *samples_hr, float *labels_hr, float *samples_lr, float *labels_disp, int32_t *counts,
                        void *stream);
 
+/* ---------------------------------------------------------------- device repack
+ * The packed images the forward reads (surs_conv_pack_weights*, the blobs of surs_mlp_pack / surs_mlp_pack_generic) rebuilt ON THE
+ * DEVICE from the plain fp32 parameters an optimiser has just stepped: the bytes the host packers give for the same values, without
+ * the copy to the host, the scalar host loops and the upload.  Every pointer is a device pointer - tables of pointers included -,
+ * every entry enqueues on `stream`, allocates nothing and never synchronises; destinations are written in place, so addresses held by
+ * a SursEncoderNet or a captured graph stay valid.  Splits as on the host: hi = f16(w), lo = f16(w - hi), round to nearest even,
+ * subnormal results kept; three parts: bf16, each the rounding of what the previous parts left. */
+
+/* One convolution of a surs_conv_repack table.  w: plain [cout][cin][ksize][ksize]; packed / x2 / x3: the images of
+ * surs_conv_pack_weights / _x2 / _x3, each nullable (not written).  tile_end: the number of tiles of this item and of every item in
+ * front of it in the table (the inclusive prefix sum of surs_conv_repack_tiles) - how a workgroup finds its item. */
+typedef struct SursRepackItem {
+    const float *w;
+    int cout, cin, ksize;
+    int tile_end;
+    float *packed;
+    void *x2;
+    void *x3;
+} SursRepackItem;
+
+/* tiles (64 output channels x 16 input channels of a 3x3, x 64 of a 1x1 convolution) of one item; 0 for an unsupported shape */
+int surs_conv_repack_tiles(int cout, int cin, int ksize);
+/* Writes every image the n items of the DEVICE table name, in full, padding included (a destination that held garbage is valid
+ * afterwards), in ONE launch over the tiles of all items.  A source tile goes through LDS: loads are contiguous runs of the source's
+ * rows, stores contiguous runs of the images.  ksize 1 or 3. */
+int surs_conv_repack(const SursRepackItem *items, int n, void *stream);
+
+/* The stack joint previous + bl(t) + al(l(t)) as one pointwise convolution (lib/model/HGFilters.py:203-206):
+ * w_out [256][256] = w_bl + w_al [256][d] . w_l [d][256], b_out [256] = b_bl + w_al . b_l + b_al; the sums over the d (--hg_dim)
+ * channels in double, in index order, then rounded to fp32.  w_out is the plain weight surs_conv_repack then packs. */
+int surs_conv1x1_merge(const float *w_bl, const float *b_bl, const float *w_al, const float *b_al, const float *w_l, const float *b_l,
+                       int d, float *w_out, float *b_out, void *stream);
+
+/* Rewrites every section of an existing surs_mlp_pack blob (released shape) behind its header from the plain Conv1d weights
+ * [out][in] and biases [out]: w_lr, b_lr, w_hr, b_hr are DEVICE tables of five device pointers each.  dtype: SURS_BF16 / SURS_F16, the
+ * blob's own (the header is neither read nor written).  Byte for byte what surs_mlp_pack gives for the same values. */
+int surs_mlp_repack(int dtype, const float *const *w_lr, const float *const *b_lr, const float *const *w_hr, const float *const *b_hr,
+                    void *blob, void *stream);
+/* The same for a surs_mlp_pack_generic blob: the one-, two- and three-part images and the biases of every layer, padding included
+ * (lr, hr HOST; the tables DEVICE, n_layers pointers each). */
+int surs_mlp_repack_generic(const SursMlpShape *lr, const float *const *w_lr, const float *const *b_lr, const SursMlpShape *hr,
+                            const float *const *w_hr, const float *const *b_hr, void *blob, void *stream);
+/* The two entries above as plain HOST loops over the same per-element arithmetic (csrc/surs_repack_gather.h): every pointer a HOST
+ * pointer, no device needed.  What the gather form is held against the host packers with; not a path of the product. */
+int surs_mlp_repack_host(int dtype, const float *const *w_lr, const float *const *b_lr, const float *const *w_hr,
+                         const float *const *b_hr, void *blob);
+int surs_mlp_repack_generic_host(const SursMlpShape *lr, const float *const *w_lr, const float *const *b_lr, const SursMlpShape *hr,
+                                 const float *const *w_hr, const float *const *b_hr, void *blob);
+
 #ifdef __cplusplus
 }
 #endif

@@ -115,6 +115,13 @@ class MlpShape(C.Structure):
     _fields_ = [("n_layers", C.c_int), ("dims", C.c_int * 9), ("res_mask", C.c_uint)]
 
 
+class RepackItem(C.Structure):
+    """SursRepackItem of include/surs.h: one convolution of a surs_conv_repack table (device pointers; tile_end: the inclusive prefix
+    sum of surs_conv_repack_tiles over the table)."""
+    _fields_ = [("w", C.c_void_p), ("cout", C.c_int), ("cin", C.c_int), ("ksize", C.c_int), ("tile_end", C.c_int),
+                ("packed", C.c_void_p), ("x2", C.c_void_p), ("x3", C.c_void_p)]
+
+
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 _shp = C.POINTER(MlpShape)
 _SIGS = {
@@ -260,6 +267,13 @@ _SIGS = {
     "surs_mesh_sample_pool": (C.c_int, [_vp, _i, _vp, _i, _vp, C.c_ulonglong, _i, _i, _f, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                         _vp, _vp, _vp, _vp]),
     "surs_sample_select": (C.c_int, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "surs_conv_repack_tiles": (C.c_int, [_i, _i, _i]),
+    "surs_conv_repack": (C.c_int, [_vp, _i, _vp]),
+    "surs_conv1x1_merge": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "surs_mlp_repack": (C.c_int, [_i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "surs_mlp_repack_generic": (C.c_int, [_shp, _vp, _vp, _shp, _vp, _vp, _vp, _vp]),
+    "surs_mlp_repack_host": (C.c_int, [_i, _vp, _vp, _vp, _vp, _vp]),
+    "surs_mlp_repack_generic_host": (C.c_int, [_shp, _vp, _vp, _shp, _vp, _vp, _vp]),
 }
 MESH_FACES_PER_PART, SAMPLE_SELECT_CHUNK = 4096, 1024     # SURS_MESH_FACES_PER_PART, SURS_SAMPLE_SELECT_CHUNK of include/surs.h
 EXPORTS = sorted(_SIGS)

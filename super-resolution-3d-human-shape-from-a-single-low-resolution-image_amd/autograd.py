@@ -75,8 +75,8 @@ def super_res_features(net, images_lr, params=None):
         loss = autograd.point_loss(net, torch_hg_filter(feature_lr), feat_hr, ...) + srweight * l1_loss(img_SR, images_hr)
         loss.backward()
     trains the super-resolution network on this package, the hourglass being a torch module with a backward of its own.
-    The VALUES are those of the weights the net has LOADED, not of `params`: after an optimiser step on sr_parameters(), call
-    net.load_state_dict() with the updated values before the next forward (as the classifier example of INTEGRATION.md does).
+    The VALUES are those of the PACKED weights the forward runs on, not of `params`: after an optimiser step on sr_parameters(), call
+    net.commit() before the next forward (as the examples of INTEGRATION.md do): it repacks them on the device from the parameters.
     Nothing else in the package grows a graph: forward()'s error.grad_fn stays None."""
     if params is None:
         params = net.sr_parameters()
@@ -126,8 +126,8 @@ def _hg_apply(net, which, prefixes, x, params):
 def conv_block(net, prefix, x, params=None):
     """ConvBlock `prefix` of image_filter_lr (conv2. / top_m_{s}. / m{s}.b1_{l}. ...) of SuRSNet `net` on x [B,256,h,w], with a grad_fn:
     its backward is net.conv_block_backward() and hands x its gradient and the block's nine entries of `params` - default
-    net.hg_parameters() - theirs, summed over the batch in image order.  The VALUES are those of the weights the net has LOADED (see
-    super_res_features)."""
+    net.hg_parameters() - theirs, summed over the batch in image order.  The VALUES are those of the PACKED weights the forward runs on: net.commit()
+    after an optimiser step (see super_res_features)."""
     _, _, prefixes = net._hg_module(prefix)
     return _hg_apply(net, prefixes[0], prefixes, x, params)
 

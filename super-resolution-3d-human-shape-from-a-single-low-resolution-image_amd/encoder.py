@@ -129,6 +129,73 @@ class EncoderWeights:
                 wb, bb = get(L + "bl%d.weight" % s).astype(np.float64)[:, :, 0, 0], get(L + "bl%d.bias" % s).astype(np.float64)
                 self.conv[L + "next%d" % s] = native.ConvWeights((wb + wa @ wl).astype(np.float32)[:, :, None, None],
                                                                  (bb + wa @ bl_ + ba).astype(np.float32), device, reduced=self.reduced)
+        self._refresh = {}     # refresh(): per set of source tensors, what is built once (the addresses are constant)
+        self._merged = {}      # refresh(): next{s}'s ConvWeights -> the fp32 weight surs_conv1x1_merge writes
+
+    def refresh(self, tensors):
+        """The packed images rebuilt IN PLACE from `tensors`: state-dict key -> contiguous float32 device tensor of the parameter's
+        shape (SuRSNet.sr_parameters() / hg_parameters(), or any part of them; keys this object packs nothing from are ignored).  Per
+        call, on the current stream and without a synchronisation: one surs_conv1x1_merge per stack joint whose l / bl / al are all
+        given (into a kept fp32 next{s} weight and straight into next{s}'s bias), ONE surs_conv_repack over every convolution named
+        and those merged ones, and the biases and GroupNorm gamma / beta copied into the existing tensors.  No address changes:
+        the NativeNet struct and captured graphs stay valid.  --norm batch folds its constants on the host: NotImplementedError for
+        a norm tensor."""
+        key = tuple((k, t.data_ptr()) for k, t in tensors.items())
+        plan = self._refresh.get(key)
+        if plan is None:
+            if len(self._refresh) >= 8:
+                self._refresh.clear()
+            plan = self._refresh[key] = self._refresh_plan(tensors)
+        if any(cw._w3_wide is not None for cw in plan[4]):
+            # (wide_operands() packed a wide image after the plan was made: made again, once, with that image in the table)
+            plan = self._refresh[key] = self._refresh_plan(tensors)
+        table, merges, dst, src, wide = plan
+        for args in merges:
+            native.conv1x1_merge(*args)
+        if table is not None:
+            native.conv_repack(table)
+        if dst:
+            torch._foreach_copy_(dst, src)
+
+    def _refresh_plan(self, tensors):
+        L = "image_filter_lr."
+        entries, merges, dst, src, wide, convs, joints = [], [], [], [], [], [], []
+        t = {k: v.detach() for k, v in tensors.items()}
+        # everything is checked before the first ConvWeights is touched: a refused call leaves every convolution as it was
+        for k, v in t.items():
+            name, kind = k.rsplit(".", 1)
+            if name in self.conv and kind == "weight":
+                self.conv[name].check_master(v)
+                convs.append((self.conv[name], v))
+            elif name in self.conv and kind == "bias" and self.conv[name].b is not None:
+                dst.append(self.conv[name].b)
+                src.append(v.reshape(-1))
+            elif name in self.gn and kind in ("weight", "bias"):
+                dst.append(self.gn[name][kind == "bias"])
+                src.append(v.reshape(-1))
+            elif name in self.bn:
+                raise NotImplementedError("EncoderWeights.refresh: --norm batch folds %s into constants on the host; load_state_dict() "
+                                          "the new values instead" % name)
+        for s in range(self.opt.num_stack_lr - 1):
+            parts = [t.get(L + "%s%d.%s" % (n, s, kind)) for n in ("bl", "al", "l") for kind in ("weight", "bias")]
+            if any(p is None for p in parts):
+                if any(p is not None for p in parts):
+                    raise ValueError("EncoderWeights.refresh: stack joint %d needs bl, al and l (weight and bias) together" % s)
+                continue
+            joints.append((self.conv[L + "next%d" % s], parts))
+        for d, v in zip(dst, src):
+            if d.numel() != v.numel() or v.dtype != torch.float32 or v.device != d.device:
+                raise ValueError("EncoderWeights.refresh: a float32 tensor of %d values on %s is expected" % (d.numel(), d.device))
+        for cw, parts in joints:
+            w_out = self._merged.get(cw)    # (the merged fp32 weight, kept: a plan made again reads and writes the same tensor)
+            if w_out is None:
+                w_out = self._merged[cw] = torch.empty((cw.cout, cw.cin, 1, 1), dtype=torch.float32, device=self.device)
+            merges.append(parts + [w_out, cw.b])
+            convs.append((cw, w_out))
+        entries = [cw.repack_entry(v) for cw, v in convs]
+        # (the convolutions whose wide image does not exist yet: refresh() looks whether one has been packed since)
+        wide = [cw for cw, _ in convs if cw.parts == 2 and cw.k == 3 and cw.w3 is not None and cw._w3_wide is None]
+        return (native.RepackTable(entries, self.device) if entries else None), merges, dst, src, wide
 
 
 # ------------------------------------------------------------------ the networks sequenced inside the library (default)

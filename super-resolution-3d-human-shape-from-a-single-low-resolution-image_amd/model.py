@@ -89,6 +89,8 @@ class SuRSNet:
         self._sr_points = None        # query_sr's points and (calibs, transforms): what classifier_grads() differentiates
         self._sr_args = None
         self._grad_params = None      # native.MlpParams: the device copy of the fp32 classifier weights (dropped like the blob)
+        self._mlp_param_dict = None   # mlp_parameters()'s OrderedDict over _grad_params.tensors
+        self._stale = set()           # commit(): the keys of _sd whose current values are on the device (the masters'), not yet in _sd
         self._grad_ws = None
         self._sr_params = None        # native.SrParams + sr_parameters()'s OrderedDict: the plain fp32 super-resolution weights (dropped alike)
         self._sr_tapes = None         # what super_res_train() left for super_res_backward(): (h, w, [one tape per image])
@@ -111,11 +113,12 @@ class SuRSNet:
             device = torch.device(device)
             if device.type == "cuda" and device.index is None:
                 device = torch.device("cuda", torch.cuda.current_device())
+            self._write_back()   # (committed values live in the masters dropped below: into _sd first)
             self.device = device
             if self._enc is not None:
                 encoder.drop_graphs(self._enc)
             self._enc = self._blob = None
-            self._grad_params = self._grad_ws = None
+            self._grad_params = self._grad_ws = self._mlp_param_dict = None
             self._sr_params = self._sr_tapes = self._sr_ws = None
             self._hg_params = self._hg_ws = None
             self._hg_tapes = {}
@@ -133,12 +136,90 @@ class SuRSNet:
         return self
 
     def state_dict(self):
+        self._write_back()
         return OrderedDict((k, v.clone()) for k, v in self._sd.items())
 
     def parameters(self):
+        self._write_back()
         return iter(self._sd.values())
 
+    def _masters(self):
+        """name of each parameter set -> its device masters (state-dict key -> tensor), for the sets that exist."""
+        out = OrderedDict()
+        if self._grad_params is not None:
+            out["mlp"] = self._grad_params.tensors
+        if self._sr_params is not None:
+            out["sr"] = self._sr_params[0].tensors
+        if self._hg_params is not None:
+            out["hg"] = self._hg_params[0].tensors
+        return out
+
+    def _write_back(self):
+        """Downloads the keys commit() marked stale from their device masters into _sd (the spec's shapes: [out,in,1] classifier
+        weights).  Everything that reads _sd, or drops a master, calls this first; nothing to do when nothing was committed."""
+        if not self._stale:
+            return
+        shape = {k: tuple(sh) for k, sh, _ in self._spec}
+        for tensors in self._masters().values():
+            for k, t in tensors.items():
+                if k in self._stale:
+                    self._sd[k] = t.detach().to("cpu", torch.float32).reshape(shape[k]).contiguous()
+                    self._stale.discard(k)
+        assert not self._stale, "committed keys without a master: %s" % sorted(self._stale)[:3]
+
+    SETS = ("mlp", "sr", "hg")
+
+    def commit(self, which=None):
+        """Makes the forward run on the CURRENT values of the device masters - mlp_parameters(), sr_parameters(), hg_parameters(): what
+        an optimiser has just stepped - without leaving the device: the packed encoder images (EncoderWeights.refresh: surs_conv_repack,
+        surs_conv1x1_merge), the classifier blob in its own dtype (surs_mlp_repack, or surs_mlp_repack_generic for any other shape) are
+        rewritten in place on the current stream, with no synchronisation; no address changes, so the library's network struct and
+        captured graphs stay valid.  `which`: a subset of ("mlp", "sr", "hg"); default: every set whose master exists.  The keys of the
+        committed sets are then current on the device only: state_dict() / parameters() download them on demand (every other key -
+        bn4, the unused parts of image_filter_hr, the mean shifts, downsample.0's aliases - keeps its loaded value), to() writes them
+        back before it drops the masters, load_state_dict() replaces them.  Feature maps and predictions computed before the call
+        are those of the old weights.  "hg" under --norm batch: NotImplementedError (no backward; the constants are folded)."""
+        if which is None:
+            which = tuple(self._masters())
+        elif isinstance(which, str):
+            which = (which,)
+        which = tuple(which)
+        for w in which:
+            if w not in self.SETS:
+                raise ValueError("commit: unknown parameter set %r; the sets are %s" % (w, self.SETS))
+        if "hg" in which and weights.check_norm(getattr(self.opt, "norm", "group")) == "batch":
+            raise NotImplementedError("commit('hg'): --norm group only (a BatchNorm encoder has no backward and its constants are folded "
+                                      "on the host)")
+        self._device()
+        masters = self._masters()
+        for w in which:
+            if w not in masters:
+                raise RuntimeError("commit(%r): %s_parameters() has not been asked for: there is nothing to commit" % (w, w))
+        enc = OrderedDict()
+        for w in ("sr", "hg"):
+            if w in which:
+                enc.update(masters[w])
+        if enc and self._enc is not None:    # (not packed yet: the next use packs from the written-back values)
+            self._enc.refresh(enc)
+        if "mlp" in which and self._blob is not None:
+            if self._generic is not None:
+                native.mlp_repack_generic(self._grad_params, self._generic)
+            else:
+                native.mlp_repack(self._grad_params, self._blob, self._core_dtype)
+        for w in which:
+            self._stale.update(masters[w])
+        return self
+
+    def mlp_parameters(self):
+        """The cached OrderedDict of torch.nn.Parameter over the plain fp32 device copies of every mlp_lr.* / mlp_hr.* tensor
+        (state_dict() order; weights [out, in], biases [out]: the shapes native.MlpParams holds): what classifier_grads() reads and an
+        optimiser steps.  The FORWARD runs on the packed blob: commit() after a step."""
+        if self._mlp_param_dict is None:
+            self._mlp_param_dict = OrderedDict((k, torch.nn.Parameter(v)) for k, v in self._mlp_params().tensors.items())
+        return self._mlp_param_dict
+
     def load_state_dict(self, sd, strict=True):
+        self._write_back()   # (a key `sd` lacks keeps its CURRENT value: a committed one lives in a master dropped below)
         want = {k: tuple(s) for k, s, _ in self._spec}
         int_keys = {k for k, _, kind in self._spec if kind.endswith("bn_nbt") or kind.endswith("num_batches_tracked")}
         missing = [k for k in want if k not in sd]
@@ -158,10 +239,11 @@ class SuRSNet:
             else:
                 new[k] = self._sd[k]
         self._sd = new
+        self._stale = set()
         if self._enc is not None:
             encoder.drop_graphs(self._enc)
         self._enc = self._blob = None
-        self._grad_params = None
+        self._grad_params = self._mlp_param_dict = None
         self._sr_params = None
         self._hg_params = None
         return self
@@ -174,11 +256,13 @@ class SuRSNet:
 
     def _encoder_weights(self):
         if self._enc is None:
+            self._write_back()
             self._enc = encoder.EncoderWeights(self._sd, self.opt, self._device())
         return self._enc
 
     def _mlp_blob(self):
         if self._blob is None:
+            self._write_back()
             sd = {k: v.numpy() for k, v in self._sd.items() if k.startswith("mlp_")}
             shapes = native.mlp_shapes(sd, self.opt)
             if native.is_default_mlp(shapes):
@@ -248,6 +332,7 @@ class SuRSNet:
 
     def _sr_param_set(self):
         if self._sr_params is None:
+            self._write_back()
             p = native.SrParams(self._sd, self.opt.n_block, self._device())
             self._sr_params = (p, OrderedDict((k, torch.nn.Parameter(v)) for k, v in p.tensors.items()))
         return self._sr_params
@@ -255,8 +340,8 @@ class SuRSNet:
     def sr_parameters(self):
         """The cached OrderedDict of torch.nn.Parameter over the plain fp32 device copies of every super_resolution.* convolution and
         image_filter_hr.conv5 (state_dict() order, no sub_mean / add_mean): the tensors super_res_backward() reads, what an optimiser
-        steps and autograd.super_res_features hands gradients to.  The FORWARD runs on the packed weights of load_state_dict(): after
-        an optimiser step, load_state_dict() the updated values (which drops this cache, as it drops the classifiers')."""
+        steps and autograd.super_res_features hands gradients to.  The FORWARD runs on PACKED copies: after an optimiser step,
+        commit() repacks them on the device from these tensors (load_state_dict() drops this cache, as it drops the classifiers')."""
         return self._sr_param_set()[1]
 
     def super_res_train(self, images):
@@ -330,6 +415,7 @@ class SuRSNet:
 
     def _hg_param_set(self):
         if self._hg_params is None:
+            self._write_back()
             p = native.HgParams(self._sd, self.opt.num_stack_lr, self.opt.hg_depth, self._device())
             self._hg_params = (p, OrderedDict((k, torch.nn.Parameter(v)) for k, v in p.tensors.items()))
         return self._hg_params
@@ -338,7 +424,8 @@ class SuRSNet:
         """The cached OrderedDict of torch.nn.Parameter over the plain fp32 device copies of every image_filter_lr.* tensor the forward
         reads (state_dict() order: the ConvBlocks' conv1-3.weight and bn1-3.weight / .bias - not bn4 -, conv_last, bn_end, l, bl, al):
         what conv_block_backward() / hourglass_backward() read and autograd.conv_block / autograd.hourglass hand gradients to.  The
-        FORWARD runs on the packed weights of load_state_dict(), which drops this cache (as it drops sr_parameters()'s)."""
+        FORWARD runs on PACKED copies: commit() repacks them from these tensors after an optimiser step (load_state_dict() drops this
+        cache, as it drops sr_parameters()'s)."""
         return self._hg_param_set()[1]
 
     def _hg_module(self, which):
@@ -879,6 +966,7 @@ class SuRSNet:
 
     def _mlp_params(self):
         if self._grad_params is None:
+            self._write_back()
             sd = {k: v for k, v in self._sd.items() if k.startswith("mlp_")}
             shapes = native.mlp_shapes({k: v.numpy() for k, v in sd.items()}, self.opt)
             self._grad_params = native.MlpParams(sd, self._device(), shapes)

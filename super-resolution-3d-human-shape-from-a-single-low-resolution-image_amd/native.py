@@ -127,6 +127,7 @@ class ConvWeights:
     def __init__(self, w, b, device, reduced=False):
         w = np.ascontiguousarray(w, np.float32)
         self._host_w, self._w3_wide = w, None
+        self._master = self._table = None   # repack(): the device tensor the images were last packed from, and its one-item table
         self.reduced = bool(reduced)   # 3x3: one f16 product per MAC (surs_conv2d_nhwc_x1) - the encoder of --precision bf16 / fp16
         self.cout, self.cin, self.k = w.shape[0], w.shape[1], w.shape[2]
         n = lib().surs_conv_pack_weights(None, self.cout, self.cin, self.k, None)
@@ -155,10 +156,82 @@ class ConvWeights:
         if self._w3_wide is None:
             pack = lib().surs_conv_pack_weights_x3
             nb = pack(None, self.cout, self.cin, self.k, None)
+            if self._master is not None:
+                # (the values were committed on the device: repack(); the host copy is gone - pack from the device master.  Whoever
+                # holds a table over this convolution sees the new image through wide_image_built() and takes it in)
+                self._w3_wide = torch.empty(nb, dtype=torch.uint8, device=self.w.device)
+                conv_repack(RepackTable([(self._master, self.cout, self.cin, self.k, None, None, self._w3_wide)], self.w.device))
+                return self._w3_wide, 3
             buf = np.empty(nb, np.uint8)
             pack(self._host_w.ctypes.data_as(C.c_void_p), self.cout, self.cin, self.k, buf.ctypes.data_as(C.c_void_p))
             self._w3_wide = torch.from_numpy(buf).to(self.w.device)
         return self._w3_wide, 3
+
+    def check_master(self, w_dev):
+        """ValueError unless w_dev can be this convolution's device master; changes nothing."""
+        if tuple(w_dev.shape) != (self.cout, self.cin, self.k, self.k) or w_dev.dtype != torch.float32 or not w_dev.is_contiguous() \
+                or w_dev.device != self.w.device:
+            raise ValueError("repack: a contiguous float32 [%d,%d,%d,%d] tensor on %s is expected, not %s %s on %s"
+                             % (self.cout, self.cin, self.k, self.k, self.w.device, w_dev.dtype, tuple(w_dev.shape), w_dev.device))
+
+    def repack_entry(self, w_dev):
+        """This convolution's row of a RepackTable reading the plain [cout,cin,k,k] device tensor w_dev: the images the constructor
+        packed - w, and w3 as two f16 or (SURS_CONV_SPLIT=bf16x3) three bf16 parts, none with SURS_CONV_X3=0; `reduced` reads part 0
+        of the two-part image - plus the wide image where wide_operands() has already asked for it.  The object then packs a wide
+        image it is asked for later from w_dev (kept, not copied: its host copy of the old values is dropped)."""
+        self.check_master(w_dev)
+        self._master, self._host_w = w_dev.detach(), None
+        x2 = self.w3 if self.parts == 2 else None
+        x3 = self.w3 if self.parts == 3 else self._w3_wide
+        return (self._master, self.cout, self.cin, self.k, self.w, x2, x3)
+
+    def repack(self, w_dev, b_dev=None):
+        """Refreshes w, w3 (and the wide image, if it exists) and b IN PLACE from device tensors of new values: one surs_conv_repack
+        of a one-item table on the current stream.  data_ptr() of every image stays, so a NativeNet or a captured graph that holds
+        the raw pointers keeps reading valid - now updated - weights."""
+        entry = self.repack_entry(w_dev)
+        key = tuple(t.data_ptr() if t is not None else 0 for t in (entry[0],) + entry[4:])
+        if self._table is None or self._table[0] != key:
+            self._table = (key, RepackTable([entry], self.w.device))
+        conv_repack(self._table[1])
+        if b_dev is not None:
+            if self.b is None:
+                raise ValueError("repack: this convolution has no bias")
+            self.b.copy_(b_dev.detach().reshape(-1))
+
+
+class RepackTable:
+    """A device table of SursRepackItem (include/surs.h) over entries (w, cout, cin, ksize, packed, x2, x3) of device tensors (the
+    images nullable), with the tile prefix surs_conv_repack finds a workgroup's item by.  Built once: the addresses are constant."""
+
+    def __init__(self, entries, device):
+        items = (_lib.RepackItem * len(entries))()
+        end = 0
+        for it, (w, cout, cin, k, packed, x2, x3) in zip(items, entries):
+            tiles = lib().surs_conv_repack_tiles(cout, cin, k)
+            if tiles <= 0:
+                raise ValueError("surs_conv_repack: a %dx%d convolution of %d -> %d channels is not supported" % (k, k, cin, cout))
+            end += tiles
+            it.w, it.cout, it.cin, it.ksize, it.tile_end = w.data_ptr(), cout, cin, k, end
+            it.packed, it.x2, it.x3 = [t.data_ptr() if t is not None else None for t in (packed, x2, x3)]
+        self.n, self.tiles = len(entries), end
+        self.keep = [t for e in entries for t in e if torch.is_tensor(t)]
+        self.table = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(device)
+
+
+def conv_repack(table):
+    """surs_conv_repack of a RepackTable: every image it names, in one launch on the current stream."""
+    check(lib().surs_conv_repack(_ptr(table.table), table.n, _stream()))
+
+
+def conv1x1_merge(w_bl, b_bl, w_al, b_al, w_l, b_l, w_out, b_out):
+    """surs_conv1x1_merge: w_out [256,256] = w_bl + w_al [256,d] w_l [d,256], b_out = b_bl + w_al b_l + b_al, sums in double in index
+    order - EncoderWeights' next{s} - on the current stream."""
+    d = w_l.shape[0]
+    assert tuple(w_bl.shape[:2]) == (256, 256) and tuple(w_al.shape[:2]) == (256, d) and tuple(w_l.shape[:2]) == (d, 256)
+    assert w_out.numel() == 256 * 256 and b_out.numel() == 256
+    check(lib().surs_conv1x1_merge(*[_ptr(_f32c(t)) for t in (w_bl, b_bl, w_al, b_al, w_l, b_l)], d, _ptr(_f32c(w_out)),
+                                   _ptr(_f32c(b_out)), _stream()))
 
 
 def conv2d(x, cw, out=None, stride=1, in_scale=None, in_shift=None, act=0, slope=0.0, residual=None):
@@ -971,6 +1044,31 @@ class MlpParams:
         p = ("mlp_lr.", "mlp_hr.")[m]
         L = len(self.shapes[m][0]) - 1
         return (C.c_void_p * L)(*[t[p + "conv%d.%s" % (l, kind)].data_ptr() for l in range(L)])
+
+    def device_tables(self):
+        """(w_lr, b_lr, w_hr, b_hr): the four pointer tables of the parameters as device tensors (int64), built once - what the
+        device repack reads."""
+        if getattr(self, "_dev_tables", None) is None:
+            dev = next(iter(self.tensors.values())).device
+            self._dev_tables = [torch.tensor(list(self.table(m, kind)), dtype=torch.int64).to(dev)
+                                for m in (0, 1) for kind in ("weight", "bias")]
+        return self._dev_tables
+
+
+def mlp_repack(params, blob, dtype):
+    """surs_mlp_repack: every section of the released shape's blob (pack_mlp) rewritten in place from MlpParams `params`, in the
+    blob's 16-bit dtype (BF16 / F16), on the current stream."""
+    if not is_default_mlp(params.shapes):
+        raise ValueError("mlp_repack: the released shape only; a GenericMlp is refreshed by mlp_repack_generic")
+    check(lib().surs_mlp_repack(dtype, *[_ptr(t) for t in params.device_tables()], _ptr(blob), _stream()))
+
+
+def mlp_repack_generic(params, g):
+    """surs_mlp_repack_generic: the images and biases of GenericMlp `g`'s blob rewritten in place from MlpParams `params`."""
+    if tuple(params.shapes) != tuple(g.shapes):
+        raise ValueError("mlp_repack_generic: parameters of shapes %s against a blob packed for %s" % (params.shapes, g.shapes))
+    wl, bl, wh, bh = params.device_tables()
+    check(lib().surs_mlp_repack_generic(C.byref(g.lr), _ptr(wl), _ptr(bl), C.byref(g.hr), _ptr(wh), _ptr(bh), _ptr(g.blob), _stream()))
 
 
 def mlp_grad_workspace_bytes(shapes):
