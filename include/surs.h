@@ -342,7 +342,7 @@ int surs_encoder_super_res_backward(const SursEncoderNet *net, const SursSrParam
  * csrc/surs_encoder_net.cpp (the modules).  --norm group and net->parts == 2 only.  The rules of the super-resolution gradients
  * hold: fp32 with fp32 accumulation, no float atomics, two calls give the same bits wherever buffers, workspace and tape lie, NHWC
  * maps with a channel pitch (here: multiples of 4, 16-byte aligned pixels - every access is 16 bytes), parameters and their
- * gradients in the plain torch layout.  The stack's tail (conv_last, bn_end, l, bl, al) is not part of this.
+ * gradients in the plain torch layout.  The stack's tail (conv_last, bn_end, l, bl, al): "stack-tail gradients" below.
  *
  * surs_groupnorm_fold: the four vectors of a GroupNorm(32) site - mean[32], rstd[32] (per group) and scale[c] = rstd gamma,
  * shift[c] = beta - mean rstd gamma (per channel) - from the statistics the producer of the map left (stats, the in-kernel fold of
@@ -406,6 +406,76 @@ int surs_encoder_convblock_backward(const SursEncoderNet *net, const SursConvBlo
 int surs_encoder_hourglass_backward(const SursEncoderNet *net, int stack, const SursHgBlockParams *params, const void *tape, int h, int w,
                                     const float *g, float *dx, const SursHgBlockParams *grads, int accumulate, void *workspace,
                                     size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------ stack-tail gradients, and the whole low-resolution filter
+ * The tail of stack s of image_filter_lr (lib/model/HGFilters.py:196-206), D = --hg_dim, p over the h w pixels:
+ *   t = conv_last{s}(ll) [p][256],  a = relu(GroupNorm32(t; bn_end{s})) (never stored),  out = l{s}(a) [p][D],
+ *   next = previous + bl{s}(a) + al{s}(out) [p][256]   (not for the last stack; ONE launch on the merged next{s} = W_bl + W_al W_l)
+ * and its backward from G_out = d L / d out and G_next = d L / d next (either may be missing = zero; the last stack has no G_next):
+ *   dOut = G_out + G_next W_al,   dA = dOut W_l + G_next W_bl,
+ *   dW_al = G_next^T out, db_al = sum_p G_next;  dW_bl = G_next^T a, db_bl = sum_p G_next;  dW_l = dOut^T a, db_l = sum_p dOut,
+ *   (dt, dgamma, dbeta) = surs_groupnorm_relu_grad(dA, t, bn_end's folded vectors),
+ *   dW_cl = dt^T ll, db_cl = sum_p dt,  d ll = dt W_cl,  d previous = G_next (nothing is computed for it).
+ * The gradients are those of the UN-MERGED bl, al, l; the forward runs the merged launch, so its values are the packed weights'.
+ * csrc/surs_tail_grad.hip (the joint) and csrc/surs_encoder_net.cpp (the modules); the rules of the hourglass gradients hold:
+ * --norm group and net->parts == 2 only, fp32 on v_mfma_f32_32x32x2_f32 with fp32 accumulation, no float atomics, the same bits on
+ * every call wherever buffers, tape and workspace lie.
+ *
+ * surs_tail_joint_grad: dOut [p][D] and dA [p][256] in one launch (weights in the plain layout: w_al [256][D], w_l [D][256],
+ * w_bl [256][256]; D = 1 .. 512, any p; g_next: pitch a multiple of 4, 16-byte aligned pixels).  A workgroup owns 64 pixels for
+ * D <= 256 and 32 above; it stages its tile of g_next once for both products and keeps its tile of dOut in LDS.  Per element:
+ *   dOut[p][d] = g_out[p][d] + S,  S = 0, then + g_next[p][c] w_al[c][d] for c = 0 .. 255 in this order (each step one fused
+ *     multiply-add, one rounding); g_out is added last.  g_next == NULL: dOut = g_out (a copy); g_out == NULL: dOut = S.
+ *   dA[p][j]: ONE accumulator from 0: + dOut[p][d] w_l[d][j] for d = 0 .. D - 1 in this order, then + g_next[p][c] w_bl[c][j] for
+ *     c = 0 .. 255 in this order (g_next == NULL: nothing more).
+ * Both missing is SURS_E_INVALID.  The chain it replaces - surs_conv_grad_input (k = 1) three times, the second and third adding
+ * into their target - stays in the library and rounds dA's two sums separately. */
+int surs_tail_joint_grad(const float *g_out, int g_out_ld, const float *g_next, int g_next_ld, const float *w_al, const float *w_l,
+                         const float *w_bl, int p, int d, float *d_out, int d_out_ld, float *d_a, int d_a_ld, void *stream);
+
+/* The plain fp32 parameters (or their gradients) of one stack's tail; HOST struct of DEVICE pointers: conv_last{s} [256][256][1][1],
+ * l{s} [D][256][1][1], bl{s} [256][256][1][1], al{s} [256][D][1][1] with their biases, bn_end{s}.weight / .bias; bl and al are NULL
+ * for the last stack. */
+typedef struct SursHgTailParams { SursSrParam conv_last, l, bl, al; float *gamma, *beta; } SursHgTailParams;
+/* every image_filter_lr.* parameter: conv2, hg [num_stack * (3 hg_depth + 1)] in SursEncoderNet.hg's order, top_m and tail [num_stack] */
+typedef struct SursHgFilterParams {
+    SursHgBlockParams conv2;
+    const SursHgBlockParams *hg, *top_m;
+    const SursHgTailParams *tail;
+} SursHgFilterParams;
+/* bytes of the tape / of the backward's workspace of a tail (the largest over the stacks) and of the whole filter on an h x w map:
+ * functions of the net and the size alone, the sequencing run without launches; 0: refused (--norm batch, parts == 1, for the filter
+ * h or w not a multiple of 2^hg_depth). */
+size_t surs_encoder_tail_tape_bytes(const SursEncoderNet *net, int h, int w);
+size_t surs_encoder_tail_backward_workspace_bytes(const SursEncoderNet *net, int h, int w);
+size_t surs_encoder_filter_lr_tape_bytes(const SursEncoderNet *net, int h, int w);
+size_t surs_encoder_filter_lr_backward_workspace_bytes(const SursEncoderNet *net, int h, int w);
+/* The tail of stack `stack` on ll [h][w][256] (pitch ll_ld) and previous [h][w][256] (pitch previous_ld; NULL, with next, for the
+ * last stack) into out [h][w][D] and next [h][w][256] (dense): surs_encoder_filter_lr's launches - the pointwise convolution
+ * conv_last leaving bn_end's statistics, l, the merged next with the residual in its epilogue - plus one surs_groupnorm_fold, the
+ * same bits.  The tape (256-byte aligned) keeps ll, t, out and bn_end's four vectors. */
+int surs_encoder_tail_train(const SursEncoderNet *net, int stack, const float *ll, int ll_ld, const float *previous, int previous_ld, int h,
+                            int w, float *out, float *next, void *tape, size_t tape_bytes, void *stream);
+/* g_out [h][w][D], g_next [h][w][256] (dense, nullable, not both) -> d_ll [h][w][256] (dense, replaced) and the tail's parameter
+ * gradients; accumulate = 1 adds to what grads holds.  One stream, launches in a fixed order: a = relu(norm(t))
+ * (surs_scale_shift_act), surs_tail_joint_grad, surs_conv_grad_weight (k = 1) for al and bl (g_next missing: they are zeroed instead,
+ * accumulate = 0), for l, surs_groupnorm_relu_grad, surs_conv_grad_weight and surs_conv_grad_input for conv_last. */
+int surs_encoder_tail_backward(const SursEncoderNet *net, int stack, const SursHgTailParams *params, const void *tape, int h, int w,
+                               const float *g_out, const float *g_next, float *d_ll, const SursHgTailParams *grads, int accumulate,
+                               void *workspace, size_t workspace_bytes, void *stream);
+/* HGFilter.forward (low_res) with ONE tape: conv2, then per stack hourglass -> top_m -> tail, the launches of surs_encoder_filter_lr
+ * in its one-stream, separate-sum form (statistics handed from kernel to kernel as there) plus one surs_groupnorm_fold per norm
+ * site; outs[s] [h][w][D] (HOST array of num_stack device pointers, ALL required: training keeps every stack's output). */
+int surs_encoder_filter_lr_train(const SursEncoderNet *net, const float *feature_lr, int h, int w, int ld, float *const *outs, void *tape,
+                                 size_t tape_bytes, void *stream);
+/* g_outs[s] = d L / d outs[s] (HOST array; a NULL entry is zero, all NULL is SURS_E_INVALID) -> d_feature_lr [h][w][256] (dense) and
+ * every parameter's gradient.  From the last stack to the first: the tail (g_outs[s], d previous_{s+1}), top_m, the hourglass;
+ * previous_s has two consumers, the hourglass and the identity into next_s: d previous_s = (hourglass's input gradient) +
+ * d previous_{s+1}, ONE fp32 sum of two terms (surs_add3); conv2 last.  A stack no gradient reaches costs nothing: its gradients are
+ * zeroed (accumulate = 0). */
+int surs_encoder_filter_lr_backward(const SursEncoderNet *net, const SursHgFilterParams *params, const void *tape, int h, int w,
+                                    const float *const *g_outs, float *d_feature_lr, const SursHgFilterParams *grads, int accumulate,
+                                    void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------ point evaluator */
 

@@ -97,6 +97,18 @@ class HgBlockParams(C.Structure):
     _fields_ = [("weight", C.c_void_p * 3), ("gamma", C.c_void_p * 3), ("beta", C.c_void_p * 3)]
 
 
+class HgTailParams(C.Structure):
+    """SursHgTailParams of include/surs.h: one stack tail's plain fp32 conv_last / l / bl / al (weight, bias) and bn_end.weight / .bias
+    on the device; bl and al are NULL for the last stack."""
+    _fields_ = [("conv_last", SrParam), ("l", SrParam), ("bl", SrParam), ("al", SrParam), ("gamma", C.c_void_p), ("beta", C.c_void_p)]
+
+
+class HgFilterParams(C.Structure):
+    """SursHgFilterParams of include/surs.h: every image_filter_lr.* parameter (the arrays behind the pointers are the caller's)."""
+    _fields_ = [("conv2", HgBlockParams), ("hg", C.POINTER(HgBlockParams)), ("top_m", C.POINTER(HgBlockParams)),
+                ("tail", C.POINTER(HgTailParams))]
+
+
 class EncoderStreams(C.Structure):
     _fields_ = [("side", C.c_void_p * 4)]
 
@@ -192,6 +204,17 @@ _SIGS = {
                                                   _vp, C.POINTER(HgBlockParams), _i, _vp, _sz, _vp]),
     "surs_encoder_hourglass_backward": (C.c_int, [C.POINTER(EncoderNet), _i, C.POINTER(HgBlockParams), _vp, _i, _i, _vp, _vp,
                                                   C.POINTER(HgBlockParams), _i, _vp, _sz, _vp]),
+    "surs_tail_joint_grad": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp]),
+    "surs_encoder_tail_tape_bytes": (_sz, [C.POINTER(EncoderNet), _i, _i]),
+    "surs_encoder_tail_backward_workspace_bytes": (_sz, [C.POINTER(EncoderNet), _i, _i]),
+    "surs_encoder_filter_lr_tape_bytes": (_sz, [C.POINTER(EncoderNet), _i, _i]),
+    "surs_encoder_filter_lr_backward_workspace_bytes": (_sz, [C.POINTER(EncoderNet), _i, _i]),
+    "surs_encoder_tail_train": (C.c_int, [C.POINTER(EncoderNet), _i, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "surs_encoder_tail_backward": (C.c_int, [C.POINTER(EncoderNet), _i, C.POINTER(HgTailParams), _vp, _i, _i, _vp, _vp, _vp,
+                                             C.POINTER(HgTailParams), _i, _vp, _sz, _vp]),
+    "surs_encoder_filter_lr_train": (C.c_int, [C.POINTER(EncoderNet), _vp, _i, _i, _i, C.POINTER(_vp), _vp, _sz, _vp]),
+    "surs_encoder_filter_lr_backward": (C.c_int, [C.POINTER(EncoderNet), C.POINTER(HgFilterParams), _vp, _i, _i, C.POINTER(_vp), _vp,
+                                                  C.POINTER(HgFilterParams), _i, _vp, _sz, _vp]),
     "surs_mlp_pack": (_sz, [_vp, _vp, _vp, _vp, _i, _vp]),
     "surs_mlp_pack_generic": (_sz, [_shp, _vp, _vp, _shp, _vp, _vp, _vp]),
     "surs_mlp_generic_info": (C.c_int, [_shp, _shp, C.POINTER(C.c_int), C.POINTER(C.c_int), _vp]),

@@ -134,7 +134,85 @@ def conv_block(net, prefix, x, params=None):
 
 def hourglass(net, stack, x, params=None):
     """The HourGlass module image_filter_lr.m{stack} on x [B,256,h,w] (h, w multiples of 2^hg_depth), with a grad_fn: its backward is
-    net.hourglass_backward() and hands x and every parameter of the module its gradient.  With conv_block and four 1 x 1 layers in
-    plain torch on net.hg_parameters() this composes a trainable filter_lr ("Hourglass gradients")."""
+    net.hourglass_backward() and hands x and every parameter of the module its gradient.  With conv_block and stack_tail this
+    composes a trainable filter_lr; filter_lr below is that composition as one call ("Hourglass gradients")."""
     _, _, prefixes = net._hg_module(int(stack))
     return _hg_apply(net, int(stack), prefixes, x, params)
+
+
+class _StackTail(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, net, stack, keys, ll, previous, *params):
+        out, nxt = net.stack_tail_train(stack, ll, previous)
+        ctx.net, ctx.stack, ctx.keys, ctx.tapes = net, stack, keys, net._hg_tapes[("tail", stack)]
+        ctx.set_materialize_grads(False)
+        if nxt is None:
+            return out.clone()
+        return out.clone(), nxt.clone()
+
+    @staticmethod
+    def backward(ctx, g_out, g_next=None):
+        net, key = ctx.net, ("tail", ctx.stack)
+        kept = net._hg_tapes.get(key)
+        net._hg_tapes[key] = ctx.tapes   # the tapes of THIS forward, whatever ran on the net since
+        try:
+            d_ll, d_prev, grads = net.stack_tail_backward(ctx.stack, g_out, g_next)
+        finally:
+            if kept is None:
+                del net._hg_tapes[key]
+            else:
+                net._hg_tapes[key] = kept
+        return (None, None, None, d_ll, d_prev) + tuple(grads[k] for k in ctx.keys)
+
+
+def _hg_keys(net, keys, params):
+    if params is None:
+        params = net.hg_parameters()
+    missing = [k for k in keys if k not in params]
+    if missing:
+        raise ValueError("params lacks %s" % missing[:3])
+    return params
+
+
+def stack_tail(net, stack, ll, previous=None, params=None):
+    """The tail of stack `stack` of image_filter_lr on ll [B,256,h,w] (and previous, for every stack but the last), with a grad_fn:
+    returns out, or (out, next) for a stack that is not the last; its backward is net.stack_tail_backward() and hands ll, previous
+    and the tail's entries of `params` - default net.hg_parameters() - their gradients.  The VALUES are those of the PACKED weights,
+    the merged next{s} included: net.commit() after an optimiser step."""
+    from . import native
+    stack = int(stack)
+    keys = native.hg_tail_keys(stack, net.opt.num_stack_lr)
+    params = _hg_keys(net, keys, params)
+    return _StackTail.apply(net, stack, keys, ll, previous, *[params[k] for k in keys])
+
+
+class _FilterLr(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, net, keys, x, *params):
+        outs = net.filter_lr_train(x)
+        ctx.net, ctx.keys, ctx.tapes = net, keys, net._hg_tapes["filter_lr"]
+        ctx.set_materialize_grads(False)
+        return tuple(o.clone() for o in outs)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        net = ctx.net
+        kept = net._hg_tapes.get("filter_lr")
+        net._hg_tapes["filter_lr"] = ctx.tapes
+        try:
+            dx, grads = net.filter_lr_backward(list(gs))
+        finally:
+            if kept is None:
+                del net._hg_tapes["filter_lr"]
+            else:
+                net._hg_tapes["filter_lr"] = kept
+        return (None, None, dx) + tuple(grads[k] for k in ctx.keys)
+
+
+def filter_lr(net, feature_lr, params=None):
+    """HGFilter.forward of SuRSNet `net` on feature_lr [B,256,h,w] with a grad_fn: the list of every stack's output; its backward is
+    net.filter_lr_backward() - ONE call for the whole filter - and hands feature_lr and every entry of `params` (default
+    net.hg_parameters(), all of its keys) their gradients.  net.commit() after an optimiser step, as for the modules."""
+    keys = list(net.hg_parameters())
+    params = _hg_keys(net, keys, params)
+    return list(_FilterLr.apply(net, keys, feature_lr, *[params[k] for k in keys]))

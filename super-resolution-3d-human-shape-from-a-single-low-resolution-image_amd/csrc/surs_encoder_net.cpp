@@ -14,14 +14,17 @@
 // blocks (one stream: reuse is ordered); filter_lr alternates between two arenas per stack (stack s + 2 starts after every
 // kernel of stack s has been joined).  surs_encoder_workspace_bytes() runs the same sequencing with a counting allocator.
 //
-// ONE sequencing per network.  super_res() (over a plan of buffers), conv_block() and hourglass() (with an optional tape) are the
-// only launch lists of their networks: the inference calls, the train forwards of the gradient entry points further down and - run
+// ONE sequencing per network.  super_res() (over a plan of buffers), conv_block(), hourglass() and stack_tail() (with an optional
+// tape) are the only launch lists of their networks: the inference calls, the train forwards of the gradient entry points further down and - run
 // without launches - every size query and the backwards' address computation all go through them.  The layout of a tape is the
 // order of the allocator's takes of that sequencing; the backwards walk the same plan / the same level table in reverse.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstring>
+#include <initializer_list>
+#include <memory>
+#include <vector>
 
 #include "surs_common.h"
 
@@ -547,6 +550,40 @@ Map hourglass(Run &r, const SursConvBlock *blocks, int depth, const Map &x, cons
     return f.run(depth, x);
 }
 
+// What a stack's tail leaves for its backward (surs_encoder_tail_backward): its input ll, conv_last's raw output t, the stack's output
+// out = l(relu(bn_end(t))) and bn_end's four coefficient vectors.
+struct TailTape {
+    Map ll, t, out;
+    NormTape nt;
+};
+
+// The tail of GroupNorm stack s: conv_last leaves bn_end's statistics; l (where the stack's output is wanted: out.p) and the merged
+// next (not for the last stack; returned, with the statistics for the next hourglass) fold them.  The ONE launch list of the tail:
+// filter_lr() below, surs_encoder_tail_train and surs_encoder_filter_lr_train (tape: plus one surs_groupnorm_fold for bn_end).
+Map stack_tail(Run &r, int s, const Map &ll, const Map &previous, Map out, bool last, TailTape *tape = nullptr) {
+    const SursEncoderNet &n = *r.net;
+    Map t = r.map(ll.h, ll.w, n.conv_last[s].cout);
+    conv_gn(r, ll, n.conv_last[s], t, nullptr, true);
+    if (out.p) conv_gn(r, t, n.l[s], out, &n.bn_end[s], false);
+    Map nx;
+    if (!last) {
+        nx = r.map(t.h, t.w, n.next[s].cout);
+        conv_gn(r, t, n.next[s], nx, &n.bn_end[s], true, &previous);
+    }
+    if (tape) {
+        tape->ll = ll; tape->t = t; tape->out = out;
+        NormTape &v = tape->nt;
+        v.mean = (float *)r.a->take(sizeof(float) * 32);
+        v.rstd = (float *)r.a->take(sizeof(float) * 32);
+        v.scale = (float *)r.a->take(sizeof(float) * t.c);
+        v.shift = (float *)r.a->take(sizeof(float) * t.c);
+        if (!r.dry && !r.rc)
+            r.fail(surs_groupnorm_fold(&t.st, nullptr, t.h * t.w, t.c, t.ld, 1e-5f, n.bn_end[s].gamma, n.bn_end[s].beta, v.mean, v.rstd, v.scale,
+                                       v.shift, nullptr, r.st));
+    }
+    return nx;
+}
+
 // HGFilter.forward, low_res (lib/model/HGFilters.py:183-206).  outs[s]: where stack s's output goes (NULL: not wanted; the last
 // stack's is always wanted).  The tail of a stack is two launches (three where the stack's output is wanted): conv_last leaves
 // bn_end's statistics, the pointwise convolutions behind it fold them; previous + bl(t') + al(l(t')) is ONE pointwise convolution
@@ -562,9 +599,9 @@ void filter_lr(Run &r, const Map &feature_lr, float *const *outs, const SursEnco
         Map hg = hourglass(r, n.hg + (size_t)s * per_stack, n.hg_depth, previous, ss);
         Map ll = conv_block(r, n.top_m[s], hg, false);
         const bool last = s == n.num_stack - 1;
-        Map t = r.map(ll.h, ll.w, n.conv_last[s].cout);
         if (r.bn()) {   // the same pointwise launches with bn_end's constants, no statistics
             const SursBatchNorm &be = n.bn_end_bn[s];
+            Map t = r.map(ll.h, ll.w, n.conv_last[s].cout);
             conv(r, ll, n.conv_last[s], t, 1, 0, 0.0f, nullptr);
             if (outs[s]) {
                 Map o = input_map(outs[s], t.h, t.w, n.l[s].cout, n.l[s].cout);
@@ -577,16 +614,8 @@ void filter_lr(Run &r, const Map &feature_lr, float *const *outs, const SursEnco
             }
             continue;
         }
-        conv_gn(r, ll, n.conv_last[s], t, nullptr, true);
-        if (outs[s]) {
-            Map o = input_map(outs[s], t.h, t.w, n.l[s].cout, n.l[s].cout);
-            conv_gn(r, t, n.l[s], o, &n.bn_end[s], false);
-        }
-        if (!last) {
-            Map nx = r.map(t.h, t.w, n.next[s].cout);
-            conv_gn(r, t, n.next[s], nx, &n.bn_end[s], true, &previous);
-            previous = nx;
-        }
+        const Map nx = stack_tail(r, s, ll, previous, outs[s] ? input_map(outs[s], ll.h, ll.w, n.l[s].cout, n.l[s].cout) : Map(), last);
+        if (!last) previous = nx;
     }
 }
 
@@ -1225,4 +1254,364 @@ extern "C" int surs_encoder_hourglass_backward(const SursEncoderNet *net, int st
     SURS_REQUIRE(stack >= 0 && stack < net->num_stack, "hourglass_backward: stack %d of %d", stack, net->num_stack);
     return hg_backward(net, stack_blocks(net, stack), net->hg_depth, params, tape, h, w, g, dx, grads, accumulate, workspace, workspace_bytes,
                        stream, "hourglass_backward");
+}
+
+// ---------------------------------------------------------------- stack-tail gradients, and the whole low-resolution filter (include/surs.h)
+// surs_encoder_tail_train runs stack_tail() above with a tape; surs_encoder_filter_lr_train runs conv_block(), hourglass() and
+// stack_tail() in filter_lr()'s order on ONE tape (one stream, the separate-sum forms, every map kept).  As for the hourglass, the
+// layout of a tape is the order of the arena takes of that sequencing, and the backwards find the addresses by running it dry.
+namespace {
+
+bool is_pointwise(const SursConv &c, int cin, int cout) { return c.cin == cin && c.cout == cout && c.ksize == 1 && c.w_split; }
+
+int check_tail(const SursEncoderNet *net, int s, const char *what) {
+    SURS_REQUIRE(net->conv_last && net->l && net->bn_end, "%s: null argument", what);
+    SURS_REQUIRE(s >= 0 && s < net->num_stack, "%s: stack %d of %d", what, s, net->num_stack);
+    const int d = net->l[s].cout;
+    SURS_REQUIRE(d >= 16 && d <= 512 && d % 16 == 0, "hg_dim %d: the supported values are the multiples of 16 from 16 to 512", d);
+    SURS_REQUIRE(is_pointwise(net->conv_last[s], 256, 256) && is_pointwise(net->l[s], 256, d) && net->bn_end[s].gamma && net->bn_end[s].beta &&
+                 (s == net->num_stack - 1 || (net->next && is_pointwise(net->next[s], 256, 256))),
+                 "%s: the tail of stack %d is not image_filter_lr's (1 x 1, 256 -> 256 -> hg_dim, GroupNorm)", what, s);
+    return 0;
+}
+
+bool tail_param_filled(const SursHgTailParams &p, bool last) {
+    return p.conv_last.weight && p.conv_last.bias && p.l.weight && p.l.bias && p.gamma && p.beta &&
+           (last || (p.bl.weight && p.bl.bias && p.al.weight && p.al.bias));
+}
+
+// the tape of a tail: the input's copy, the stack's output, then the sequencing's maps
+struct TailLayout {
+    Map ll, out, next;
+    TailTape T;
+};
+
+void tail_layout(Run &r, int s, int h, int w, TailLayout &L, const float *ll = nullptr, int ld = 0, const float *previous = nullptr,
+                 int previous_ld = 0) {
+    const SursEncoderNet &n = *r.net;
+    L.ll = r.map(h, w, 256);
+    if (!r.dry && hipMemcpy2DAsync(L.ll.p, sizeof(float) * 256, ll, sizeof(float) * ld, sizeof(float) * 256, (size_t)h * w,
+                                   hipMemcpyDeviceToDevice, r.st) != hipSuccess)
+        r.fail(fail(SURS_E_HIP, "stack-tail gradients: hipMemcpy2DAsync failed"));
+    L.out = r.map(h, w, n.l[s].cout);
+    L.next = stack_tail(r, s, L.ll, input_map(previous, h, w, 256, previous_ld), L.out, s == n.num_stack - 1, &L.T);
+}
+
+size_t tail_tape_need(const SursEncoderNet *net, int s, int h, int w) {
+    Dry d(net);
+    TailLayout L;
+    tail_layout(d.r, s, h, w, L);
+    return align_up(d.a.peak, 256);
+}
+
+struct TailBack {
+    Run &r;
+    int acc;
+    Map A, DA, DO, DT;         // relu(bn_end(t)), d / d that, d / d out (the joint's), d / d t
+    void *wws = nullptr;       // the weight gradients' slabs
+    size_t wws_bytes = 0;
+    void *gws = nullptr;       // the GroupNorm gradient's parts
+    size_t gws_bytes = 0;
+
+    void alloc(int h, int w, int d) {
+        A = r.map(h, w, 256); DA = r.map(h, w, 256); DO = r.map(h, w, d); DT = r.map(h, w, 256);
+        const int m = d > 256 ? d : 256;
+        wws_bytes = surs_conv_grad_weight_workspace_bytes(h, w, m, m, 1);
+        wws = r.a->take(wws_bytes);
+        gws_bytes = surs_groupnorm_relu_grad_workspace_bytes(h * w, 256);
+        gws = r.a->take(gws_bytes);
+    }
+    void wgrad(const Map &g, const Map &x, const SursSrParam &d) {
+        if (!r.rc)
+            r.fail(surs_conv_grad_weight(g.p, g.h, g.w, g.c, g.ld, nullptr, 0, 1.0f, x.p, x.h, x.w, x.c, x.ld, 1, 1, d.weight, d.bias, acc, wws,
+                                         wws_bytes, r.st));
+    }
+    void zero(float *p, size_t count) {
+        if (!r.rc && hipMemsetAsync(p, 0, sizeof(float) * count, r.st) != hipSuccess)
+            r.fail(fail(SURS_E_HIP, "stack-tail gradients: hipMemsetAsync failed"));
+    }
+    // g_out = d L / d out, g_next = d L / d next (a map without memory counts as zero; not both) -> d_ll (dense, replaced) and the
+    // parameters' gradients, in the order of include/surs.h
+    void run(const TailTape &t, bool last, const SursHgTailParams &P, const SursHgTailParams &D, const Map &g_out, const Map &g_next,
+             const Map &d_ll) {
+        if (r.dry || r.rc) return;
+        const int h = t.t.h, w = t.t.w, hw = h * w, d = t.out.c;
+        const Map a = input_map(A.p, h, w, 256, 256), da = input_map(DA.p, h, w, 256, 256), dt = input_map(DT.p, h, w, 256, 256);
+        const Map dout = input_map(DO.p, h, w, d, d);
+        r.fail(surs_scale_shift_act(t.t.p, hw, 256, t.t.ld, t.nt.scale, t.nt.shift, 1, a.p, a.ld, r.st));
+        if (!r.rc)
+            r.fail(surs_tail_joint_grad(g_out.p, g_out.ld, g_next.p, g_next.ld, P.al.weight, P.l.weight, P.bl.weight, hw, d, dout.p, dout.ld,
+                                        da.p, da.ld, r.st));
+        if (g_next.p) {
+            wgrad(g_next, t.out, D.al);
+            wgrad(g_next, a, D.bl);
+        } else if (!last && !acc) {   // next reaches nothing: bl and al get zero gradients
+            zero(D.al.weight, (size_t)256 * d); zero(D.al.bias, 256); zero(D.bl.weight, 256 * 256); zero(D.bl.bias, 256);
+        }
+        wgrad(dout, a, D.l);
+        if (!r.rc)
+            r.fail(surs_groupnorm_relu_grad(da.p, da.ld, t.t.p, t.t.ld, hw, 256, t.nt.mean, t.nt.rstd, t.nt.scale, t.nt.shift, P.gamma, dt.p, dt.ld,
+                                            0, D.gamma, D.beta, acc, gws, gws_bytes, r.st));
+        wgrad(dt, t.ll, D.conv_last);
+        if (!r.rc)
+            r.fail(surs_conv_grad_input(dt.p, h, w, 256, dt.ld, nullptr, 0, 1.0f, P.conv_last.weight, 256, 1, 1, d_ll.p, h, w, d_ll.ld, 0, r.st));
+    }
+};
+
+size_t tail_backward_need(const SursEncoderNet *net, int s, int h, int w) {
+    Dry d(net);
+    TailBack k{d.r, 0};
+    k.alloc(h, w, net->l[s].cout);
+    return align_up(d.a.peak, 256) + 256;
+}
+
+// ---- the whole filter: conv2, then per stack hourglass -> top_m -> tail, on one tape
+constexpr int MAX_STACKS = 16;
+struct FilterLayout {
+    Map x, outs[MAX_STACKS];
+    BlockTape conv2, top_m[MAX_STACKS], hg[MAX_STACKS][HG_MAX_BLOCKS];
+    TailTape tail[MAX_STACKS];
+};
+
+void filter_layout(Run &r, int h, int w, FilterLayout &L, const float *x = nullptr, int ld = 0) {
+    const SursEncoderNet &n = *r.net;
+    L.x = r.map(h, w, 256);
+    if (!r.dry && hipMemcpy2DAsync(L.x.p, sizeof(float) * 256, x, sizeof(float) * ld, sizeof(float) * 256, (size_t)h * w,
+                                   hipMemcpyDeviceToDevice, r.st) != hipSuccess)
+        r.fail(fail(SURS_E_HIP, "filter_lr gradients: hipMemcpy2DAsync failed"));
+    Map previous = conv_block(r, n.conv2, L.x, true, &L.conv2);
+    for (int s = 0; s < n.num_stack; ++s) {
+        const bool last = s == n.num_stack - 1;
+        Map hg = hourglass(r, n.hg + (size_t)s * per_stack_blocks(&n), n.hg_depth, previous, nullptr, L.hg[s]);
+        Map ll = conv_block(r, n.top_m[s], hg, false, &L.top_m[s]);
+        L.outs[s] = r.map(h, w, n.l[s].cout);
+        const Map nx = stack_tail(r, s, ll, previous, L.outs[s], last, &L.tail[s]);
+        if (!last) previous = nx;
+    }
+}
+
+int check_filter_train(const SursEncoderNet *net, int h, int w, const char *what) {
+    if (int rc = check_hg_train(net, h, w, net ? net->hg_depth : 0)) return rc;
+    SURS_REQUIRE(net->hg && net->top_m, "%s: null argument", what);
+    for (int s = 0; s < net->num_stack; ++s) {
+        if (int rc = check_tail(net, s, what)) return rc;
+        SURS_REQUIRE(is_hg_block(net->top_m[s]), "%s: a block is not image_filter_lr's", what);
+        for (int i = 0; i < per_stack_blocks(net); ++i)
+            SURS_REQUIRE(is_hg_block(net->hg[(size_t)s * per_stack_blocks(net) + i]), "%s: a block is not image_filter_lr's", what);
+    }
+    SURS_REQUIRE(is_hg_block(net->conv2), "%s: a block is not image_filter_lr's", what);
+    return 0;
+}
+
+size_t filter_tape_need(const SursEncoderNet *net, int h, int w) {
+    Dry d(net);
+    std::unique_ptr<FilterLayout> L(new FilterLayout);
+    filter_layout(d.r, h, w, *L);
+    return align_up(d.a.peak, 256);
+}
+
+struct FilterBack {
+    Run &r;
+    int acc;
+    HgBack k;
+    TailBack tb;
+    Map dll, dhg, dprev[2];
+
+    FilterBack(Run &run, int accumulate) : r(run), acc(accumulate), k{run, accumulate}, tb{run, accumulate} {}
+    void alloc(int h, int w) {
+        int d = 0;
+        for (int s = 0; s < r.net->num_stack; ++s) d = r.net->l[s].cout > d ? r.net->l[s].cout : d;
+        k.alloc(h, w);
+        tb.alloc(h, w, d);
+        dll = r.map(h, w, 256); dhg = r.map(h, w, 256); dprev[0] = r.map(h, w, 256); dprev[1] = r.map(h, w, 256);
+    }
+    void zero_block(const SursHgBlockParams &D) {
+        const size_t wn[3] = {128 * 256 * 9, 64 * 128 * 9, 64 * 64 * 9}, cn[3] = {256, 128, 64};
+        for (int j = 0; j < 3; ++j) {
+            tb.zero(D.weight[j], wn[j]); tb.zero(D.gamma[j], cn[j]); tb.zero(D.beta[j], cn[j]);
+        }
+    }
+    // g_outs[s] = d L / d outs[s] (NULL: zero) -> d_x = d L / d feature_lr and every parameter's gradient.  Stack s, from the last:
+    // tail (g_outs[s], d previous_{s+1}), top_m, hourglass; d previous_s = the hourglass's input gradient + d next_s (one fp32 sum)
+    void run(const FilterLayout &L, const SursHgFilterParams &P, const SursHgFilterParams &D, const float *const *g_outs, const Map &d_x) {
+        const SursEncoderNet &n = *r.net;
+        const int S = n.num_stack, per = per_stack_blocks(&n), h = d_x.h, w = d_x.w;
+        Map gnext;   // d L / d previous_{s + 1}; without memory: zero
+        for (int s = S - 1; s >= 0; --s) {
+            const bool last = s == S - 1;
+            const int d = n.l[s].cout;
+            const Map g_out = g_outs[s] ? input_map(g_outs[s], h, w, d, d) : Map();
+            if (!g_out.p && !gnext.p) {   // nothing reaches this stack: zero gradients, and none for previous_s
+                if (!acc && !r.dry) {
+                    const SursHgTailParams &T = D.tail[s];
+                    tb.zero(T.conv_last.weight, 256 * 256); tb.zero(T.conv_last.bias, 256); tb.zero(T.gamma, 256); tb.zero(T.beta, 256);
+                    tb.zero(T.l.weight, (size_t)d * 256); tb.zero(T.l.bias, d);
+                    if (!last) {
+                        tb.zero(T.al.weight, (size_t)256 * d); tb.zero(T.al.bias, 256); tb.zero(T.bl.weight, 256 * 256); tb.zero(T.bl.bias, 256);
+                    }
+                    zero_block(D.top_m[s]);
+                    for (int i = 0; i < per; ++i) zero_block(D.hg[(size_t)s * per + i]);
+                }
+                continue;
+            }
+            const Map &dp = dprev[s & 1];
+            tb.run(L.tail[s], last, P.tail[s], D.tail[s], g_out, gnext, dll);
+            k.block(L.top_m[s], P.top_m[s], D.top_m[s], dll, dhg);
+            const size_t mark = r.a->off;   // (the levels' maps are taken per call)
+            hourglass_backward(k, L.hg[s], n.hg_depth, P.hg + (size_t)s * per, D.hg + (size_t)s * per, dhg, dp);
+            r.a->off = mark;
+            if (gnext.p && !r.dry && !r.rc) r.fail(surs_add3(dp.p, dp.ld, gnext.p, gnext.ld, nullptr, 0, h * w, 256, dp.p, dp.ld, r.st));
+            gnext = dp;
+        }
+        k.block(L.conv2, P.conv2, D.conv2, gnext, d_x);
+    }
+};
+
+size_t filter_backward_need(const SursEncoderNet *net, int h, int w) {
+    Dry d(net);
+    FilterBack k(d.r, 0);
+    std::unique_ptr<FilterLayout> L(new FilterLayout);
+    const std::vector<SursHgBlockParams> blocks((size_t)net->num_stack * per_stack_blocks(net));
+    const std::vector<SursHgTailParams> tails(net->num_stack);
+    const SursHgFilterParams none = {SursHgBlockParams{}, blocks.data(), blocks.data(), tails.data()};
+    float *g[MAX_STACKS];
+    for (int s = 0; s < MAX_STACKS; ++s) g[s] = NOWHERE;
+    k.alloc(h, w);
+    k.run(*L, none, none, g, input_map(NOWHERE, h, w, 256, 256));
+    return align_up(d.a.peak, 256) + 256;
+}
+
+}  // namespace
+
+extern "C" size_t surs_encoder_tail_tape_bytes(const SursEncoderNet *net, int h, int w) {
+    if (!net || check_hg_train(net, h, w, 0)) return 0;
+    size_t need = 0;
+    for (int s = 0; s < net->num_stack; ++s) {   // (the last stack's is the smaller one)
+        if (check_tail(net, s, "tail_tape_bytes")) return 0;
+        const size_t v = tail_tape_need(net, s, h, w);
+        need = v > need ? v : need;
+    }
+    return need;
+}
+
+extern "C" size_t surs_encoder_tail_backward_workspace_bytes(const SursEncoderNet *net, int h, int w) {
+    if (!net || check_hg_train(net, h, w, 0)) return 0;
+    size_t need = 0;
+    for (int s = 0; s < net->num_stack; ++s) {
+        if (check_tail(net, s, "tail_backward_workspace_bytes")) return 0;
+        const size_t v = tail_backward_need(net, s, h, w);
+        need = v > need ? v : need;
+    }
+    return need;
+}
+
+extern "C" int surs_encoder_tail_train(const SursEncoderNet *net, int stack, const float *ll, int ll_ld, const float *previous, int previous_ld,
+                                       int h, int w, float *out, float *next, void *tape, size_t tape_bytes, void *stream) {
+    if (int rc = check_hg_train(net, h, w, 0)) return rc;
+    if (int rc = check_tail(net, stack, "tail_train")) return rc;
+    const bool last = stack == net->num_stack - 1;
+    SURS_REQUIRE(ll && out && tape, "tail_train: null argument");
+    SURS_REQUIRE(last ? (!previous && !next) : (previous && next), "tail_train: previous and next go with every stack but the last (stack %d of %d)",
+                 stack, net->num_stack);
+    SURS_REQUIRE(ll_ld >= 256 && (last || (previous_ld >= 256 && previous_ld % 4 == 0 && aligned16(previous))),
+                 "tail_train: maps of 256 channels, 16-byte aligned pixels");
+    SURS_REQUIRE(((size_t)tape & 255) == 0, "tail_train: the tape must be 256-byte aligned");
+    const size_t need = tail_tape_need(net, stack, h, w);
+    SURS_REQUIRE(need <= tape_bytes, "tail_train: tape too small: %zu bytes needed", need);
+    Arena a = tape_arena(tape, tape_bytes);
+    Run r{net, &a, as_stream(stream), net->parts, false};
+    TailLayout L;
+    tail_layout(r, stack, h, w, L, ll, ll_ld, previous, previous_ld);
+    if (r.rc) return r.rc;
+    SURS_HIP_CHECK(hipMemcpyAsync(out, L.out.p, sizeof(float) * h * w * L.out.c, hipMemcpyDeviceToDevice, r.st));
+    if (!last) SURS_HIP_CHECK(hipMemcpyAsync(next, L.next.p, sizeof(float) * h * w * 256, hipMemcpyDeviceToDevice, r.st));
+    return 0;
+}
+
+extern "C" int surs_encoder_tail_backward(const SursEncoderNet *net, int stack, const SursHgTailParams *params, const void *tape, int h, int w,
+                                          const float *g_out, const float *g_next, float *d_ll, const SursHgTailParams *grads, int accumulate,
+                                          void *workspace, size_t workspace_bytes, void *stream) {
+    if (int rc = check_hg_train(net, h, w, 0)) return rc;
+    if (int rc = check_tail(net, stack, "tail_backward")) return rc;
+    const bool last = stack == net->num_stack - 1;
+    SURS_REQUIRE(params && grads && tape && d_ll && workspace, "tail_backward: null argument");
+    SURS_REQUIRE(g_out || g_next, "tail_backward: both gradients are missing");
+    SURS_REQUIRE(!(last && g_next), "tail_backward: the last stack has no next");
+    SURS_REQUIRE(tail_param_filled(*params, last) && tail_param_filled(*grads, last), "tail_backward: a null pointer in params / grads");
+    SURS_REQUIRE(((size_t)tape & 255) == 0 && aligned16(g_out) && aligned16(g_next) && aligned16(d_ll),
+                 "tail_backward: the tape must be 256-byte aligned, the maps 16-byte");
+    Arena t = tape_arena(tape, tail_tape_need(net, stack, h, w));
+    Run rt{net, &t, nullptr, net->parts, true};   // (no launches: the addresses)
+    TailLayout L;
+    tail_layout(rt, stack, h, w, L);
+    Arena a;
+    const size_t need = tail_backward_need(net, stack, h, w);
+    SURS_REQUIRE(workspace_arena(workspace, workspace_bytes, need - 256, a), "tail_backward: workspace too small: %zu bytes needed", need);
+    Run r{net, &a, as_stream(stream), net->parts, false};
+    TailBack k{r, accumulate ? 1 : 0};
+    const int d = net->l[stack].cout;
+    k.alloc(h, w, d);
+    k.run(L.T, last, *params, *grads, input_map(g_out, h, w, d, d), input_map(g_next, h, w, 256, 256), input_map(d_ll, h, w, 256, 256));
+    return r.rc;
+}
+
+extern "C" size_t surs_encoder_filter_lr_tape_bytes(const SursEncoderNet *net, int h, int w) {
+    if (!net || check_filter_train(net, h, w, "filter_lr_tape_bytes")) return 0;
+    return filter_tape_need(net, h, w);
+}
+
+extern "C" size_t surs_encoder_filter_lr_backward_workspace_bytes(const SursEncoderNet *net, int h, int w) {
+    if (!net || check_filter_train(net, h, w, "filter_lr_backward_workspace_bytes")) return 0;
+    return filter_backward_need(net, h, w);
+}
+
+extern "C" int surs_encoder_filter_lr_train(const SursEncoderNet *net, const float *feature_lr, int h, int w, int ld, float *const *outs,
+                                            void *tape, size_t tape_bytes, void *stream) {
+    if (int rc = check_filter_train(net, h, w, "filter_lr_train")) return rc;
+    SURS_REQUIRE(feature_lr && outs && tape, "filter_lr_train: null argument");
+    for (int s = 0; s < net->num_stack; ++s) SURS_REQUIRE(outs[s], "filter_lr_train: training keeps every stack's output");
+    SURS_REQUIRE(ld >= 256, "filter_lr_train: a map of 256 channels");
+    SURS_REQUIRE(((size_t)tape & 255) == 0, "filter_lr_train: the tape must be 256-byte aligned");
+    const size_t need = filter_tape_need(net, h, w);
+    SURS_REQUIRE(need <= tape_bytes, "filter_lr_train: tape too small: %zu bytes needed", need);
+    Arena a = tape_arena(tape, tape_bytes);
+    Run r{net, &a, as_stream(stream), net->parts, false};
+    std::unique_ptr<FilterLayout> L(new FilterLayout);
+    filter_layout(r, h, w, *L, feature_lr, ld);
+    if (r.rc) return r.rc;
+    for (int s = 0; s < net->num_stack; ++s)
+        SURS_HIP_CHECK(hipMemcpyAsync(outs[s], L->outs[s].p, sizeof(float) * h * w * L->outs[s].c, hipMemcpyDeviceToDevice, r.st));
+    return 0;
+}
+
+extern "C" int surs_encoder_filter_lr_backward(const SursEncoderNet *net, const SursHgFilterParams *params, const void *tape, int h, int w,
+                                               const float *const *g_outs, float *d_feature_lr, const SursHgFilterParams *grads,
+                                               int accumulate, void *workspace, size_t workspace_bytes, void *stream) {
+    if (int rc = check_filter_train(net, h, w, "filter_lr_backward")) return rc;
+    SURS_REQUIRE(params && grads && tape && g_outs && d_feature_lr && workspace, "filter_lr_backward: null argument");
+    const int S = net->num_stack, per = per_stack_blocks(net);
+    bool any = false;
+    for (int s = 0; s < S; ++s) {
+        any = any || g_outs[s];
+        SURS_REQUIRE(aligned16(g_outs[s]), "filter_lr_backward: the maps must be 16-byte aligned");
+    }
+    SURS_REQUIRE(any, "filter_lr_backward: every gradient is missing");
+    for (const SursHgFilterParams *p : {params, grads}) {
+        SURS_REQUIRE(p->hg && p->top_m && p->tail && hg_params_filled(&p->conv2, 1) && hg_params_filled(p->hg, S * per) &&
+                     hg_params_filled(p->top_m, S), "filter_lr_backward: a null pointer in params / grads");
+        for (int s = 0; s < S; ++s) SURS_REQUIRE(tail_param_filled(p->tail[s], s == S - 1), "filter_lr_backward: a null pointer in params / grads");
+    }
+    SURS_REQUIRE(((size_t)tape & 255) == 0 && aligned16(d_feature_lr), "filter_lr_backward: the tape must be 256-byte aligned, the maps 16-byte");
+    Arena t = tape_arena(tape, filter_tape_need(net, h, w));
+    Run rt{net, &t, nullptr, net->parts, true};   // (no launches: the addresses)
+    std::unique_ptr<FilterLayout> L(new FilterLayout);
+    filter_layout(rt, h, w, *L);
+    Arena a;
+    const size_t need = filter_backward_need(net, h, w);
+    SURS_REQUIRE(workspace_arena(workspace, workspace_bytes, need - 256, a), "filter_lr_backward: workspace too small: %zu bytes needed", need);
+    Run r{net, &a, as_stream(stream), net->parts, false};
+    FilterBack k(r, accumulate ? 1 : 0);
+    k.alloc(h, w);
+    k.run(*L, *params, *grads, g_outs, input_map(d_feature_lr, h, w, 256, 256));
+    return r.rc;
 }

@@ -16,9 +16,10 @@ mlp_lr.* and mlp_hr.* parameter) and, with features=True, d error / d (the featu
 network and image_filter_hr.conv5 have a backward too: super_res_train() keeps the forward's maps, super_res_backward() returns the
 gradients of every super_resolution.* convolution and conv5 from the gradients of img_SR, feature_lr and im_feat_list_hr[0]
 (native.sr_backward), sr_parameters() are the fp32 weights it reads, autograd.super_res_features is the torch.autograd.Function over
-them.  Of the hourglass (image_filter_lr.*) the ConvBlock and the HourGlass module m{s} have a backward (--norm group):
-conv_block_train() / conv_block_backward(), hourglass_train() / hourglass_backward() (native.hg_backward), hg_parameters(),
-autograd.conv_block and autograd.hourglass, from which a trainable filter_lr is composed with the stack tails' 1 x 1 layers in torch;
+them.  The hourglass filter (image_filter_lr.*) has a backward too (--norm group): per module, conv_block_train() /
+conv_block_backward(), hourglass_train() / hourglass_backward() (native.hg_backward), stack_tail_train() / stack_tail_backward()
+(native.tail_backward), and as a whole, filter_lr_train() / filter_lr_backward() (native.filter_lr_backward); hg_parameters() are the
+fp32 weights they read, autograd.conv_block, autograd.hourglass, autograd.stack_tail and autograd.filter_lr the Functions over them;
 forward_backward() does not return encoder gradients.
 
 Encoder options: --norm group | batch and --scale 1..4 (anything else: ValueError at construction).  --norm batch is nn.BatchNorm2d in
@@ -404,9 +405,12 @@ class SuRSNet:
         return grads
 
     # ------------------------------------------------------------------ hourglass gradients
-    def _hg_native(self):
+    def _hg_check_norm(self):
         if weights.check_norm(getattr(self.opt, "norm", "group")) == "batch":
             raise NotImplementedError("hourglass gradients: --norm group only (a BatchNorm encoder runs in eval mode and has no backward)")
+
+    def _hg_native(self):
+        self._hg_check_norm()
         W = self._encoder_weights()
         if W.reduced:
             raise RuntimeError("hourglass gradients: --encoder_precision f16 (net->parts == 1) has no backward: training runs the "
@@ -494,6 +498,115 @@ class SuRSNet:
         """(d <grad_out, out> / d x, OrderedDict of the gradients of every parameter of m{stack}, blocks in module order) from the
         tapes of the preceding hourglass_train(stack, x)."""
         return self._hg_backward(int(stack), grad_out, "hourglass")
+
+    # ------------------------------------------------------------------ stack-tail gradients, and the whole low-resolution filter
+    def _hg_workspace(self, need, dev):
+        if self._hg_ws is None or self._hg_ws.numel() < need or self._hg_ws.device != dev:
+            self._hg_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        return self._hg_ws
+
+    def _nhwc(self, g, shape, name):
+        if g is None:
+            return None
+        if tuple(g.shape) != shape:
+            raise ValueError("%s %s against the output's %s" % (name, tuple(g.shape), shape))
+        return g.detach().to(self._device(), torch.float32).permute(0, 2, 3, 1).contiguous()
+
+    def stack_tail_train(self, stack, ll, previous=None):
+        """The tail of stack `stack` - conv_last -> bn_end -> ReLU -> l, and next = previous + bl(.) + al(l(.)) on the merged next{s} -
+        on ll [B,256,h,w] and, for every stack but the last, previous [B,256,h,w]: filter_lr()'s launches and bits, tapes kept
+        (surs_encoder_tail_train).  Returns (out [B,hg_dim,h,w], next [B,256,h,w] or None for the last stack)."""
+        self._hg_check_norm()
+        stack, S = int(stack), self.opt.num_stack_lr
+        if not 0 <= stack < S:
+            raise ValueError("stack %d of %d" % (stack, S))
+        if (stack == S - 1) != (previous is None):
+            raise RuntimeError("stack_tail_train: previous goes with every stack but the last (stack %d of %d)" % (stack, S))
+        if ll.dim() != 4 or ll.shape[1] != 256 or (previous is not None and tuple(previous.shape) != tuple(ll.shape)):
+            raise ValueError("[B,256,h,w] tensors of one shape are expected, not %s" % (tuple(ll.shape),))
+        net = self._hg_native()
+        dev = self._device()
+        outs, nexts, tapes = [], [], []
+        for b in range(ll.shape[0]):
+            prev = None if previous is None else _as_img(previous[b:b + 1].detach().to(dev, torch.float32))
+            out, nxt, tape = native.tail_train_forward(net, stack, _as_img(ll[b:b + 1].detach().to(dev, torch.float32)), prev)
+            outs.append(_as_nchw_view(out))
+            nexts.append(None if nxt is None else _as_nchw_view(nxt))
+            tapes.append(tape)
+        self._hg_tapes[("tail", stack)] = (ll.shape[2], ll.shape[3], tapes)
+        cat = lambda v: torch.cat(v, 0) if len(v) > 1 else v[0]
+        return cat(outs), (None if previous is None else cat(nexts))
+
+    def stack_tail_backward(self, stack, grad_out=None, grad_next=None):
+        """(d L / d ll, d L / d previous - grad_next itself; None for the last stack or without grad_next -, OrderedDict of the gradients
+        of conv_last{s}, bn_end{s}, l{s} and, for a stack that is not the last, bl{s}, al{s} (.weight, .bias each; the UN-MERGED
+        parameters), summed over the batch in image order) for L = <grad_out, out> + <grad_next, next>, from the tapes of the preceding
+        stack_tail_train(stack, ...).  Either gradient may be None (zero), not both."""
+        self._hg_check_norm()
+        stack = int(stack)
+        if grad_out is None and grad_next is None:
+            raise RuntimeError("stack_tail_backward: no upstream gradient (both are None)")
+        if grad_next is not None and stack == self.opt.num_stack_lr - 1:
+            raise RuntimeError("stack_tail_backward: the last stack has no next")
+        kept = self._hg_tapes.get(("tail", stack))
+        if kept is None:
+            raise RuntimeError("stack_tail_backward needs a preceding stack_tail_train() of the same stack: the tape of the forward's "
+                               "maps is missing")
+        net = self._hg_native()
+        h, w, tapes = kept
+        dev, B = self._device(), len(tapes)
+        go = self._nhwc(grad_out, (B, net.l[stack].cout, h, w), "grad_out")
+        gn = self._nhwc(grad_next, (B, 256, h, w), "grad_next")
+        params = self._hg_param_set()[0].tensors
+        ws = self._hg_workspace(native.tail_backward_workspace_bytes(net, h, w), dev)
+        grads, dls = None, []
+        for b in range(B):
+            dl, grads = native.tail_backward(net, stack, params, tapes[b], h, w, None if go is None else go[b], None if gn is None else gn[b],
+                                             grads=grads, accumulate=b > 0, workspace=ws)
+            dls.append(dl)
+        return torch.stack(dls, 0).permute(0, 3, 1, 2), grad_next, grads
+
+    def filter_lr_train(self, feature_lr):
+        """HGFilter.forward on feature_lr [B,256,h,w] with every map the backward reads kept, one tape per image
+        (surs_encoder_filter_lr_train): the list of every stack's output [B,hg_dim,h,w], filter_lr()'s values."""
+        self._hg_check_norm()
+        if feature_lr.dim() != 4 or feature_lr.shape[1] != 256:
+            raise ValueError("a [B,256,h,w] tensor is expected, not %s" % (tuple(feature_lr.shape),))
+        net = self._hg_native()
+        dev = self._device()
+        per, tapes = [], []
+        for b in range(feature_lr.shape[0]):
+            outs, tape = native.filter_lr_train_forward(net, _as_img(feature_lr[b:b + 1].detach().to(dev, torch.float32)))
+            per.append([_as_nchw_view(o) for o in outs])
+            tapes.append(tape)
+        self._hg_tapes["filter_lr"] = (feature_lr.shape[2], feature_lr.shape[3], tapes)
+        return [torch.cat([pv[s] for pv in per], 0) if len(per) > 1 else per[0][s] for s in range(len(per[0]))]
+
+    def filter_lr_backward(self, grad_outs):
+        """(d L / d feature_lr, OrderedDict over hg_parameters()'s keys) for L = sum_s <grad_outs[s], outs[s]> from the tapes of the
+        preceding filter_lr_train(): grad_outs holds one [B,hg_dim,h,w] tensor or None (zero) per stack, not all None.  Summed over
+        the batch in image order; the parameters of a stack no gradient reaches get zeros."""
+        self._hg_check_norm()
+        S = self.opt.num_stack_lr
+        if len(grad_outs) != S:
+            raise ValueError("one gradient (or None) per stack: %d for %d stacks" % (len(grad_outs), S))
+        if all(g is None for g in grad_outs):
+            raise RuntimeError("filter_lr_backward: no upstream gradient (all are None)")
+        kept = self._hg_tapes.get("filter_lr")
+        if kept is None:
+            raise RuntimeError("filter_lr_backward needs a preceding filter_lr_train(): the tape of the forward's maps is missing")
+        net = self._hg_native()
+        h, w, tapes = kept
+        dev, B = self._device(), len(tapes)
+        gs = [self._nhwc(g, (B, net.l[s].cout, h, w), "grad_outs[%d]" % s) for s, g in enumerate(grad_outs)]
+        hp = self._hg_param_set()[0]
+        ws = self._hg_workspace(native.filter_lr_backward_workspace_bytes(net, h, w), dev)
+        grads, dxs = None, []
+        for b in range(B):
+            dx, grads = native.filter_lr_backward(net, self.opt.hg_depth, hp.keys, hp.tensors, tapes[b], h, w,
+                                                  [None if g is None else g[b] for g in gs], grads=grads, accumulate=b > 0, workspace=ws)
+            dxs.append(dx)
+        return torch.stack(dxs, 0).permute(0, 3, 1, 2), grads
 
     def reencode_wide(self):
         """Runs the encoder again on the images of the last super_res() call with every fp32-grade product on three bf16 parts

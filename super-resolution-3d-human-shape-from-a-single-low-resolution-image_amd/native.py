@@ -1623,6 +1623,178 @@ def hg_backward(net, which, prefixes, params, tape, h, w, g, grads=None, accumul
     return dx, grads
 
 
+# ------------------------------------------------------------------ stack-tail gradients, and the whole low-resolution filter
+
+def tail_joint_grad(g_out, g_next, w_al, w_l, w_bl, d_out=None, d_a=None):
+    """surs_tail_joint_grad: (dOut Img [h,w,D], dA Img [h,w,256]) = (g_out + g_next W_al, dOut W_l + g_next W_bl) in one launch, from
+    Img g_out [h,w,D] and g_next [h,w,256] (either None = zero, not both) and the plain weights al [256,D,1,1], l [D,256,1,1],
+    bl [256,256,1,1] (device; al and bl are read only with g_next)."""
+    ref = g_out if g_out is not None else g_next
+    if ref is None:
+        raise ValueError("tail_joint_grad: both gradients are None")
+    w_l = _f32c(w_l)
+    D, h, w, dev = w_l.shape[0], ref.h, ref.w, ref.buf.device
+    if w_l.numel() != D * 256 or (g_out is not None and g_out.c != D) or (g_next is not None and g_next.c != 256):
+        raise ValueError("tail_joint_grad: l %s against g_out / g_next of %s / %s channels"
+                         % (tuple(w_l.shape), g_out and g_out.c, g_next and g_next.c))
+    if g_next is not None and (_f32c(w_al).numel() != 256 * D or _f32c(w_bl).numel() != 256 * 256 or (g_next.h, g_next.w) != (h, w)):
+        raise ValueError("tail_joint_grad: al %s, bl %s against D = %d" % (tuple(w_al.shape), tuple(w_bl.shape), D))
+    d_out = Img(h, w, D, device=dev) if d_out is None else d_out
+    d_a = Img(h, w, 256, device=dev) if d_a is None else d_a
+    if (d_out.h, d_out.w, d_out.c) != (h, w, D) or (d_a.h, d_a.w, d_a.c) != (h, w, 256):
+        raise ValueError("tail_joint_grad: outputs of %s / %s" % ((h, w, D), (h, w, 256)))
+    check(lib().surs_tail_joint_grad(g_out.ptr() if g_out is not None else None, g_out.ld if g_out is not None else 0,
+                                     g_next.ptr() if g_next is not None else None, g_next.ld if g_next is not None else 0,
+                                     _ptr(w_al) if g_next is not None else None, _ptr(w_l), _ptr(w_bl) if g_next is not None else None,
+                                     h * w, D, d_out.ptr(), d_out.ld, d_a.ptr(), d_a.ld, _stream()))
+    return d_out, d_a
+
+
+def hg_tail_keys(stack, num_stack):
+    """The tail of stack `stack`: conv_last, bn_end, l and - not for the last stack - bl, al, .weight and .bias each."""
+    names = ["conv_last%d", "bn_end%d", "l%d"] + (["bl%d", "al%d"] if stack < num_stack - 1 else [])
+    return [HG + n % stack + e for n in names for e in (".weight", ".bias")]
+
+
+def _fill_tail(t, stack, num_stack, tensors):
+    for field in ("conv_last", "l") + (("bl", "al") if stack < num_stack - 1 else ()):
+        getattr(t, field).weight = _f32c(tensors[HG + "%s%d.weight" % (field, stack)]).data_ptr()
+        getattr(t, field).bias = _f32c(tensors[HG + "%s%d.bias" % (field, stack)]).data_ptr()
+    t.gamma = _f32c(tensors[HG + "bn_end%d.weight" % stack]).data_ptr()
+    t.beta = _f32c(tensors[HG + "bn_end%d.bias" % stack]).data_ptr()
+
+
+def hg_tail_struct(stack, num_stack, tensors):
+    """SursHgTailParams of stack `stack` over `tensors`: key -> contiguous float32 device tensor."""
+    t = _lib.HgTailParams()
+    _fill_tail(t, stack, num_stack, tensors)
+    return t
+
+
+def hg_filter_struct(num_stack, depth, tensors):
+    """(SursHgFilterParams over `tensors`, the ctypes arrays behind its pointers - keep them alive for the call)."""
+    pre = [p for s in range(num_stack) for p in hg_block_prefixes(s, depth)]
+    hg = HgParams.struct(pre, tensors)
+    top = HgParams.struct([HG + "top_m_%d." % s for s in range(num_stack)], tensors)
+    tails = (_lib.HgTailParams * num_stack)()
+    for s in range(num_stack):
+        _fill_tail(tails[s], s, num_stack, tensors)
+    f = _lib.HgFilterParams(HgParams.struct([HG + "conv2."], tensors)[0], hg, top, tails)
+    return f, (hg, top, tails)
+
+
+def tail_tape_bytes(net, h, w):
+    return _hg_size("surs_encoder_tail_tape_bytes", net, h, w)
+
+
+def tail_backward_workspace_bytes(net, h, w):
+    return _hg_size("surs_encoder_tail_backward_workspace_bytes", net, h, w)
+
+
+def filter_lr_tape_bytes(net, h, w):
+    return _hg_size("surs_encoder_filter_lr_tape_bytes", net, h, w)
+
+
+def filter_lr_backward_workspace_bytes(net, h, w):
+    return _hg_size("surs_encoder_filter_lr_backward_workspace_bytes", net, h, w)
+
+
+def _check_grads(grads, keys, params, dev, accumulate):
+    if accumulate and grads is None:
+        raise ValueError("accumulate needs the grads to add to")
+    if grads is None:
+        return OrderedDict((k, torch.empty_like(params[k])) for k in keys)
+    for k in keys:
+        if k not in grads or tuple(grads[k].shape) != tuple(params[k].shape) or grads[k].dtype != torch.float32 \
+                or not grads[k].is_contiguous() or grads[k].device != dev:
+            raise ValueError("grads[%r] must be a contiguous float32 tensor %s on %s" % (k, tuple(params[k].shape), dev))
+    return grads
+
+
+def _check_g(g, shape, dev, name):
+    if g is None:
+        return None
+    if tuple(g.shape[-3:]) != shape or g.numel() != shape[0] * shape[1] * shape[2] or g.dtype != torch.float32 or not g.is_contiguous() \
+            or g.device != dev:
+        raise ValueError("%s must be a contiguous float32 NHWC tensor %s on %s, not %s" % (name, shape, dev, tuple(g.shape)))
+    return g
+
+
+def tail_train_forward(net, stack, ll, previous=None, tape=None):
+    """surs_encoder_tail_train: the tail of stack `stack` on Img ll [h,w,256] and - every stack but the last - Img previous [h,w,256].
+    Returns (out Img [h,w,D], next Img [h,w,256] or None, tape): the bits of filter_lr()'s tail on the same maps."""
+    dev, last = ll.buf.device, stack == net.num_stack - 1
+    if ll.c != 256 or (previous is not None and (previous.h, previous.w, previous.c) != (ll.h, ll.w, 256)):
+        raise ValueError("maps of 256 channels and one size are expected")
+    if last != (previous is None):
+        raise ValueError("previous goes with every stack but the last (stack %d of %d)" % (stack, net.num_stack))
+    tape = _hg_buffer(tape, tail_tape_bytes(net, ll.h, ll.w), dev, "tape")
+    out = Img(ll.h, ll.w, net.l[stack].cout, device=dev)
+    nxt = None if last else Img(ll.h, ll.w, 256, device=dev)
+    check(lib().surs_encoder_tail_train(C.byref(net), stack, ll.ptr(), ll.ld, None if last else previous.ptr(), 0 if last else previous.ld,
+                                        ll.h, ll.w, out.ptr(), None if last else nxt.ptr(), _ptr(tape), tape.numel() * tape.element_size(),
+                                        _stream()))
+    return out, nxt, tape
+
+
+def tail_backward(net, stack, params, tape, h, w, g_out=None, g_next=None, grads=None, accumulate=False, workspace=None):
+    """surs_encoder_tail_backward for ONE image: g_out [h,w,D], g_next [h,w,256] contiguous float32 NHWC device tensors (None: zero, not
+    both); params: key -> plain fp32 device tensor.  Returns (d_ll [h,w,256] tensor, grads over hg_tail_keys(stack))."""
+    dev, S = tape.device, net.num_stack
+    keys = hg_tail_keys(stack, S)
+    grads = _check_grads(grads, keys, params, dev, accumulate)
+    g_out = _check_g(g_out, (h, w, net.l[stack].cout), dev, "g_out")
+    g_next = _check_g(g_next, (h, w, 256), dev, "g_next")
+    if g_out is None and g_next is None:
+        raise ValueError("tail_backward: both gradients are None")
+    if tape.numel() * tape.element_size() < tail_tape_bytes(net, h, w):
+        raise ValueError("tape: %d bytes needed for a %dx%d map" % (tail_tape_bytes(net, h, w), h, w))
+    workspace = _hg_buffer(workspace, tail_backward_workspace_bytes(net, h, w), dev, "workspace")
+    ps, gs = hg_tail_struct(stack, S, params), hg_tail_struct(stack, S, grads)
+    d_ll = torch.empty((h, w, 256), dtype=torch.float32, device=dev)
+    check(lib().surs_encoder_tail_backward(C.byref(net), stack, C.byref(ps), _ptr(tape), h, w, _ptr(g_out), _ptr(g_next), _ptr(d_ll),
+                                           C.byref(gs), 1 if accumulate else 0, _ptr(workspace),
+                                           workspace.numel() * workspace.element_size(), _stream()))
+    return d_ll, grads
+
+
+def filter_lr_train_forward(net, x, tape=None):
+    """surs_encoder_filter_lr_train of Img x [h,w,256]: (the list of every stack's output Img [h,w,D], tape)."""
+    dev, S = x.buf.device, net.num_stack
+    if x.c != 256:
+        raise ValueError("a map of 256 channels is expected, not %d" % x.c)
+    tape = _hg_buffer(tape, filter_lr_tape_bytes(net, x.h, x.w), dev, "tape")
+    outs = [Img(x.h, x.w, net.l[s].cout, device=dev) for s in range(S)]
+    ptrs = (C.c_void_p * S)(*[o.ptr() for o in outs])
+    check(lib().surs_encoder_filter_lr_train(C.byref(net), x.ptr(), x.h, x.w, x.ld, ptrs, _ptr(tape), tape.numel() * tape.element_size(),
+                                             _stream()))
+    return outs, tape
+
+
+def filter_lr_backward(net, depth, keys, params, tape, h, w, g_outs, grads=None, accumulate=False, workspace=None):
+    """surs_encoder_filter_lr_backward for ONE image: g_outs: per stack a contiguous float32 NHWC device tensor [h,w,D] or None (zero;
+    not all); keys: hg_param_keys() - the order of the returned grads; params: key -> plain fp32 device tensor.  Returns
+    (d_feature_lr [h,w,256] tensor, grads)."""
+    dev, S = tape.device, net.num_stack
+    grads = _check_grads(grads, keys, params, dev, accumulate)
+    if len(g_outs) != S:
+        raise ValueError("one gradient (or None) per stack: %d for %d stacks" % (len(g_outs), S))
+    g_outs = [_check_g(g, (h, w, net.l[s].cout), dev, "g_outs[%d]" % s) for s, g in enumerate(g_outs)]
+    if all(g is None for g in g_outs):
+        raise ValueError("filter_lr_backward: every gradient is None")
+    if tape.numel() * tape.element_size() < filter_lr_tape_bytes(net, h, w):
+        raise ValueError("tape: %d bytes needed for a %dx%d map" % (filter_lr_tape_bytes(net, h, w), h, w))
+    workspace = _hg_buffer(workspace, filter_lr_backward_workspace_bytes(net, h, w), dev, "workspace")
+    (ps, keep_p), (gs, keep_g) = hg_filter_struct(S, depth, params), hg_filter_struct(S, depth, grads)
+    ptrs = (C.c_void_p * S)(*[None if g is None else g.data_ptr() for g in g_outs])
+    dx = torch.empty((h, w, 256), dtype=torch.float32, device=dev)
+    check(lib().surs_encoder_filter_lr_backward(C.byref(net), C.byref(ps), _ptr(tape), h, w, ptrs, _ptr(dx), C.byref(gs),
+                                                1 if accumulate else 0, _ptr(workspace), workspace.numel() * workspace.element_size(),
+                                                _stream()))
+    del keep_p, keep_g
+    return dx, grads
+
+
 def query_points_views(points, calibs, projection, zmul, zdiv, feat_lr, feat_hr, blob, ws, want_logits=False):
     """Multi-view / perspective query.  points [V,3,N] f32 device tensor; calibs [V,12] (host); feat_lr [V,hl,wl,256] and
     feat_hr [V,hh,wh,64] contiguous NHWC device tensors; projection 'orthogonal' | 'perspective'.
