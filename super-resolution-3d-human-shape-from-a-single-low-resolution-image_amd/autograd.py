@@ -1,7 +1,8 @@
 """The point path as a torch.autograd.Function: gather, both classifiers on every kept stack and the three classifier terms of
 SuRSNet.forward's loss, differentiable with respect to the feature maps.  An encoder that has a backward of its own - a torch encoder
-under autograd - trains against this library's point evaluator through it.  super_res_features, conv_block and hourglass are the
-Functions over the parts of the encoder that have a backward here; nothing else in the package grows an autograd graph."""
+under autograd - trains against this library's point evaluator through it.  super_res_features, conv_block, hourglass,
+stack_tail and filter_lr are the parts of the encoder that have a backward here, each through the one Function _Taped; nothing else in
+the package grows an autograd graph."""
 import torch
 
 from . import native
@@ -44,27 +45,31 @@ def point_loss(net, feat_lr_list, feat_hr, points_mr, points_sr, calibs, labels_
                             feat_hr)
 
 
-class _SuperResFeatures(torch.autograd.Function):
+class _Taped(torch.autograd.Function):
+    """One taped module of the encoder: train(*inputs) -> its outputs, the tapes it files under `module` in net._tapes kept HERE;
+    backward(the outputs' gradients - None where none arrived -, those tapes) -> (every input's gradient ..., key -> parameter
+    gradient).  The first n_in of `tensors` are the inputs, the others the parameters behind `keys`."""
     @staticmethod
-    def forward(ctx, net, images_lr, *params):
-        img_SR, feature_lr, _ = net.super_res_train(images_lr)
-        ctx.net, ctx.tapes, ctx.n_params = net, net._sr_tapes, len(params)
+    def forward(ctx, net, module, train, backward, keys, n_in, *tensors):
+        outs = train(*tensors[:n_in])
+        ctx.backward_fn, ctx.keys, ctx.tapes = backward, keys, net._tapes[module]   # the tapes of THIS forward, whatever runs on net later
         ctx.set_materialize_grads(False)   # an output nothing differentiates arrives as None, not as a map of zeros
-        out = (img_SR, feature_lr, net.im_feat_list_hr[0])
         # (fresh tensors for autograd to own: the model keeps its NHWC views)
-        return tuple(o.clone() for o in out)
+        return tuple(o.clone() for o in outs)
 
     @staticmethod
-    def backward(ctx, g_img, g_lr, g_hr):
-        net = ctx.net
-        if g_img is None and g_lr is None and g_hr is None:
-            return (None,) * (2 + ctx.n_params)
-        kept, net._sr_tapes = net._sr_tapes, ctx.tapes   # the tapes of THIS forward, whatever ran on the net since
-        try:
-            grads = net.super_res_backward(g_img, g_lr, g_hr)
-        finally:
-            net._sr_tapes = kept
-        return (None, None) + tuple(grads.values())
+    def backward(ctx, *gs):
+        *d_inputs, grads = ctx.backward_fn(gs, ctx.tapes)
+        return (None,) * 6 + tuple(d_inputs) + tuple(grads[k] for k in ctx.keys)
+
+
+def _taped(net, module, train, backward, keys, inputs, params, own):
+    if params is None:
+        params = own
+    missing = [k for k in keys if k not in params]
+    if missing:
+        raise ValueError("params lacks %s" % missing[:3])
+    return _Taped.apply(net, module, train, backward, keys, len(inputs), *inputs, *[params[k] for k in keys])
 
 
 def super_res_features(net, images_lr, params=None):
@@ -78,49 +83,27 @@ def super_res_features(net, images_lr, params=None):
     The VALUES are those of the PACKED weights the forward runs on, not of `params`: after an optimiser step on sr_parameters(), call
     net.commit() before the next forward (as the examples of INTEGRATION.md do): it repacks them on the device from the parameters.
     Nothing else in the package grows a graph: forward()'s error.grad_fn stays None."""
-    if params is None:
-        params = net.sr_parameters()
-    keys = list(net.sr_parameters())
-    if list(params) != keys:
+    own = net.sr_parameters()
+    keys = list(own)
+    if params is not None and list(params) != keys:
         raise ValueError("params must hold net.sr_parameters()'s keys in their order")
-    return _SuperResFeatures.apply(net, images_lr, *params.values())
+
+    def train(x):
+        img_SR, feature_lr, _ = net.super_res_train(x)
+        return img_SR, feature_lr, net.im_feat_list_hr[0]
+
+    def backward(gs, tapes):
+        if all(g is None for g in gs):      # (nothing to go back through, and super_res_backward() refuses the call)
+            return None, dict.fromkeys(keys)
+        return None, net.super_res_backward(*gs, tapes=tapes)
+    return _taped(net, net.SR_TAPES, train, backward, keys, (images_lr,), params, own)
 
 
-class _HgModule(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, net, which, keys, x, *params):
-        hourglass = isinstance(which, int)
-        out = net.hourglass_train(which, x) if hourglass else net.conv_block_train(which, x)
-        key = which   # (an hourglass is filed under its stack, a block under its full prefix: net._hg_train)
-        ctx.net, ctx.which, ctx.keys, ctx.key, ctx.tapes = net, which, keys, key, net._hg_tapes[key]
-        return out.clone()   # (a fresh tensor for autograd to own)
-
-    @staticmethod
-    def backward(ctx, g):
-        net = ctx.net
-        kept = net._hg_tapes.get(ctx.key)
-        net._hg_tapes[ctx.key] = ctx.tapes   # the tapes of THIS forward, whatever ran on the net since
-        try:
-            fn = net.hourglass_backward if isinstance(ctx.which, int) else net.conv_block_backward
-            dx, grads = fn(ctx.which, g)
-        finally:
-            if kept is None:
-                del net._hg_tapes[ctx.key]
-            else:
-                net._hg_tapes[ctx.key] = kept
-        return (None, None, None, dx) + tuple(grads[k] for k in ctx.keys)
-
-
-def _hg_apply(net, which, prefixes, x, params):
-    from . import native
-    own = net.hg_parameters()
+def _hg_module(net, which, train, backward, x, params):
+    _, _, prefixes, module = net._hg_module(which)
     keys = [k for p in prefixes for k in native.hg_block_keys(p)]
-    if params is None:
-        params = own
-    missing = [k for k in keys if k not in params]
-    if missing:
-        raise ValueError("params lacks %s" % missing[:3])
-    return _HgModule.apply(net, which, keys, x, *[params[k] for k in keys])
+    return _taped(net, module, lambda x: (train(which, x),), lambda gs, tapes: backward(which, gs[0], tapes=tapes), keys, (x,), params,
+                  net.hg_parameters())[0]
 
 
 def conv_block(net, prefix, x, params=None):
@@ -128,50 +111,14 @@ def conv_block(net, prefix, x, params=None):
     its backward is net.conv_block_backward() and hands x its gradient and the block's nine entries of `params` - default
     net.hg_parameters() - theirs, summed over the batch in image order.  The VALUES are those of the PACKED weights the forward runs on: net.commit()
     after an optimiser step (see super_res_features)."""
-    _, _, prefixes = net._hg_module(prefix)
-    return _hg_apply(net, prefixes[0], prefixes, x, params)
+    return _hg_module(net, prefix, net.conv_block_train, net.conv_block_backward, x, params)
 
 
 def hourglass(net, stack, x, params=None):
     """The HourGlass module image_filter_lr.m{stack} on x [B,256,h,w] (h, w multiples of 2^hg_depth), with a grad_fn: its backward is
     net.hourglass_backward() and hands x and every parameter of the module its gradient.  With conv_block and stack_tail this
     composes a trainable filter_lr; filter_lr below is that composition as one call ("Hourglass gradients")."""
-    _, _, prefixes = net._hg_module(int(stack))
-    return _hg_apply(net, int(stack), prefixes, x, params)
-
-
-class _StackTail(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, net, stack, keys, ll, previous, *params):
-        out, nxt = net.stack_tail_train(stack, ll, previous)
-        ctx.net, ctx.stack, ctx.keys, ctx.tapes = net, stack, keys, net._hg_tapes[("tail", stack)]
-        ctx.set_materialize_grads(False)
-        if nxt is None:
-            return out.clone()
-        return out.clone(), nxt.clone()
-
-    @staticmethod
-    def backward(ctx, g_out, g_next=None):
-        net, key = ctx.net, ("tail", ctx.stack)
-        kept = net._hg_tapes.get(key)
-        net._hg_tapes[key] = ctx.tapes   # the tapes of THIS forward, whatever ran on the net since
-        try:
-            d_ll, d_prev, grads = net.stack_tail_backward(ctx.stack, g_out, g_next)
-        finally:
-            if kept is None:
-                del net._hg_tapes[key]
-            else:
-                net._hg_tapes[key] = kept
-        return (None, None, None, d_ll, d_prev) + tuple(grads[k] for k in ctx.keys)
-
-
-def _hg_keys(net, keys, params):
-    if params is None:
-        params = net.hg_parameters()
-    missing = [k for k in keys if k not in params]
-    if missing:
-        raise ValueError("params lacks %s" % missing[:3])
-    return params
+    return _hg_module(net, int(stack), net.hourglass_train, net.hourglass_backward, x, params)
 
 
 def stack_tail(net, stack, ll, previous=None, params=None):
@@ -179,40 +126,17 @@ def stack_tail(net, stack, ll, previous=None, params=None):
     returns out, or (out, next) for a stack that is not the last; its backward is net.stack_tail_backward() and hands ll, previous
     and the tail's entries of `params` - default net.hg_parameters() - their gradients.  The VALUES are those of the PACKED weights,
     the merged next{s} included: net.commit() after an optimiser step."""
-    from . import native
     stack = int(stack)
-    keys = native.hg_tail_keys(stack, net.opt.num_stack_lr)
-    params = _hg_keys(net, keys, params)
-    return _StackTail.apply(net, stack, keys, ll, previous, *[params[k] for k in keys])
-
-
-class _FilterLr(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, net, keys, x, *params):
-        outs = net.filter_lr_train(x)
-        ctx.net, ctx.keys, ctx.tapes = net, keys, net._hg_tapes["filter_lr"]
-        ctx.set_materialize_grads(False)
-        return tuple(o.clone() for o in outs)
-
-    @staticmethod
-    def backward(ctx, *gs):
-        net = ctx.net
-        kept = net._hg_tapes.get("filter_lr")
-        net._hg_tapes["filter_lr"] = ctx.tapes
-        try:
-            dx, grads = net.filter_lr_backward(list(gs))
-        finally:
-            if kept is None:
-                del net._hg_tapes["filter_lr"]
-            else:
-                net._hg_tapes["filter_lr"] = kept
-        return (None, None, dx) + tuple(grads[k] for k in ctx.keys)
+    outs = _taped(net, ("tail", stack), lambda ll, previous: [o for o in net.stack_tail_train(stack, ll, previous) if o is not None],
+                  lambda gs, tapes: net.stack_tail_backward(stack, *gs, tapes=tapes), native.hg_tail_keys(stack, net.opt.num_stack_lr),
+                  (ll, previous), params, net.hg_parameters())
+    return outs if len(outs) > 1 else outs[0]
 
 
 def filter_lr(net, feature_lr, params=None):
     """HGFilter.forward of SuRSNet `net` on feature_lr [B,256,h,w] with a grad_fn: the list of every stack's output; its backward is
     net.filter_lr_backward() - ONE call for the whole filter - and hands feature_lr and every entry of `params` (default
     net.hg_parameters(), all of its keys) their gradients.  net.commit() after an optimiser step, as for the modules."""
-    keys = list(net.hg_parameters())
-    params = _hg_keys(net, keys, params)
-    return list(_FilterLr.apply(net, keys, feature_lr, *[params[k] for k in keys]))
+    own = net.hg_parameters()
+    return list(_taped(net, "filter_lr", net.filter_lr_train, lambda gs, tapes: net.filter_lr_backward(list(gs), tapes=tapes), list(own),
+                       (feature_lr,), params, own))

@@ -45,6 +45,11 @@ def _as_nchw_view(img):
     return img.buf.view(1, img.h, img.w, img.c).permute(0, 3, 1, 2)
 
 
+def _cat_views(imgs):
+    """The [B,C,h,w] batch of the NHWC Imgs `imgs` of one shape: a zero-copy view of a single one."""
+    return torch.cat([_as_nchw_view(i) for i in imgs], 0) if len(imgs) > 1 else _as_nchw_view(imgs[0])
+
+
 def _as_img(t):
     """torch [1,C,H,W] (any layout) or [C,H,W] -> NHWC Img; zero-copy when it already is channels_last."""
     if t.dim() == 3:
@@ -89,16 +94,15 @@ class SuRSNet:
         self._mr_hr = None
         self._sr_points = None        # query_sr's points and (calibs, transforms): what classifier_grads() differentiates
         self._sr_args = None
-        self._grad_params = None      # native.MlpParams: the device copy of the fp32 classifier weights (dropped like the blob)
-        self._mlp_param_dict = None   # mlp_parameters()'s OrderedDict over _grad_params.tensors
+        # "mlp" / "sr" / "hg" -> (native.MlpParams / SrParams / HgParams: the plain fp32 device masters, {mlp,sr,hg}_parameters()'s
+        # OrderedDict of torch.nn.Parameter over them), for the sets asked for so far (dropped like the blob)
+        self._param_sets = {}
         self._stale = set()           # commit(): the keys of _sd whose current values are on the device (the masters'), not yet in _sd
         self._grad_ws = None
-        self._sr_params = None        # native.SrParams + sr_parameters()'s OrderedDict: the plain fp32 super-resolution weights (dropped alike)
-        self._sr_tapes = None         # what super_res_train() left for super_res_backward(): (h, w, [one tape per image])
-        self._sr_ws = None
-        self._hg_params = None        # native.HgParams + hg_parameters()'s OrderedDict: the plain fp32 image_filter_lr weights (dropped alike)
-        self._hg_tapes = {}           # what conv_block_train() / hourglass_train() left: module -> (h, w, [one tape per image])
-        self._hg_ws = None
+        # what the last *_train() of each module left for its *_backward(): module -> (h, w, [one tape per image]); the modules are
+        # SR_TAPES (the super-resolution net), a ConvBlock's full prefix, an hourglass's stack index, ("tail", s) and "filter_lr"
+        self._tapes = {}
+        self._train_ws = None         # the *_backward() calls' workspace: one buffer, grown to the largest asked for
         self.last_classifier_grads = None   # what autograd.point_loss last left: classifier_grads()'s OrderedDict
         self._feat_cache = None
         self._stack_feat_cache = None
@@ -119,10 +123,8 @@ class SuRSNet:
             if self._enc is not None:
                 encoder.drop_graphs(self._enc)
             self._enc = self._blob = None
-            self._grad_params = self._grad_ws = self._mlp_param_dict = None
-            self._sr_params = self._sr_tapes = self._sr_ws = None
-            self._hg_params = self._hg_ws = None
-            self._hg_tapes = {}
+            self._grad_ws = self._train_ws = None
+            self._param_sets, self._tapes = {}, {}
         return self
 
     def cuda(self, index=None):
@@ -146,14 +148,7 @@ class SuRSNet:
 
     def _masters(self):
         """name of each parameter set -> its device masters (state-dict key -> tensor), for the sets that exist."""
-        out = OrderedDict()
-        if self._grad_params is not None:
-            out["mlp"] = self._grad_params.tensors
-        if self._sr_params is not None:
-            out["sr"] = self._sr_params[0].tensors
-        if self._hg_params is not None:
-            out["hg"] = self._hg_params[0].tensors
-        return out
+        return OrderedDict((w, self._param_sets[w][0].tensors) for w in self.SETS if w in self._param_sets)
 
     def _write_back(self):
         """Downloads the keys commit() marked stale from their device masters into _sd (the spec's shapes: [out,in,1] classifier
@@ -204,9 +199,9 @@ class SuRSNet:
             self._enc.refresh(enc)
         if "mlp" in which and self._blob is not None:
             if self._generic is not None:
-                native.mlp_repack_generic(self._grad_params, self._generic)
+                native.mlp_repack_generic(self._param_sets["mlp"][0], self._generic)
             else:
-                native.mlp_repack(self._grad_params, self._blob, self._core_dtype)
+                native.mlp_repack(self._param_sets["mlp"][0], self._blob, self._core_dtype)
         for w in which:
             self._stale.update(masters[w])
         return self
@@ -215,9 +210,23 @@ class SuRSNet:
         """The cached OrderedDict of torch.nn.Parameter over the plain fp32 device copies of every mlp_lr.* / mlp_hr.* tensor
         (state_dict() order; weights [out, in], biases [out]: the shapes native.MlpParams holds): what classifier_grads() reads and an
         optimiser steps.  The FORWARD runs on the packed blob: commit() after a step."""
-        if self._mlp_param_dict is None:
-            self._mlp_param_dict = OrderedDict((k, torch.nn.Parameter(v)) for k, v in self._mlp_params().tensors.items())
-        return self._mlp_param_dict
+        return self._param_set("mlp")[1]
+
+    def _param_set(self, which):
+        """(the native.MlpParams / SrParams / HgParams of set `which` of SETS, the OrderedDict of torch.nn.Parameter over its tensors),
+        built from the current values on first use."""
+        if which not in self._param_sets:
+            self._write_back()
+            if which == "mlp":
+                sd = {k: v for k, v in self._sd.items() if k.startswith("mlp_")}
+                shapes = native.mlp_shapes({k: v.numpy() for k, v in sd.items()}, self.opt)
+                p = native.MlpParams(sd, self._device(), shapes)
+            elif which == "sr":
+                p = native.SrParams(self._sd, self.opt.n_block, self._device())
+            else:
+                p = native.HgParams(self._sd, self.opt.num_stack_lr, self.opt.hg_depth, self._device())
+            self._param_sets[which] = (p, OrderedDict((k, torch.nn.Parameter(v)) for k, v in p.tensors.items()))
+        return self._param_sets[which]
 
     def load_state_dict(self, sd, strict=True):
         self._write_back()   # (a key `sd` lacks keeps its CURRENT value: a committed one lives in a master dropped below)
@@ -244,9 +253,7 @@ class SuRSNet:
         if self._enc is not None:
             encoder.drop_graphs(self._enc)
         self._enc = self._blob = None
-        self._grad_params = self._mlp_param_dict = None
-        self._sr_params = None
-        self._hg_params = None
+        self._param_sets = {}
         return self
 
     # ------------------------------------------------------------------ lazily packed device state
@@ -323,6 +330,51 @@ class SuRSNet:
                                 else _as_nchw_view(per_view[0][0])]
         self._hr_from = self.im_feat_list_hr[0].data_ptr() if (self._sr_out and images.data_ptr() == self._sr_out[1]) else None
 
+    # ------------------------------------------------------------------ training: taped forwards and their backwards
+    SR_TAPES = "super_res"   # the super-resolution network's key in _tapes
+
+    def _train(self, module, fn, *batches):
+        """The per-image train forward of one module: fn(Img, ...) -> (outputs ..., tape) on every image of the [B,C,h,w] tensors
+        `batches` (a None stays None), (h, w, [the tape of every image]) filed under `module` in _tapes.  Returns every image's outputs."""
+        batches = [None if t is None else t.detach().to(self._device(), torch.float32) for t in batches]
+        outs, tapes = [], []
+        for b in range(batches[0].shape[0]):
+            *o, tape = fn(*[None if t is None else _as_img(t[b:b + 1]) for t in batches])
+            outs.append(o)
+            tapes.append(tape)
+        self._tapes[module] = (batches[0].shape[2], batches[0].shape[3], tapes)
+        return outs
+
+    def _kept_tapes(self, module, tapes, what, of=""):
+        """`tapes` where given - the model is not touched -, else what the preceding {what}_train() filed under `module`."""
+        if tapes is None:
+            tapes = self._tapes.get(module)
+        if tapes is None:
+            raise RuntimeError("%s_backward needs a preceding %s_train()%s: the tape of the forward's maps is missing" % (what, what, of))
+        return tapes
+
+    def _backward(self, tapes, upstream, need, fn):
+        """The per-image backward of one module from `tapes` (one per image).  upstream: per output (its name, its gradient [B,c,h,w] or
+        None = zero, its (c, h, w)); need: the workspace's bytes; fn(tape, [image b's NHWC gradient or None per output], grads=,
+        accumulate=, workspace=) -> (the input's gradient [h,w,c] or None, grads).  The parameters' gradients are summed by the library in
+        image order: the first image overwrites, the later ones add.  Returns (the input's gradient [B,c,h,w] or None, grads)."""
+        dev, B = self._device(), len(tapes)
+        gs = []
+        for name, g, shape in upstream:
+            if g is not None:
+                if tuple(g.shape) != (B,) + shape:
+                    raise ValueError("%s %s against the output's %s" % (name, tuple(g.shape), (B,) + shape))
+                g = g.detach().to(dev, torch.float32).permute(0, 2, 3, 1).contiguous()
+            gs.append(g)
+        # (one workspace for every module: the calls are enqueued on the current stream in order)
+        if self._train_ws is None or self._train_ws.numel() < need or self._train_ws.device != dev:
+            self._train_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        grads, dxs = None, []
+        for b in range(B):
+            dx, grads = fn(tapes[b], [None if g is None else g[b] for g in gs], grads=grads, accumulate=b > 0, workspace=self._train_ws)
+            dxs.append(dx)
+        return (None if dxs[0] is None else torch.stack(dxs, 0).permute(0, 3, 1, 2)), grads
+
     # ------------------------------------------------------------------ super-resolution gradients
     def _sr_native(self):
         W = self._encoder_weights()
@@ -332,18 +384,14 @@ class SuRSNet:
         return encoder._native_net(W).net, W.scale
 
     def _sr_param_set(self):
-        if self._sr_params is None:
-            self._write_back()
-            p = native.SrParams(self._sd, self.opt.n_block, self._device())
-            self._sr_params = (p, OrderedDict((k, torch.nn.Parameter(v)) for k, v in p.tensors.items()))
-        return self._sr_params
+        return self._param_set("sr")
 
     def sr_parameters(self):
         """The cached OrderedDict of torch.nn.Parameter over the plain fp32 device copies of every super_resolution.* convolution and
         image_filter_hr.conv5 (state_dict() order, no sub_mean / add_mean): the tensors super_res_backward() reads, what an optimiser
         steps and autograd.super_res_features hands gradients to.  The FORWARD runs on PACKED copies: after an optimiser step,
         commit() repacks them on the device from these tensors (load_state_dict() drops this cache, as it drops the classifiers')."""
-        return self._sr_param_set()[1]
+        return self._param_set("sr")[1]
 
     def super_res_train(self, images):
         """super_res(images) followed by filter_hr(feature_hr) - the same kernels and bits in im_SR, feature_lr, feature_hr and
@@ -352,57 +400,39 @@ class SuRSNet:
         net, scale = self._sr_native()
         self._last_images = images
         self._sharded_encode = None
-        outs, tapes = [], []
-        for v in range(images.shape[0]):
-            x = _as_img(images[v:v + 1])
+
+        def one(x):
             encoder.check_image_size(x.h, x.w, scale)
-            *o, tape = native.sr_train_forward(net, x, scale)
-            outs.append(o)
-            tapes.append(tape)
-        cat = lambda i: torch.cat([_as_nchw_view(o[i]) for o in outs], 0) if len(outs) > 1 else _as_nchw_view(outs[0][i])
+            return native.sr_train_forward(net, x, scale)
+        outs = self._train(self.SR_TAPES, one, images)
+        cat = lambda i: _cat_views([o[i] for o in outs])
         self.im_SR, self.feature_lr, self.feature_hr = cat(0), cat(1), cat(2)
         self._sr_out = (self.feature_lr.data_ptr(), self.feature_hr.data_ptr())
         self._lr_from = None
         self._feat_hr_imgs = [[o[3] for o in outs]]
         self.im_feat_list_hr = [cat(3)]
         self._hr_from = self.im_feat_list_hr[0].data_ptr()
-        self._sr_tapes = (images.shape[2], images.shape[3], tapes)
         return self.im_SR, self.feature_lr, self.feature_hr
 
-    def super_res_backward(self, grad_img_SR=None, grad_feature_lr=None, grad_feat_hr=None):
+    def super_res_backward(self, grad_img_SR=None, grad_feature_lr=None, grad_feat_hr=None, tapes=None):
         """The gradients of <grad_img_SR, img_SR> + <grad_feature_lr, feature_lr> + <grad_feat_hr, im_feat_list_hr[0]> with respect to
         every super_resolution.* convolution and image_filter_hr.conv5 (surs_encoder_super_res_backward), from the tapes of the
         preceding super_res_train().  The arguments are NCHW tensors of those outputs' shapes, or None (zero; at least one is
         needed).  Returns an OrderedDict in state_dict() order (sr_parameters()'s keys): float32 device tensors of the parameters'
         shapes, summed over the images of the batch.  fp32 matrix products whatever --precision says, deterministic.  The gradient of
         feature_lr through image_filter_lr (the hourglass) is not part of this: whoever owns that network supplies
-        grad_feature_lr."""
-        if self._sr_tapes is None:
-            raise RuntimeError("super_res_backward needs a preceding super_res_train(): the tape of the forward's maps is missing")
+        grad_feature_lr.  tapes: what an earlier super_res_train() filed in _tapes[SR_TAPES], to go back through THAT forward
+        whatever ran since; the model's own entry is neither read nor changed."""
+        h, w, tapes = self._kept_tapes(self.SR_TAPES, tapes, "super_res")
         net, scale = self._sr_native()
-        params = self._sr_param_set()[0]
-        h, w, tapes = self._sr_tapes
-        dev, B = self._device(), len(tapes)
+        params = self._param_set("sr")[0]
         H2, W2 = scale * h, scale * w
-        shapes = ((B, 3, H2, W2), (B, 256, H2 // 4, W2 // 4), (B, net.conv5.cout, H2, W2))
-        gs = []
-        for name, g, shape in zip(("grad_img_SR", "grad_feature_lr", "grad_feat_hr"), (grad_img_SR, grad_feature_lr, grad_feat_hr), shapes):
-            if g is None:
-                gs.append(None)
-                continue
-            if tuple(g.shape) != shape:
-                raise ValueError("%s %s against the output's %s" % (name, tuple(g.shape), shape))
-            gs.append(g.detach().to(dev, torch.float32).permute(0, 2, 3, 1).contiguous())
-        if all(g is None for g in gs):
+        upstream = (("grad_img_SR", grad_img_SR, (3, H2, W2)), ("grad_feature_lr", grad_feature_lr, (256, H2 // 4, W2 // 4)),
+                    ("grad_feat_hr", grad_feat_hr, (net.conv5.cout, H2, W2)))
+        if all(g is None for _, g, _ in upstream):
             raise ValueError("super_res_backward: no upstream gradient (all three are None)")
-        need = native.sr_backward_workspace_bytes(net, h, w)
-        if self._sr_ws is None or self._sr_ws.numel() < need or self._sr_ws.device != dev:
-            self._sr_ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        grads = None
-        for b in range(B):
-            grads = native.sr_backward(net, params, tapes[b], h, w, *[None if g is None else g[b] for g in gs], grads=grads,
-                                       accumulate=b > 0, workspace=self._sr_ws, scale=scale)
-        return grads
+        return self._backward(tapes, upstream, native.sr_backward_workspace_bytes(net, h, w),
+                              lambda tape, g, **kw: (None, native.sr_backward(net, params, tape, h, w, *g, scale=scale, **kw)))[1]
 
     # ------------------------------------------------------------------ hourglass gradients
     def _hg_check_norm(self):
@@ -418,11 +448,7 @@ class SuRSNet:
         return encoder._native_net(W).net
 
     def _hg_param_set(self):
-        if self._hg_params is None:
-            self._write_back()
-            p = native.HgParams(self._sd, self.opt.num_stack_lr, self.opt.hg_depth, self._device())
-            self._hg_params = (p, OrderedDict((k, torch.nn.Parameter(v)) for k, v in p.tensors.items()))
-        return self._hg_params
+        return self._param_set("hg")
 
     def hg_parameters(self):
         """The cached OrderedDict of torch.nn.Parameter over the plain fp32 device copies of every image_filter_lr.* tensor the forward
@@ -430,53 +456,33 @@ class SuRSNet:
         what conv_block_backward() / hourglass_backward() read and autograd.conv_block / autograd.hourglass hand gradients to.  The
         FORWARD runs on PACKED copies: commit() repacks them from these tensors after an optimiser step (load_state_dict() drops this
         cache, as it drops sr_parameters()'s)."""
-        return self._hg_param_set()[1]
+        return self._param_set("hg")[1]
 
     def _hg_module(self, which):
-        """(the library's handle, the module's ConvBlock prefixes) of a stack index (its hourglass m{s}) or a ConvBlock's prefix."""
+        """(the library's net, the module's handle, its ConvBlock prefixes, its key in _tapes) of a stack index (its hourglass m{s},
+        filed under the index) or a ConvBlock's prefix (filed under the full prefix)."""
         net = self._hg_native()
         if isinstance(which, (int, np.integer)) and not isinstance(which, bool):
             if not 0 <= which < self.opt.num_stack_lr:
                 raise ValueError("stack %d of %d" % (which, self.opt.num_stack_lr))
-            return net, int(which), native.hg_block_prefixes(int(which), self.opt.hg_depth)
+            return net, int(which), native.hg_block_prefixes(int(which), self.opt.hg_depth), int(which)
         prefix = which if which.endswith(".") else which + "."
         if not prefix.startswith(native.HG):
             prefix = native.HG + prefix
-        return net, native.hg_block_of(net, prefix, self.opt.hg_depth), [prefix]
+        return net, native.hg_block_of(net, prefix, self.opt.hg_depth), [prefix], prefix
 
     def _hg_train(self, which, x):
-        net, handle, prefixes = self._hg_module(which)
+        net, handle, _, module = self._hg_module(which)
         if x.dim() != 4 or x.shape[1] != 256:
             raise ValueError("a [B,256,h,w] tensor is expected, not %s" % (tuple(x.shape),))
-        outs, tapes = [], []
-        for b in range(x.shape[0]):
-            out, tape = native.hg_train_forward(net, handle, _as_img(x[b:b + 1].detach().to(self._device(), torch.float32)))
-            outs.append(_as_nchw_view(out))
-            tapes.append(tape)
-        self._hg_tapes[prefixes[0] if len(prefixes) == 1 else handle] = (x.shape[2], x.shape[3], tapes)
-        return torch.cat(outs, 0) if len(outs) > 1 else outs[0]
+        return _cat_views([o[0] for o in self._train(module, lambda img: native.hg_train_forward(net, handle, img), x)])
 
-    def _hg_backward(self, which, grad_out, what):
-        net, handle, prefixes = self._hg_module(which)
-        kept = self._hg_tapes.get(prefixes[0] if len(prefixes) == 1 else handle)
-        if kept is None:
-            raise RuntimeError("%s_backward needs a preceding %s_train() of the same module: the tape of the forward's maps is missing"
-                               % (what, what))
-        h, w, tapes = kept
-        dev, B = self._device(), len(tapes)
-        if tuple(grad_out.shape) != (B, 256, h, w):
-            raise ValueError("grad_out %s against the output's %s" % (tuple(grad_out.shape), (B, 256, h, w)))
-        g = grad_out.detach().to(dev, torch.float32).permute(0, 2, 3, 1).contiguous()
-        params = self._hg_param_set()[0].tensors
-        need = native.hg_backward_workspace_bytes(net, h, w, len(prefixes) > 1)
-        if self._hg_ws is None or self._hg_ws.numel() < need or self._hg_ws.device != dev:
-            self._hg_ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        grads, dxs = None, []
-        for b in range(B):
-            dx, grads = native.hg_backward(net, handle, prefixes, params, tapes[b], h, w, g[b], grads=grads, accumulate=b > 0,
-                                           workspace=self._hg_ws)
-            dxs.append(dx)
-        return torch.stack(dxs, 0).permute(0, 3, 1, 2), grads
+    def _hg_backward(self, which, grad_out, what, tapes):
+        net, handle, prefixes, module = self._hg_module(which)
+        h, w, tapes = self._kept_tapes(module, tapes, what, " of the same module")
+        params = self._param_set("hg")[0].tensors
+        return self._backward(tapes, [("grad_out", grad_out, (256, h, w))], native.hg_backward_workspace_bytes(net, h, w, len(prefixes) > 1),
+                              lambda tape, g, **kw: native.hg_backward(net, handle, prefixes, params, tape, h, w, g[0], **kw))
 
     def conv_block_train(self, prefix, x):
         """ConvBlock `prefix` (image_filter_lr.conv2. / .top_m_{s}. / .m{s}.b1_{l}. ...; 'image_filter_lr.' may be left out) on x
@@ -484,34 +490,23 @@ class SuRSNet:
         (surs_encoder_convblock_train)."""
         return self._hg_train(prefix, x)
 
-    def conv_block_backward(self, prefix, grad_out):
+    def conv_block_backward(self, prefix, grad_out, tapes=None):
         """(d <grad_out, out> / d x [B,256,h,w], OrderedDict of the gradients of the block's nine parameters summed over the batch in
-        image order) from the tapes of the preceding conv_block_train(prefix, x)."""
-        return self._hg_backward(prefix, grad_out, "conv_block")
+        image order) from the tapes of the preceding conv_block_train(prefix, x), or from `tapes`: what an earlier one filed in
+        _tapes[the block's full prefix] (the model's own entry is neither read nor changed)."""
+        return self._hg_backward(prefix, grad_out, "conv_block", tapes)
 
     def hourglass_train(self, stack, x):
         """image_filter_lr.m{stack} on x [B,256,h,w] (h, w multiples of 2^hg_depth): encoder.hourglass's values, tapes kept
         (surs_encoder_hourglass_train)."""
         return self._hg_train(int(stack), x)
 
-    def hourglass_backward(self, stack, grad_out):
+    def hourglass_backward(self, stack, grad_out, tapes=None):
         """(d <grad_out, out> / d x, OrderedDict of the gradients of every parameter of m{stack}, blocks in module order) from the
-        tapes of the preceding hourglass_train(stack, x)."""
-        return self._hg_backward(int(stack), grad_out, "hourglass")
+        tapes of the preceding hourglass_train(stack, x), or from `tapes`: what an earlier one filed in _tapes[stack]."""
+        return self._hg_backward(int(stack), grad_out, "hourglass", tapes)
 
     # ------------------------------------------------------------------ stack-tail gradients, and the whole low-resolution filter
-    def _hg_workspace(self, need, dev):
-        if self._hg_ws is None or self._hg_ws.numel() < need or self._hg_ws.device != dev:
-            self._hg_ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        return self._hg_ws
-
-    def _nhwc(self, g, shape, name):
-        if g is None:
-            return None
-        if tuple(g.shape) != shape:
-            raise ValueError("%s %s against the output's %s" % (name, tuple(g.shape), shape))
-        return g.detach().to(self._device(), torch.float32).permute(0, 2, 3, 1).contiguous()
-
     def stack_tail_train(self, stack, ll, previous=None):
         """The tail of stack `stack` - conv_last -> bn_end -> ReLU -> l, and next = previous + bl(.) + al(l(.)) on the merged next{s} -
         on ll [B,256,h,w] and, for every stack but the last, previous [B,256,h,w]: filter_lr()'s launches and bits, tapes kept
@@ -525,46 +520,28 @@ class SuRSNet:
         if ll.dim() != 4 or ll.shape[1] != 256 or (previous is not None and tuple(previous.shape) != tuple(ll.shape)):
             raise ValueError("[B,256,h,w] tensors of one shape are expected, not %s" % (tuple(ll.shape),))
         net = self._hg_native()
-        dev = self._device()
-        outs, nexts, tapes = [], [], []
-        for b in range(ll.shape[0]):
-            prev = None if previous is None else _as_img(previous[b:b + 1].detach().to(dev, torch.float32))
-            out, nxt, tape = native.tail_train_forward(net, stack, _as_img(ll[b:b + 1].detach().to(dev, torch.float32)), prev)
-            outs.append(_as_nchw_view(out))
-            nexts.append(None if nxt is None else _as_nchw_view(nxt))
-            tapes.append(tape)
-        self._hg_tapes[("tail", stack)] = (ll.shape[2], ll.shape[3], tapes)
-        cat = lambda v: torch.cat(v, 0) if len(v) > 1 else v[0]
-        return cat(outs), (None if previous is None else cat(nexts))
+        outs = self._train(("tail", stack), lambda l, p: native.tail_train_forward(net, stack, l, p), ll, previous)
+        return _cat_views([o[0] for o in outs]), (None if previous is None else _cat_views([o[1] for o in outs]))
 
-    def stack_tail_backward(self, stack, grad_out=None, grad_next=None):
+    def stack_tail_backward(self, stack, grad_out=None, grad_next=None, tapes=None):
         """(d L / d ll, d L / d previous - grad_next itself; None for the last stack or without grad_next -, OrderedDict of the gradients
         of conv_last{s}, bn_end{s}, l{s} and, for a stack that is not the last, bl{s}, al{s} (.weight, .bias each; the UN-MERGED
         parameters), summed over the batch in image order) for L = <grad_out, out> + <grad_next, next>, from the tapes of the preceding
-        stack_tail_train(stack, ...).  Either gradient may be None (zero), not both."""
+        stack_tail_train(stack, ...), or from `tapes`: what an earlier one filed in _tapes[("tail", stack)].  Either gradient may be
+        None (zero), not both."""
         self._hg_check_norm()
         stack = int(stack)
         if grad_out is None and grad_next is None:
             raise RuntimeError("stack_tail_backward: no upstream gradient (both are None)")
         if grad_next is not None and stack == self.opt.num_stack_lr - 1:
             raise RuntimeError("stack_tail_backward: the last stack has no next")
-        kept = self._hg_tapes.get(("tail", stack))
-        if kept is None:
-            raise RuntimeError("stack_tail_backward needs a preceding stack_tail_train() of the same stack: the tape of the forward's "
-                               "maps is missing")
+        h, w, tapes = self._kept_tapes(("tail", stack), tapes, "stack_tail", " of the same stack")
         net = self._hg_native()
-        h, w, tapes = kept
-        dev, B = self._device(), len(tapes)
-        go = self._nhwc(grad_out, (B, net.l[stack].cout, h, w), "grad_out")
-        gn = self._nhwc(grad_next, (B, 256, h, w), "grad_next")
-        params = self._hg_param_set()[0].tensors
-        ws = self._hg_workspace(native.tail_backward_workspace_bytes(net, h, w), dev)
-        grads, dls = None, []
-        for b in range(B):
-            dl, grads = native.tail_backward(net, stack, params, tapes[b], h, w, None if go is None else go[b], None if gn is None else gn[b],
-                                             grads=grads, accumulate=b > 0, workspace=ws)
-            dls.append(dl)
-        return torch.stack(dls, 0).permute(0, 3, 1, 2), grad_next, grads
+        params = self._param_set("hg")[0].tensors
+        d_ll, grads = self._backward(tapes, [("grad_out", grad_out, (net.l[stack].cout, h, w)), ("grad_next", grad_next, (256, h, w))],
+                                     native.tail_backward_workspace_bytes(net, h, w),
+                                     lambda tape, g, **kw: native.tail_backward(net, stack, params, tape, h, w, *g, **kw))
+        return d_ll, grad_next, grads
 
     def filter_lr_train(self, feature_lr):
         """HGFilter.forward on feature_lr [B,256,h,w] with every map the backward reads kept, one tape per image
@@ -573,40 +550,26 @@ class SuRSNet:
         if feature_lr.dim() != 4 or feature_lr.shape[1] != 256:
             raise ValueError("a [B,256,h,w] tensor is expected, not %s" % (tuple(feature_lr.shape),))
         net = self._hg_native()
-        dev = self._device()
-        per, tapes = [], []
-        for b in range(feature_lr.shape[0]):
-            outs, tape = native.filter_lr_train_forward(net, _as_img(feature_lr[b:b + 1].detach().to(dev, torch.float32)))
-            per.append([_as_nchw_view(o) for o in outs])
-            tapes.append(tape)
-        self._hg_tapes["filter_lr"] = (feature_lr.shape[2], feature_lr.shape[3], tapes)
-        return [torch.cat([pv[s] for pv in per], 0) if len(per) > 1 else per[0][s] for s in range(len(per[0]))]
+        outs = self._train("filter_lr", lambda x: native.filter_lr_train_forward(net, x), feature_lr)
+        return [_cat_views([o[0][s] for o in outs]) for s in range(len(outs[0][0]))]
 
-    def filter_lr_backward(self, grad_outs):
+    def filter_lr_backward(self, grad_outs, tapes=None):
         """(d L / d feature_lr, OrderedDict over hg_parameters()'s keys) for L = sum_s <grad_outs[s], outs[s]> from the tapes of the
-        preceding filter_lr_train(): grad_outs holds one [B,hg_dim,h,w] tensor or None (zero) per stack, not all None.  Summed over
-        the batch in image order; the parameters of a stack no gradient reaches get zeros."""
+        preceding filter_lr_train(), or from `tapes`: what an earlier one filed in _tapes["filter_lr"].  grad_outs holds one
+        [B,hg_dim,h,w] tensor or None (zero) per stack, not all None.  Summed over the batch in image order; the parameters of a stack
+        no gradient reaches get zeros."""
         self._hg_check_norm()
         S = self.opt.num_stack_lr
         if len(grad_outs) != S:
             raise ValueError("one gradient (or None) per stack: %d for %d stacks" % (len(grad_outs), S))
         if all(g is None for g in grad_outs):
             raise RuntimeError("filter_lr_backward: no upstream gradient (all are None)")
-        kept = self._hg_tapes.get("filter_lr")
-        if kept is None:
-            raise RuntimeError("filter_lr_backward needs a preceding filter_lr_train(): the tape of the forward's maps is missing")
+        h, w, tapes = self._kept_tapes("filter_lr", tapes, "filter_lr")
         net = self._hg_native()
-        h, w, tapes = kept
-        dev, B = self._device(), len(tapes)
-        gs = [self._nhwc(g, (B, net.l[s].cout, h, w), "grad_outs[%d]" % s) for s, g in enumerate(grad_outs)]
-        hp = self._hg_param_set()[0]
-        ws = self._hg_workspace(native.filter_lr_backward_workspace_bytes(net, h, w), dev)
-        grads, dxs = None, []
-        for b in range(B):
-            dx, grads = native.filter_lr_backward(net, self.opt.hg_depth, hp.keys, hp.tensors, tapes[b], h, w,
-                                                  [None if g is None else g[b] for g in gs], grads=grads, accumulate=b > 0, workspace=ws)
-            dxs.append(dx)
-        return torch.stack(dxs, 0).permute(0, 3, 1, 2), grads
+        hp = self._param_set("hg")[0]
+        return self._backward(tapes, [("grad_outs[%d]" % s, g, (net.l[s].cout, h, w)) for s, g in enumerate(grad_outs)],
+                              native.filter_lr_backward_workspace_bytes(net, h, w),
+                              lambda tape, g, **kw: native.filter_lr_backward(net, self.opt.hg_depth, hp.keys, hp.tensors, tape, h, w, g, **kw))
 
     def reencode_wide(self):
         """Runs the encoder again on the images of the last super_res() call with every fp32-grade product on three bf16 parts
@@ -1078,12 +1041,7 @@ class SuRSNet:
     _GRADS_LIMIT = ("classifier gradients (forward_backward(), classifier_grads()): num_views == 1 and orthogonal projection only")
 
     def _mlp_params(self):
-        if self._grad_params is None:
-            self._write_back()
-            sd = {k: v for k, v in self._sd.items() if k.startswith("mlp_")}
-            shapes = native.mlp_shapes({k: v.numpy() for k, v in sd.items()}, self.opt)
-            self._grad_params = native.MlpParams(sd, self._device(), shapes)
-        return self._grad_params
+        return self._param_set("mlp")[0]
 
     def classifier_grads(self, features=False):
         """d error / d (every mlp_lr.* and mlp_hr.* parameter) of forward()'s loss - opt.mlp1 get_error_lr() + opt.mlp2 get_error_hr()

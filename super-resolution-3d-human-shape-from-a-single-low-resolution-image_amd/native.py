@@ -1019,18 +1019,25 @@ def mlp_param_keys(shapes):
             for kind in ("weight", "bias")]
 
 
+def _f32_tensors(sd, keys, device):
+    """OrderedDict key -> sd[key] (a tensor or an array) as a contiguous float32 tensor on `device`, in `keys`' order: the masters of
+    MlpParams, SrParams and HgParams."""
+    out = OrderedDict()
+    for k in keys:
+        v = sd[k]
+        v = v.detach() if torch.is_tensor(v) else torch.from_numpy(np.asarray(v, np.float32))
+        out[k] = v.to(device, torch.float32).contiguous()
+    return out
+
+
 class MlpParams:
     """The plain fp32 Conv1d weights [out,in] and biases [out] of a classifier pair on the device: what surs_mlp_grad reads."""
 
     def __init__(self, sd, device, shapes=None):
         self.shapes = mlp_shapes(sd) if shapes is None else shapes
         self.lr, self.hr = (_shape_struct(*s) for s in self.shapes)
-        self.tensors = OrderedDict()
-        for k in mlp_param_keys(self.shapes):
-            v = sd[k]
-            v = v.detach() if torch.is_tensor(v) else torch.from_numpy(np.asarray(v, np.float32))
-            v = v.to(device, torch.float32)
-            self.tensors[k] = (v.reshape(v.shape[0], -1) if k.endswith("weight") else v.reshape(-1)).contiguous()
+        self.tensors = OrderedDict((k, v.reshape(v.shape[0], -1) if k.endswith("weight") else v.reshape(-1))
+                                   for k, v in _f32_tensors(sd, mlp_param_keys(self.shapes), device).items())
         for m, p in enumerate(("mlp_lr.", "mlp_hr.")):
             dims, res = self.shapes[m]
             for l in range(len(dims) - 1):
@@ -1288,11 +1295,7 @@ class SrParams:
     def __init__(self, sd, n_block, device):
         self.n_block = [int(v) for v in n_block]
         self.keys = sr_param_keys(sd, self.n_block)
-        self.tensors = OrderedDict()
-        for k in self.keys:
-            v = sd[k]
-            v = v.detach() if torch.is_tensor(v) else torch.from_numpy(np.asarray(v, np.float32))
-            self.tensors[k] = v.to(device, torch.float32).contiguous()
+        self.tensors = _f32_tensors(sd, self.keys, device)
         want = 2 * (len(sr_conv_names(self.n_block)) + 1)
         if len(self.keys) != want:
             raise ValueError("the state dict holds %d of the %d super-resolution / conv5 parameters" % (len(self.keys), want))
@@ -1317,21 +1320,60 @@ class SrParams:
         return s, body
 
 
-def _sr_size(fn, what, net, h, w):
-    n = fn(C.byref(net), h, w)
+# the checks the taped train forwards and their backwards below share (super-resolution, ConvBlock / HourGlass, stack tail, filter_lr)
+
+def _size(what, net, h, w):
+    """The library's size query `what` - a tape's or a backward workspace's bytes - for an h x w input of _lib.EncoderNet `net`."""
+    n = getattr(lib(), what)(C.byref(net), h, w)
     if n == 0:
-        raise ValueError("%s refused a %dx%d image: %s" % (what, h, w, lib().surs_last_error().decode()))
+        raise ValueError("%s refused a %dx%d input: %s" % (what, h, w, lib().surs_last_error().decode()))
     return n
+
+
+def _nbytes(t):
+    return t.numel() * t.element_size()
+
+
+def _buffer(t, need, dev, what, aligned=True):
+    """The tape or workspace `t` if it holds `need` bytes on `dev` (256-byte aligned, unless the call aligns it itself); None: a new one."""
+    if t is None:
+        return torch.empty(need, dtype=torch.uint8, device=dev)
+    if _nbytes(t) < need or t.device != dev or (aligned and t.data_ptr() % 256):
+        raise ValueError("%s: %d bytes needed on %s%s" % (what, need, dev, ", 256-byte aligned" if aligned else ""))
+    return t
+
+
+def _check_grads(grads, keys, params, dev, accumulate):
+    """`grads` if it holds a contiguous float32 tensor of params[k]'s shape on `dev` for every k of `keys`; None: a new OrderedDict."""
+    if accumulate and grads is None:
+        raise ValueError("accumulate needs the grads to add to")
+    if grads is None:
+        return OrderedDict((k, torch.empty_like(params[k])) for k in keys)
+    for k in keys:
+        if k not in grads or tuple(grads[k].shape) != tuple(params[k].shape) or grads[k].dtype != torch.float32 \
+                or not grads[k].is_contiguous() or grads[k].device != dev:
+            raise ValueError("grads[%r] must be a contiguous float32 tensor %s on %s" % (k, tuple(params[k].shape), dev))
+    return grads
+
+
+def _check_g(g, shape, dev, name):
+    """The upstream gradient `g` if it is None or a contiguous float32 NHWC tensor of `shape` on `dev`."""
+    if g is None:
+        return None
+    if tuple(g.shape[-3:]) != shape or g.numel() != shape[0] * shape[1] * shape[2] or g.dtype != torch.float32 or not g.is_contiguous() \
+            or g.device != dev:
+        raise ValueError("%s must be a contiguous float32 NHWC tensor %s on %s, not %s" % (name, shape, dev, tuple(g.shape)))
+    return g
 
 
 def sr_tape_bytes(net, h, w):
     """surs_encoder_sr_tape_bytes: the tape of sr_train_forward for an h x w input image (net: _lib.EncoderNet)."""
-    return _sr_size(lib().surs_encoder_sr_tape_bytes, "surs_encoder_sr_tape_bytes", net, h, w)
+    return _size("surs_encoder_sr_tape_bytes", net, h, w)
 
 
 def sr_backward_workspace_bytes(net, h, w):
     """surs_encoder_sr_backward_workspace_bytes."""
-    return _sr_size(lib().surs_encoder_sr_backward_workspace_bytes, "surs_encoder_sr_backward_workspace_bytes", net, h, w)
+    return _size("surs_encoder_sr_backward_workspace_bytes", net, h, w)
 
 
 def sr_scale(net):
@@ -1344,18 +1386,14 @@ def sr_train_forward(net, x, scale=None, tape=None):
     (a uint8 / float32 device tensor of sr_tape_bytes, 256-byte aligned; None: a new one).  Returns (img_sr, feature_lr, feature_hr,
     im_feat_hr, tape) - the four as Img, bit for bit those of the two calls."""
     dev = x.buf.device
-    need = sr_tape_bytes(net, x.h, x.w)
-    if tape is None:
-        tape = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif tape.numel() * tape.element_size() < need or tape.device != dev:
-        raise ValueError("tape: %d bytes needed on %s" % (need, dev))
+    tape = _buffer(tape, sr_tape_bytes(net, x.h, x.w), dev, "tape")
     if scale not in (None, sr_scale(net)):
         raise ValueError("scale %r against the net's %d" % (scale, sr_scale(net)))
     H2, W2 = sr_scale(net) * x.h, sr_scale(net) * x.w
     img_sr, f_lr, f_hr = Img(H2, W2, 3, device=dev), Img(H2 // 4, W2 // 4, 256, device=dev), Img(H2, W2, 64, device=dev)
     im_hr = Img(H2, W2, net.conv5.cout, device=dev)
     check(lib().surs_encoder_super_res_train(C.byref(net), x.ptr(), x.h, x.w, x.ld, img_sr.ptr(), f_lr.ptr(), f_hr.ptr(), im_hr.ptr(),
-                                             _ptr(tape), tape.numel() * tape.element_size(), _stream()))
+                                             _ptr(tape), _nbytes(tape), _stream()))
     return img_sr, f_lr, f_hr, im_hr, tape
 
 
@@ -1366,35 +1404,20 @@ def sr_backward(net, params, tape, h, w, g_img_sr=None, g_feature_lr=None, g_im_
     g_*: contiguous float32 NHWC device tensors of the outputs' shapes, or None (zero).  grads: an OrderedDict as returned, to
     overwrite or (accumulate) add to; None: a new one.  Returns grads: params.keys in order, tensors of the parameters' shapes."""
     dev = tape.device
-    if accumulate and grads is None:
-        raise ValueError("accumulate needs the grads to add to")
-    if grads is None:
-        grads = OrderedDict((k, torch.empty_like(v)) for k, v in params.tensors.items())
-    else:
-        for k, v in params.tensors.items():
-            if k not in grads or tuple(grads[k].shape) != tuple(v.shape) or grads[k].dtype != torch.float32 \
-                    or not grads[k].is_contiguous() or grads[k].device != dev:
-                raise ValueError("grads[%r] must be a contiguous float32 tensor %s on %s" % (k, tuple(v.shape), dev))
+    grads = _check_grads(grads, params.keys, params.tensors, dev, accumulate)
     if scale not in (None, sr_scale(net)):
         raise ValueError("scale %r against the net's %d" % (scale, sr_scale(net)))
     H2, W2 = sr_scale(net) * h, sr_scale(net) * w
-    for name, g, shape in (("g_img_sr", g_img_sr, (H2, W2, 3)), ("g_feature_lr", g_feature_lr, (H2 // 4, W2 // 4, 256)),
-                           ("g_im_feat_hr", g_im_feat_hr, (H2, W2, net.conv5.cout))):
-        if g is not None and (tuple(g.shape[-3:]) != shape or g.numel() != shape[0] * shape[1] * shape[2] or g.dtype != torch.float32
-                              or not g.is_contiguous() or g.device != dev):
-            raise ValueError("%s must be a contiguous float32 NHWC tensor %s on %s, not %s" % (name, shape, dev, tuple(g.shape)))
-    if tape.numel() * tape.element_size() < sr_tape_bytes(net, h, w):
-        raise ValueError("tape: %d bytes needed for a %dx%d image" % (sr_tape_bytes(net, h, w), h, w))
-    need = sr_backward_workspace_bytes(net, h, w)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif workspace.numel() * workspace.element_size() < need or workspace.device != dev:
-        raise ValueError("workspace: %d bytes needed on %s" % (need, dev))
+    g_img_sr = _check_g(g_img_sr, (H2, W2, 3), dev, "g_img_sr")
+    g_feature_lr = _check_g(g_feature_lr, (H2 // 4, W2 // 4, 256), dev, "g_feature_lr")
+    g_im_feat_hr = _check_g(g_im_feat_hr, (H2, W2, net.conv5.cout), dev, "g_im_feat_hr")
+    tape = _buffer(tape, sr_tape_bytes(net, h, w), dev, "tape")
+    workspace = _buffer(workspace, sr_backward_workspace_bytes(net, h, w), dev, "workspace", aligned=False)   # (the library aligns it)
     ps, keep_p = params.struct()
     gs, keep_g = params.struct(grads)
     check(lib().surs_encoder_super_res_backward(C.byref(net), C.byref(ps), _ptr(tape), h, w, _ptr(g_img_sr), _ptr(g_feature_lr),
                                                 _ptr(g_im_feat_hr), C.byref(gs), 1 if accumulate else 0, _ptr(workspace),
-                                                workspace.numel() * workspace.element_size(), _stream()))
+                                                _nbytes(workspace), _stream()))
     del keep_p, keep_g
     return grads
 
@@ -1514,11 +1537,7 @@ class HgParams:
     def __init__(self, sd, num_stack, depth, device):
         self.num_stack, self.depth = int(num_stack), int(depth)
         self.keys = hg_param_keys(sd, self.num_stack, self.depth)
-        self.tensors = OrderedDict()
-        for k in self.keys:
-            v = sd[k]
-            v = v.detach() if torch.is_tensor(v) else torch.from_numpy(np.asarray(v, np.float32))
-            self.tensors[k] = v.to(device, torch.float32).contiguous()
+        self.tensors = _f32_tensors(sd, self.keys, device)
 
     @staticmethod
     def struct(prefixes, tensors):
@@ -1546,30 +1565,13 @@ def hg_block_of(net, prefix, depth):
     raise ValueError("%r is no ConvBlock of image_filter_lr" % (prefix,))
 
 
-def _hg_size(what, net, h, w):
-    n = getattr(lib(), what)(C.byref(net), h, w)
-    if n == 0:
-        raise ValueError("%s refused a %dx%d map: %s" % (what, h, w, lib().surs_last_error().decode()))
-    return n
-
-
 def hg_tape_bytes(net, h, w, hourglass):
     """surs_encoder_hourglass_tape_bytes / surs_encoder_convblock_tape_bytes."""
-    what = "surs_encoder_%s_tape_bytes" % ("hourglass" if hourglass else "convblock")
-    return _hg_size(what, net, h, w)
+    return _size("surs_encoder_%s_tape_bytes" % ("hourglass" if hourglass else "convblock"), net, h, w)
 
 
 def hg_backward_workspace_bytes(net, h, w, hourglass):
-    what = "surs_encoder_%s_backward_workspace_bytes" % ("hourglass" if hourglass else "convblock")
-    return _hg_size(what, net, h, w)
-
-
-def _hg_buffer(t, need, dev, what):
-    if t is None:
-        return torch.empty(need, dtype=torch.uint8, device=dev)
-    if t.numel() * t.element_size() < need or t.device != dev or t.data_ptr() % 256:
-        raise ValueError("%s: %d bytes needed on %s, 256-byte aligned" % (what, need, dev))
-    return t
+    return _size("surs_encoder_%s_backward_workspace_bytes" % ("hourglass" if hourglass else "convblock"), net, h, w)
 
 
 def hg_train_forward(net, which, x, tape=None):
@@ -1579,9 +1581,9 @@ def hg_train_forward(net, which, x, tape=None):
     hourglass = isinstance(which, int)
     if x.c != 256:
         raise ValueError("a map of 256 channels is expected, not %d" % x.c)
-    tape = _hg_buffer(tape, hg_tape_bytes(net, x.h, x.w, hourglass), dev, "tape")
+    tape = _buffer(tape, hg_tape_bytes(net, x.h, x.w, hourglass), dev, "tape")
     out = Img(x.h, x.w, 256, device=dev)
-    tb = tape.numel() * tape.element_size()
+    tb = _nbytes(tape)
     if hourglass:
         check(lib().surs_encoder_hourglass_train(C.byref(net), which, x.ptr(), x.h, x.w, x.ld, out.ptr(), _ptr(tape), tb, _stream()))
     else:
@@ -1597,23 +1599,15 @@ def hg_backward(net, which, prefixes, params, tape, h, w, g, grads=None, accumul
     dev = tape.device
     hourglass = isinstance(which, int)
     keys = [k for p in prefixes for k in hg_block_keys(p)]
-    if accumulate and grads is None:
-        raise ValueError("accumulate needs the grads to add to")
-    if grads is None:
-        grads = OrderedDict((k, torch.empty_like(params[k])) for k in keys)
-    else:
-        for k in keys:
-            if k not in grads or tuple(grads[k].shape) != tuple(params[k].shape) or grads[k].dtype != torch.float32 \
-                    or not grads[k].is_contiguous() or grads[k].device != dev:
-                raise ValueError("grads[%r] must be a contiguous float32 tensor %s on %s" % (k, tuple(params[k].shape), dev))
-    if tuple(g.shape[-3:]) != (h, w, 256) or g.numel() != h * w * 256 or g.dtype != torch.float32 or not g.is_contiguous() or g.device != dev:
-        raise ValueError("g must be a contiguous float32 NHWC tensor %s on %s, not %s" % ((h, w, 256), dev, tuple(g.shape)))
-    if tape.numel() * tape.element_size() < hg_tape_bytes(net, h, w, hourglass):
-        raise ValueError("tape: %d bytes needed for a %dx%d map" % (hg_tape_bytes(net, h, w, hourglass), h, w))
-    workspace = _hg_buffer(workspace, hg_backward_workspace_bytes(net, h, w, hourglass), dev, "workspace")
+    grads = _check_grads(grads, keys, params, dev, accumulate)
+    if g is None:
+        raise ValueError("hg_backward: the gradient is None")
+    g = _check_g(g, (h, w, 256), dev, "g")
+    tape = _buffer(tape, hg_tape_bytes(net, h, w, hourglass), dev, "tape")
+    workspace = _buffer(workspace, hg_backward_workspace_bytes(net, h, w, hourglass), dev, "workspace")
     ps, gs = HgParams.struct(prefixes, params), HgParams.struct(prefixes, grads)
     dx = torch.empty((h, w, 256), dtype=torch.float32, device=dev)
-    wb = workspace.numel() * workspace.element_size()
+    wb = _nbytes(workspace)
     if hourglass:
         check(lib().surs_encoder_hourglass_backward(C.byref(net), which, ps, _ptr(tape), h, w, _ptr(g), _ptr(dx), gs, 1 if accumulate else 0,
                                                     _ptr(workspace), wb, _stream()))
@@ -1684,40 +1678,19 @@ def hg_filter_struct(num_stack, depth, tensors):
 
 
 def tail_tape_bytes(net, h, w):
-    return _hg_size("surs_encoder_tail_tape_bytes", net, h, w)
+    return _size("surs_encoder_tail_tape_bytes", net, h, w)
 
 
 def tail_backward_workspace_bytes(net, h, w):
-    return _hg_size("surs_encoder_tail_backward_workspace_bytes", net, h, w)
+    return _size("surs_encoder_tail_backward_workspace_bytes", net, h, w)
 
 
 def filter_lr_tape_bytes(net, h, w):
-    return _hg_size("surs_encoder_filter_lr_tape_bytes", net, h, w)
+    return _size("surs_encoder_filter_lr_tape_bytes", net, h, w)
 
 
 def filter_lr_backward_workspace_bytes(net, h, w):
-    return _hg_size("surs_encoder_filter_lr_backward_workspace_bytes", net, h, w)
-
-
-def _check_grads(grads, keys, params, dev, accumulate):
-    if accumulate and grads is None:
-        raise ValueError("accumulate needs the grads to add to")
-    if grads is None:
-        return OrderedDict((k, torch.empty_like(params[k])) for k in keys)
-    for k in keys:
-        if k not in grads or tuple(grads[k].shape) != tuple(params[k].shape) or grads[k].dtype != torch.float32 \
-                or not grads[k].is_contiguous() or grads[k].device != dev:
-            raise ValueError("grads[%r] must be a contiguous float32 tensor %s on %s" % (k, tuple(params[k].shape), dev))
-    return grads
-
-
-def _check_g(g, shape, dev, name):
-    if g is None:
-        return None
-    if tuple(g.shape[-3:]) != shape or g.numel() != shape[0] * shape[1] * shape[2] or g.dtype != torch.float32 or not g.is_contiguous() \
-            or g.device != dev:
-        raise ValueError("%s must be a contiguous float32 NHWC tensor %s on %s, not %s" % (name, shape, dev, tuple(g.shape)))
-    return g
+    return _size("surs_encoder_filter_lr_backward_workspace_bytes", net, h, w)
 
 
 def tail_train_forward(net, stack, ll, previous=None, tape=None):
@@ -1728,12 +1701,11 @@ def tail_train_forward(net, stack, ll, previous=None, tape=None):
         raise ValueError("maps of 256 channels and one size are expected")
     if last != (previous is None):
         raise ValueError("previous goes with every stack but the last (stack %d of %d)" % (stack, net.num_stack))
-    tape = _hg_buffer(tape, tail_tape_bytes(net, ll.h, ll.w), dev, "tape")
+    tape = _buffer(tape, tail_tape_bytes(net, ll.h, ll.w), dev, "tape")
     out = Img(ll.h, ll.w, net.l[stack].cout, device=dev)
     nxt = None if last else Img(ll.h, ll.w, 256, device=dev)
     check(lib().surs_encoder_tail_train(C.byref(net), stack, ll.ptr(), ll.ld, None if last else previous.ptr(), 0 if last else previous.ld,
-                                        ll.h, ll.w, out.ptr(), None if last else nxt.ptr(), _ptr(tape), tape.numel() * tape.element_size(),
-                                        _stream()))
+                                        ll.h, ll.w, out.ptr(), None if last else nxt.ptr(), _ptr(tape), _nbytes(tape), _stream()))
     return out, nxt, tape
 
 
@@ -1747,14 +1719,12 @@ def tail_backward(net, stack, params, tape, h, w, g_out=None, g_next=None, grads
     g_next = _check_g(g_next, (h, w, 256), dev, "g_next")
     if g_out is None and g_next is None:
         raise ValueError("tail_backward: both gradients are None")
-    if tape.numel() * tape.element_size() < tail_tape_bytes(net, h, w):
-        raise ValueError("tape: %d bytes needed for a %dx%d map" % (tail_tape_bytes(net, h, w), h, w))
-    workspace = _hg_buffer(workspace, tail_backward_workspace_bytes(net, h, w), dev, "workspace")
+    tape = _buffer(tape, tail_tape_bytes(net, h, w), dev, "tape")
+    workspace = _buffer(workspace, tail_backward_workspace_bytes(net, h, w), dev, "workspace")
     ps, gs = hg_tail_struct(stack, S, params), hg_tail_struct(stack, S, grads)
     d_ll = torch.empty((h, w, 256), dtype=torch.float32, device=dev)
     check(lib().surs_encoder_tail_backward(C.byref(net), stack, C.byref(ps), _ptr(tape), h, w, _ptr(g_out), _ptr(g_next), _ptr(d_ll),
-                                           C.byref(gs), 1 if accumulate else 0, _ptr(workspace),
-                                           workspace.numel() * workspace.element_size(), _stream()))
+                                           C.byref(gs), 1 if accumulate else 0, _ptr(workspace), _nbytes(workspace), _stream()))
     return d_ll, grads
 
 
@@ -1763,11 +1733,10 @@ def filter_lr_train_forward(net, x, tape=None):
     dev, S = x.buf.device, net.num_stack
     if x.c != 256:
         raise ValueError("a map of 256 channels is expected, not %d" % x.c)
-    tape = _hg_buffer(tape, filter_lr_tape_bytes(net, x.h, x.w), dev, "tape")
+    tape = _buffer(tape, filter_lr_tape_bytes(net, x.h, x.w), dev, "tape")
     outs = [Img(x.h, x.w, net.l[s].cout, device=dev) for s in range(S)]
     ptrs = (C.c_void_p * S)(*[o.ptr() for o in outs])
-    check(lib().surs_encoder_filter_lr_train(C.byref(net), x.ptr(), x.h, x.w, x.ld, ptrs, _ptr(tape), tape.numel() * tape.element_size(),
-                                             _stream()))
+    check(lib().surs_encoder_filter_lr_train(C.byref(net), x.ptr(), x.h, x.w, x.ld, ptrs, _ptr(tape), _nbytes(tape), _stream()))
     return outs, tape
 
 
@@ -1782,15 +1751,13 @@ def filter_lr_backward(net, depth, keys, params, tape, h, w, g_outs, grads=None,
     g_outs = [_check_g(g, (h, w, net.l[s].cout), dev, "g_outs[%d]" % s) for s, g in enumerate(g_outs)]
     if all(g is None for g in g_outs):
         raise ValueError("filter_lr_backward: every gradient is None")
-    if tape.numel() * tape.element_size() < filter_lr_tape_bytes(net, h, w):
-        raise ValueError("tape: %d bytes needed for a %dx%d map" % (filter_lr_tape_bytes(net, h, w), h, w))
-    workspace = _hg_buffer(workspace, filter_lr_backward_workspace_bytes(net, h, w), dev, "workspace")
+    tape = _buffer(tape, filter_lr_tape_bytes(net, h, w), dev, "tape")
+    workspace = _buffer(workspace, filter_lr_backward_workspace_bytes(net, h, w), dev, "workspace")
     (ps, keep_p), (gs, keep_g) = hg_filter_struct(S, depth, params), hg_filter_struct(S, depth, grads)
     ptrs = (C.c_void_p * S)(*[None if g is None else g.data_ptr() for g in g_outs])
     dx = torch.empty((h, w, 256), dtype=torch.float32, device=dev)
     check(lib().surs_encoder_filter_lr_backward(C.byref(net), C.byref(ps), _ptr(tape), h, w, ptrs, _ptr(dx), C.byref(gs),
-                                                1 if accumulate else 0, _ptr(workspace), workspace.numel() * workspace.element_size(),
-                                                _stream()))
+                                                1 if accumulate else 0, _ptr(workspace), _nbytes(workspace), _stream()))
     del keep_p, keep_g
     return dx, grads
 

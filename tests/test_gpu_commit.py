@@ -276,7 +276,7 @@ def test_to_writes_the_committed_values_back():
     net.commit()
     want = {k: p.detach().cpu().reshape(_sd0()[k].shape).clone() for k, p in masters.items()}
     net.to(g.dev())
-    assert net._grad_params is None and net._sr_params is None
+    assert not net._masters()
     sd = net.state_dict()
     for k, v in sd.items():
         assert torch.equal(v, want[k] if k in want else _sd0()[k]), k
@@ -295,7 +295,7 @@ def test_partial_load_after_commit_keeps_the_committed_values():
     net.commit()
     want = _as_state_dict(sd0, {k: p for k, p in masters.items() if not k.startswith("mlp_")})
     net.load_state_dict(OrderedDict((k, v) for k, v in sd0.items() if k.startswith("mlp_")), strict=False)
-    assert net._stale == set() and net._sr_params is None and net._hg_params is None
+    assert net._stale == set() and not net._masters()
     sd = net.state_dict()
     for k, v in sd.items():
         assert torch.equal(v, want[k]), k

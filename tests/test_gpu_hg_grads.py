@@ -425,6 +425,59 @@ def test_autograd_functions(golden_dir):
     assert torch.equal(got[0], dx) and all(torch.equal(g, grads[k]) for k, g in zip(grads, got[1:]))
 
 
+def _fresh(c):
+    from surs_amd import model
+    net = model.SuRSNet(c.opt).to(device=_dev())
+    net.load_state_dict(hg.state_dict(c.name))
+    return net
+
+
+def test_autograd_backward_leaves_the_models_tape_alone(golden_dir):
+    """The Function owns the tape of its forward: its backward, run after hourglass_train() on ONE other image has filed the model's own
+    latest tape, gives the first forward's gradients, and hourglass_backward() then gives what it gives on a fresh net after that
+    hourglass_train() alone - the model's tape, its key and its image count are as the train call left them."""
+    from surs_amd import autograd
+    c = _case(golden_dir, "hg_d1")
+    net, params = c.net, c.net.hg_parameters()
+    c.train()
+    want_dx, want = c.backward()
+    keys = list(want)
+    x = c.x.clone().requires_grad_()
+    out = autograd.hourglass(net, 0, x)
+    net.hourglass_train(0, c.x[:1] * 0.5)
+    kept, filed = net._tapes[0], set(net._tapes)
+    got = torch.autograd.grad((c.G * out).sum(), [x] + [params[k] for k in keys])
+    assert torch.equal(got[0], want_dx)
+    for k, g in zip(keys, got[1:]):
+        assert torch.equal(g, want[k]), k
+    assert net._tapes[0] is kept and len(kept[2]) == 1 and set(net._tapes) == filed
+    dx, grads = net.hourglass_backward(0, c.G[:1])
+    fresh = _fresh(c)
+    fresh.hourglass_train(0, c.x[:1] * 0.5)
+    fresh_dx, fresh_grads = fresh.hourglass_backward(0, c.G[:1])
+    assert torch.equal(dx, fresh_dx) and list(grads) == list(fresh_grads)
+    for k in grads:
+        assert torch.equal(grads[k], fresh_grads[k]), k
+
+
+def test_explicit_tapes_serve_their_own_forward(golden_dir):
+    """conv_block_backward(tapes=): the tapes of a first forward, passed after the same block ran on another input, give the first
+    forward's backward bit for bit, and the model's own entry is neither used nor changed."""
+    c = _case(golden_dir, "hg_d1")
+    net, block = c.net, "m0.b2_plus_1"
+    net.conv_block_train(block, c.x)
+    first = net._tapes[hg.P + block + "."]
+    want_dx, want = net.conv_block_backward(block, c.G)
+    net.conv_block_train(block, c.x[:1] * 0.5)
+    latest = net._tapes[hg.P + block + "."]
+    assert latest is not first and len(first[2]) == c.B and len(latest[2]) == 1
+    dx, grads = net.conv_block_backward(block, c.G, tapes=first)
+    assert torch.equal(dx, want_dx) and list(grads) == list(want)
+    for k in grads:
+        assert torch.equal(grads[k], want[k]), k
+    assert net._tapes[hg.P + block + "."] is latest
+
+
 def test_composed_stack_against_the_reference(golden_dir):
     """stack1: conv2 -> m0 -> top_m_0 through the two autograd Functions, then conv_last0 / bn_end0 / ReLU / l0 in plain torch on
     hg_parameters() (1 x 1 convolutions as matrix products, GroupNorm from mean and variance): the hand-off to torch autograd and a

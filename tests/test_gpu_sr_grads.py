@@ -446,6 +446,32 @@ def test_autograd_function(golden_dir):
         assert torch.equal(g, w), k
 
 
+def test_autograd_backward_leaves_the_models_tape_alone(golden_dir):
+    """The Function owns the tape of its forward: its backward, run after super_res_train() on ONE other image has filed the model's own
+    latest tape, gives the first forward's gradients, and super_res_backward() then gives what it gives on a fresh net after that
+    super_res_train() alone - the model's tape and its image count are as the train call left them."""
+    from surs_amd import autograd, model
+    c = _case(golden_dir, "tiny")
+    net, params = c.net, c.net.sr_parameters()
+    net.super_res_train(c.x)
+    want = net.super_res_backward(*c.G)
+    outs = autograd.super_res_features(net, c.x)
+    net.super_res_train(c.x[:1] * 0.5)
+    kept, filed = net._tapes[net.SR_TAPES], set(net._tapes)
+    got = torch.autograd.grad(sum((g * o).sum() for g, o in zip(c.G, outs)), list(params.values()))
+    for (k, w), g in zip(want.items(), got):
+        assert torch.equal(g, w), k
+    assert net._tapes[net.SR_TAPES] is kept and len(kept[2]) == 1 and set(net._tapes) == filed
+    grads = net.super_res_backward(*[g[:1] for g in c.G])
+    fresh = model.SuRSNet(c.opt).to(device=_dev())
+    fresh.load_state_dict(sg.state_dict("tiny"))
+    fresh.super_res_train(c.x[:1] * 0.5)
+    fresh_grads = fresh.super_res_backward(*[g[:1] for g in c.G])
+    assert list(grads) == list(fresh_grads)
+    for k in grads:
+        assert torch.equal(grads[k], fresh_grads[k]), k
+
+
 def test_sgd_step_lowers_the_super_resolution_loss(golden_dir):
     """One SGD step on sr_parameters(), then load_state_dict: srweight * l1_loss(img_SR, images_hr) goes down on the same image (step
     0.01: the float64 restatement's loss falls from 0.5111 to 0.4897 with it); forward() still has no graph afterwards."""

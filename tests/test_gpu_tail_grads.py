@@ -359,6 +359,88 @@ def test_autograd_filter_lr_and_stack_tail(golden_dir):
     assert all(g is None for g in got)
 
 
+def _same_grads(got, want):
+    assert list(got) == list(want)
+    for k in got:
+        assert torch.equal(got[k], want[k]), k
+
+
+def test_autograd_backward_leaves_the_models_tape_alone(golden_dir):
+    """The Functions own the tapes of their forwards: a backward run after the model's *_train() on ONE other image has filed its own
+    latest tape gives the first forward's gradients, and the model's *_backward() then gives what it gives on a fresh net after that
+    *_train() alone - the model's tape, its key and its image count are as the train call left them."""
+    from surs_amd import autograd, model
+    # the stack tail
+    c = _case(golden_dir, "joint57")
+    net, p = c.net, c.net.hg_parameters()
+    net.stack_tail_train(0, c.ll, c.prev)
+    d_ll, d_prev, want = net.stack_tail_backward(0, c.g_out, c.g_next)
+    ll, prev = c.ll.clone().requires_grad_(), c.prev.clone().requires_grad_()
+    out, nxt = autograd.stack_tail(net, 0, ll, prev)
+    net.stack_tail_train(0, c.ll[:1] * 0.5, c.prev[:1])
+    kept, filed = net._tapes[("tail", 0)], set(net._tapes)
+    got = torch.autograd.grad((c.g_out * out).sum() + (c.g_next * nxt).sum(), [ll, prev] + [p[k] for k in want])
+    assert torch.equal(got[0], d_ll) and torch.equal(got[1], d_prev)
+    assert all(torch.equal(g, want[k]) for k, g in zip(want, got[2:]))
+    assert net._tapes[("tail", 0)] is kept and len(kept[2]) == 1 and set(net._tapes) == filed
+    one, _, grads = net.stack_tail_backward(0, c.g_out[:1], c.g_next[:1])
+    fresh = model.SuRSNet(c.opt).to(device=_dev())
+    fresh.load_state_dict(tg.state_dict("joint57"))
+    fresh.stack_tail_train(0, c.ll[:1] * 0.5, c.prev[:1])
+    fresh_one, _, fresh_grads = fresh.stack_tail_backward(0, c.g_out[:1], c.g_next[:1])
+    assert torch.equal(one, fresh_one)
+    _same_grads(grads, fresh_grads)
+    # the whole filter
+    f = _filter("s2d1")
+    net, p = f.net, f.net.hg_parameters()
+    G1 = [None if g is None else g[:1] for g in f.G]
+    x = f.x.clone().requires_grad_()
+    outs = autograd.filter_lr(net, x)
+    net.filter_lr_train(f.x[:1] * 0.5)
+    kept, filed = net._tapes["filter_lr"], set(net._tapes)
+    got = torch.autograd.grad(sum((g * o).sum() for g, o in zip(f.G, outs) if g is not None), [x] + list(p.values()))
+    assert torch.equal(got[0], f.dx)
+    assert all(torch.equal(g, f.grads[k]) for k, g in zip(p, got[1:]))
+    assert net._tapes["filter_lr"] is kept and len(kept[2]) == 1 and set(net._tapes) == filed
+    one, grads = net.filter_lr_backward(G1)
+    fresh = model.SuRSNet(f.opt).to(device=_dev())
+    fresh.load_state_dict(f.sd)
+    fresh.filter_lr_train(f.x[:1] * 0.5)
+    fresh_one, fresh_grads = fresh.filter_lr_backward(G1)
+    assert torch.equal(one, fresh_one)
+    _same_grads(grads, fresh_grads)
+    net.filter_lr_train(f.x)     # (the shared case's own tape again, for the tests that go back through it)
+
+
+def test_explicit_tapes_serve_their_own_forward(golden_dir):
+    """stack_tail_backward(tapes=) and filter_lr_backward(tapes=): the tapes of a first forward, passed after the same module ran on
+    another input, give the first forward's backward bit for bit, and the model's own entry is neither used nor changed."""
+    c = _case(golden_dir, "joint57")
+    net = c.net
+    net.stack_tail_train(0, c.ll, c.prev)
+    first = net._tapes[("tail", 0)]
+    d_ll, d_prev, want = net.stack_tail_backward(0, c.g_out, c.g_next)
+    net.stack_tail_train(0, c.ll[:1] * 0.5, c.prev[:1])
+    latest = net._tapes[("tail", 0)]
+    assert latest is not first and len(first[2]) == c.ll.shape[0] and len(latest[2]) == 1
+    got_ll, got_prev, grads = net.stack_tail_backward(0, c.g_out, c.g_next, tapes=first)
+    assert torch.equal(got_ll, d_ll) and torch.equal(got_prev, d_prev)
+    _same_grads(grads, want)
+    assert net._tapes[("tail", 0)] is latest
+    f = _filter("s2d1")
+    net = f.net
+    net.filter_lr_train(f.x)
+    first = net._tapes["filter_lr"]
+    net.filter_lr_train(f.x[:1] * 0.5)
+    latest = net._tapes["filter_lr"]
+    assert latest is not first and len(first[2]) == f.x.shape[0] and len(latest[2]) == 1
+    dx, grads = net.filter_lr_backward(f.G, tapes=first)
+    assert torch.equal(dx, f.dx)
+    _same_grads(grads, f.grads)
+    assert net._tapes["filter_lr"] is latest
+    net.filter_lr_train(f.x)     # (the shared case's own tape again)
+
+
 # ------------------------------------------------------------------ 6. train, commit, agree
 def test_step_commit_and_a_fresh_net_agree():
     """One SGD step on hg_parameters() from filter_lr_backward's gradients, commit(): filter_lr_train then equals a fresh net loaded from
