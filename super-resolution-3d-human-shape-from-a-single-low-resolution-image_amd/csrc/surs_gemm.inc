@@ -1,6 +1,7 @@
 // The layer GEMM of the point path (included by surs_query.hip inside namespace surs, after split3_bf16 and the vector
 // typedefs): gemm_x3g_kernel, one family of 256-point LDS-DMA tiles on split operands (one f16, two f16 or three bf16 parts),
-// and rvec_small_kernel, the same products for the small batches of the column kernels' affine part.  DESIGN.md section 4.3.
+// rvec_small_kernel, the same products for the small batches of the column kernels' affine part, and rvec_fused_kernel, the same
+// products for the bf16 sweep's large batches with the operand formed in the kernel.  DESIGN.md section 4.3.
 // ------------------------------------------------------------------------------------------------
 // Workgroup -> output tile for the layer GEMMs.  The point tile (128 columns of X, up to 1360 x 128 values) is the big
 // operand and every row block of the layer re-reads it, so the row blocks of one point tile must run together and on
@@ -406,4 +407,185 @@ __global__ __launch_bounds__(256) void rvec_small_kernel(RvecSmallArgs a) {
         for (int gq = 0; gq < 4; ++gq)
 #pragma unroll
             for (int r = 0; r < 4; ++r) out[(n0 + 32 * j + 4 * kh + 8 * gq + r) * D2 + m0 + li] = acc[j][4 * gq + r] + 0.0f;
+}
+
+// The affine part's GEMM of the bf16 sweep's LARGE batches (one f16 part, > 1024 columns), with its point operand formed in the
+// kernel: R = W1 (g . [a0 | w0z | w0p]) straight from the column constants.  colsum_prepare_kernel + two gemm_x3g launches wrote the
+// g-scaled f16 image to HBM (335 MB per batch of 32 768 columns) only to read it back once; here the image exists only in LDS.
+//   * A workgroup (8 waves) takes 64 columns x 256 of the 512 rows, ALL five vectors of its columns, in two phases: lr (2 vectors
+//     = 128 points = 4 point tiles), then hr (3 vectors = 192 points = 6 tiles).  The phases share nothing but the columns (lr reads
+//     a0_lr and w0z_lr, hr a0_hr, w0z_hr and w0p_hr), so running them one after the other keeps the accumulators at 6 tiles = 96
+//     registers where both together would need 160.  The two row blocks of a column tile are neighbours in gemm_block_tile's
+//     order: same XCD, same time - HBM sees a column's a0 once, the second block reads it from L2.
+//   * A step = eight k-tiles = 128 channels = 512 consecutive bytes of a column's a0 (four whole cache lines: no half line is left
+//     to L2).  Thread (columns fc + 16 q, quad of channels) loads four f32x4 of a0 a step ahead of their use, takes the same
+//     channels of w0z / w0p from LDS (copied there once per phase), forms g and the g-scaled values with colsum_prepare_kernel's
+//     expressions, converts with SplitKind<1>::split and writes 8 bytes per vector into the stage, which is laid out as the MFMA
+//     fragments of the point operand ([k-tile][point tile][half kh][point][8 halfwords], 16 bytes of padding behind every half so
+//     that the k-tiles of a wave's writes fall into different banks): a fragment read is one ds_read_b128.  Two stages; the stage
+//     of step s + 1 is written behind the barrier that ends step s - 1, a column group behind each of the first four k-tiles'
+//     products (plain loads, ds_write, __syncthreads: no counted waits).
+//   * A wave takes 32 rows x all point tiles: its weight fragment (h.wt2[m][1], the f16(w) plane in A-fragment order) is its
+//     own, read from L2 straight into registers eight k-tiles ahead - 8 KB of weights per k-tile and workgroup.  (The vector
+//     memory counter retires in order: a weight fragment that was sent for behind an a0 load cannot be used before that load has
+//     come back from HBM, so the weights' distance is what the a0 loads get.)  The fragments of k-tile t + 1 are read while the
+//     products of k-tile t run.
+// The SAME products in the same order on the same instruction as gemm_x3g_kernel<8, 256, G3_F32_T, 1> and rvec_small_kernel<1>
+// (operands swapped, k-tiles ascending, one product per MAC, + 0 for the zero bias): the same bits.
+struct RvecFusedArgs {
+    const float *cc;                // column constants [ncp][CC_PAD] (rows beyond the batch's columns: anything)
+    const float *zvec;
+    const unsigned short *w[2];     // weights of lr / hr, first plane: [64 k-tiles][512 / 32 row pieces][64 lanes][8]
+    float *r[2];                    // out: [nvec * ncp][512]
+    float zmid;
+    int tiles;                      // ncp / 64
+};
+constexpr int RVF_COLS = 64, RVF_ROWS = 256, RVF_THREADS = 512;
+constexpr int RVF_KS = 8;                                  // k-tiles per step: 128 channels = 512 bytes of a column's a0
+constexpr int RVF_PIECE = 1040, RVF_HALF = 528;            // a fragment in LDS: two halves (kh) of 32 points x 16 bytes, 16 bytes of padding behind each
+constexpr int RVF_STAGE_BYTES = RVF_KS * 6 * RVF_PIECE;    // x six point tiles (hr)
+constexpr int RVF_Z_BYTES = 2 * D1 * 4;                    // w0z and w0p of the phase's classifier
+constexpr int RVF_LDS_BYTES = 2 * RVF_STAGE_BYTES + RVF_Z_BYTES;
+
+template <int M>
+__device__ __forceinline__ void rvec_fused_phase(const RvecFusedArgs &a, unsigned char *smem, int col0, int m0) {
+    typedef SplitKind<1> SK;
+    typedef SK::vec8 vec8;
+    constexpr int NV = M ? 3 : 2, NT = 2 * NV;   // vectors per column; 32-point tiles of the 64 columns (NV of them per wave)
+    constexpr int KS = RVF_KS, STEPS = D1 / (16 * KS), KT = D1 / 16, PF = RVF_KS, NQ = RVF_COLS / 16, PS = RVF_PIECE;
+    static_assert(KS * NT * PS <= RVF_STAGE_BYTES && STEPS % 2 == 0 && KS == PF && KS >= NQ && KS % 2 == 0, "stage size; steps in pairs");
+    const int tid = threadIdx.x, lane = tid & 63, kh = lane >> 5, li = lane & 31;
+    // forming: thread = (columns fc + 16 q, quad fq of the step's 128 channels): 32 lanes read 512 consecutive bytes of a column;
+    // k-tile fq >> 2 of the step, halfwords 4 (fq & 3) .. + 3 of the point's 16 = half (fq & 3) >> 1 of the fragment, bytes
+    // 8 (fq & 1) .. + 7 of the lane's 16
+    const int fc = tid >> 5, fq = tid & 31;
+    const float *crow = a.cc + (size_t)(col0 + fc) * CC_PAD + (M ? CC_A0_HR : CC_A0_LR) + 4 * fq;
+    const float zmid = a.zmid;
+    float *zs = reinterpret_cast<float *>(smem + 2 * RVF_STAGE_BYTES);   // [w0z | w0p][1024]
+    {   // (everybody has left the previous phase's last form: the barrier that ended its last step)
+        const int v = tid >> 8, c = 4 * (tid & 255);
+        if (M || v == 0)
+            *reinterpret_cast<f32x4 *>(zs + v * D1 + c) =
+                *reinterpret_cast<const f32x4 *>(a.zvec + (v ? ZV_W0P_HR : (M ? ZV_W0Z_HR : ZV_W0Z_LR)) + c);
+    }
+    const unsigned wbase = (unsigned)(((fq >> 2) * NT * PS) + (((fq & 3) >> 1) * RVF_HALF) + (fq & 1) * 8);
+    auto load = [&](int s, int q) {
+        return *reinterpret_cast<const f32x4 *>(crow + (size_t)(16 * q) * CC_PAD + 16 * KS * s);
+    };
+    // the values of column fc + 16 q and the step's channels 4 fq .. + 3 (wz, wp: the same channels of w0z, w0p) into the stage
+    auto form = [&](int q, const f32x4 a0, const f32x4 wz, const f32x4 wp, unsigned char *stage) {
+        unsigned short hw[NV][4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            // (colsum_prepare_kernel's expressions)
+            float g, val[3];
+            if constexpr (M) {
+                g = fmaf(0.5f, wp[e], fmaf(zmid, wz[e], a0[e])) > 0.0f ? 1.0f : 0.01f;
+                val[2] = g * wp[e];
+            } else {
+                g = fmaf(zmid, wz[e], a0[e]) > 0.0f ? 1.0f : 0.01f;
+                val[2] = 0.0f;
+            }
+            val[0] = g * a0[e];
+            val[1] = g * wz[e];
+#pragma unroll
+            for (int v = 0; v < NV; ++v) {
+                unsigned short p[1];
+                SK::split(val[v], p);
+                hw[v][e] = p[0];
+            }
+        }
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            const int p = (fc + 16 * q) * NV + v;   // point = column * vectors + vector
+            *reinterpret_cast<u32x2 *>(stage + wbase + (unsigned)((p >> 5) * PS + (p & 31) * 16)) =
+                u32x2{(unsigned)hw[v][0] | ((unsigned)hw[v][1] << 16), (unsigned)hw[v][2] | ((unsigned)hw[v][3] << 16)};
+        }
+    };
+    auto zload = [&](int s, f32x4 &wz, f32x4 &wp) {
+        wz = *reinterpret_cast<const f32x4 *>(zs + 16 * KS * s + 4 * fq);
+        wp = wz;
+        if constexpr (M) wp = *reinterpret_cast<const f32x4 *>(zs + D1 + 16 * KS * s + 4 * fq);
+    };
+    // (the weight image is in A-fragment order: [k-tile][row / 32][lane][8] - surs_pack.cpp)
+    const unsigned short *wp_ = a.w[M] + (size_t)(m0 / 32) * 512 + lane * 8;   // + kt * D2 * 16
+    auto wload = [&](int kt) { return *reinterpret_cast<const vec8 *>(wp_ + (size_t)kt * D2 * 16); };
+    f32x16 acc[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) acc[j][q] = 0.0f;
+    vec8 wf[PF];
+#pragma unroll
+    for (int k = 0; k < PF; ++k) wf[k] = wload(k);
+    f32x4 ring[NQ];   // a0 of the step to be formed next, sent for again as soon as it has been formed (a step ahead of its use)
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) ring[q] = load(0, q);
+    __syncthreads();   // (w0z, w0p)
+    {
+        f32x4 wz, wp;
+        zload(0, wz, wp);
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            form(q, ring[q], wz, wp, smem);
+            ring[q] = load(1, q);
+        }
+    }
+    __syncthreads();
+    const unsigned char *rd = smem + kh * RVF_HALF + li * 16;
+    vec8 x[2][NT];   // the fragments of k-tile t in x[t & 1], read while the products of k-tile t - 1 run
+#pragma unroll
+    for (int j = 0; j < NT; ++j) x[0][j] = *reinterpret_cast<const vec8 *>(rd + j * PS);
+    // (no branches in the loop: the loads and the form beyond the end repeat the last step's - into registers and a stage nobody reads)
+#pragma unroll 1
+    for (int s2 = 0; s2 < STEPS; s2 += 2) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int s = s2 + u;
+            // stage u holds step s; everybody has finished reading the other one (step s - 1): step s + 1 is written there, a column
+            // group behind each of the first k-tiles' products, and its a0 sent for again
+            const int sf = s + 1 < STEPS ? s + 1 : STEPS - 1, sl = s + 2 < STEPS ? s + 2 : STEPS - 1;
+#pragma unroll
+            for (int t = 0; t < KS; ++t) {
+                const int kt = KS * s + t;
+                if (t + 1 < KS) {
+#pragma unroll
+                    for (int j = 0; j < NT; ++j)
+                        x[(t + 1) & 1][j] = *reinterpret_cast<const vec8 *>(rd + u * RVF_STAGE_BYTES + ((t + 1) * NT + j) * PS);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                const vec8 w = wf[t];
+#pragma unroll
+                for (int j = 0; j < NT; ++j) acc[j] = SK::mfma(x[t & 1][j], w, acc[j]);
+                if (t < NQ) {
+                    f32x4 wz, wp;
+                    zload(sf, wz, wp);
+                    form(t, ring[t], wz, wp, smem + (u ^ 1) * RVF_STAGE_BYTES);
+                    ring[t] = load(sl, t);
+                }
+                wf[t] = wload(kt + PF < KT ? kt + PF : KT - 1);
+            }
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < NT; ++j) x[0][j] = *reinterpret_cast<const vec8 *>(rd + (u ^ 1) * RVF_STAGE_BYTES + j * PS);
+        }
+    }
+    // register 4 g + r of tile j = point 32 j + 8 g + 4 kh + r of the workgroup's NV x 64, the lane's column = row m0 + li (+ 0: the
+    // other kernels' zero bias)
+    float *out = a.r[M] + (size_t)col0 * NV * D2 + m0 + li;
+#pragma unroll
+    for (int j = 0; j < NT; ++j)
+#pragma unroll
+        for (int gq = 0; gq < 4; ++gq)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) out[(size_t)(32 * j + 4 * kh + 8 * gq + r) * D2] = acc[j][4 * gq + r] + 0.0f;
+}
+
+__global__ __launch_bounds__(RVF_THREADS) void rvec_fused_kernel(RvecFusedArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char rvf_smem[];
+    int mb, nb;
+    if (!gemm_block_tile(D2 / RVF_ROWS, a.tiles, mb, nb)) return;   // (the whole workgroup)
+    const int col0 = nb * RVF_COLS, m0 = mb * RVF_ROWS + (int)(threadIdx.x >> 6) * 32;   // a wave: 32 rows x all point tiles
+    rvec_fused_phase<0>(a, rvf_smem, col0, m0);
+    rvec_fused_phase<1>(a, rvf_smem, col0, m0);
 }

@@ -436,6 +436,7 @@ static int g3_set_attributes() {
         SURS_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_x3g_kernel<8, 256, G3_SPLIT, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, g3_lds_bytes(256, 1)));
         SURS_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_x3g_kernel<8, 256, G3_F32, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, g3_lds_bytes(256, 1)));
         SURS_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_x3g_kernel<8, 128, G3_F32, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, g3_lds_bytes(128, 1)));
+        SURS_HIP_CHECK(hipFuncSetAttribute((const void *)rvec_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RVF_LDS_BYTES));
     }
     return 0;
 }
@@ -1271,7 +1272,6 @@ static int run_column_batch(const ColumnSweep &cs, const PointSource &src, long 
         unsigned short *g_lr = (unsigned short *)v7, *g_hr = g_lr + (size_t)COL_BATCH * 2 * D1 * 3;
         float *r_lr = (float *)(v7 + col_v7_image_bytes(COL_BATCH)), *r_hr = r_lr + (size_t)COL_BATCH * 2 * D2;
         float *zero_bias = r_hr + (size_t)COL_BATCH * 3 * D2;
-        SURS_HIP_CHECK(hipMemsetAsync(zero_bias, 0, D2 * 4 + 256, st));   // + the column counter behind it
         a.colctr = (unsigned *)(zero_bias + D2);
         {
             // (any depth serves - the restated layer 1 is an identity for every choice -; point runs have no grid: world z = 0)
@@ -1285,12 +1285,32 @@ static int run_column_batch(const ColumnSweep &cs, const PointSource &src, long 
         // of the MFMA work, no measurable change of the bf16 sweep's error (SURS_R_PARTS=0: the split's parts there too)
         const int r_parts_env = option(OPT_R_PARTS);
         const int rparts = (dtype == SURS_BF16 && r_parts_env == 1) ? 1 : parts;
-        with_parts<1, 2, 3>(rparts, [&](auto NP) {
-            hipLaunchKernelGGL(colsum_prepare_kernel<NP>, pg, dim3(256), 0, st, CC, (const float *)(blob + h.zvec), (int)ncp, a.zmid,
-                               g_lr, part_lr, g_hr, part_hr);
-        });
-        SURS_LAUNCH_CHECK();
-        if (ncp <= 1024 && option(OPT_RVEC_SMALL)) {
+        // the bf16 sweep's large batches: one kernel forms the g-scaled operand itself (rvec_fused_kernel; r_fused = 0: the image +
+        // two GEMM launches, same bits); it needs neither the image nor the zero bias, only the column counters behind it
+        const bool fused = rparts == 1 && ncp > 1024 && option(OPT_R_FUSED);
+        if (fused) SURS_HIP_CHECK(hipMemsetAsync(a.colctr, 0, 256, st));
+        else SURS_HIP_CHECK(hipMemsetAsync(zero_bias, 0, D2 * 4 + 256, st));   // + the column counters behind it
+        if (!fused) {
+            with_parts<1, 2, 3>(rparts, [&](auto NP) {
+                hipLaunchKernelGGL(colsum_prepare_kernel<NP>, pg, dim3(256), 0, st, CC, (const float *)(blob + h.zvec), (int)ncp, a.zmid,
+                                   g_lr, part_lr, g_hr, part_hr);
+            });
+            SURS_LAUNCH_CHECK();
+        }
+        if (fused) {
+            RvecFusedArgs fa;
+            fa.cc = CC;
+            fa.zvec = (const float *)(blob + h.zvec);
+            fa.zmid = a.zmid;
+            fa.tiles = (int)(ncp / RVF_COLS);   // (ncp is a multiple of 256)
+            for (int m = 0; m < 2; ++m) {
+                fa.w[m] = (const unsigned short *)(blob + h.wt2[m][1]);
+                fa.r[m] = m ? r_hr : r_lr;
+            }
+            if ((rc = g3_set_attributes())) return rc;
+            hipLaunchKernelGGL(rvec_fused_kernel, dim3(gemm_grid(D2 / RVF_ROWS, fa.tiles)), dim3(RVF_THREADS), RVF_LDS_BYTES, st, fa);
+            SURS_LAUNCH_CHECK();
+        } else if (ncp <= 1024 && option(OPT_RVEC_SMALL)) {
             // small batches (the ~ 100 runs of a point-runs call, small slabs, coarse octree levels): both classifiers in one launch of
             // 64-point x 128-row workgroups (rvec_small_kernel: the same bits as the 256 x 256-tile GEMM below, 4 - 6 workgroups of which
             // walk K = 1024 in 34 - 62 us each here)
