@@ -1001,6 +1001,54 @@ int surs_mlp_repack_host(int dtype, const float *const *w_lr, const float *const
 int surs_mlp_repack_generic_host(const SursMlpShape *lr, const float *const *w_lr, const float *const *b_lr, const SursMlpShape *hr,
                                  const float *const *w_hr, const float *const *b_hr, void *blob);
 
+/* ---------------------------------------------------------------- optimiser step
+ * optimizerG.step() of the reference's training loop (apps/train_SuRS.py:54-72, :148) on the plain fp32 parameters: SGD (momentum,
+ * dampening 0, no Nesterov), ADAM, AMSgrad and RMSprop (momentum 0, not centred), weight decay as an L2 term of the gradient
+ * (g + wd p), in the order of operations of torch.optim's single-tensor path (csrc/surs_optim_update.h has the arithmetic, one
+ * function per kind).  ONE launch updates every tensor of a device table in place; what it leaves is what surs_conv_repack /
+ * surs_mlp_repack then pack.  Every element's new bits depend on its own old values alone: equal inputs give equal bits wherever
+ * the buffers lie.  Non-finite gradients propagate as they do in torch. */
+enum { SURS_OPTIM_SGD = 0, SURS_OPTIM_ADAM = 1, SURS_OPTIM_AMSGRAD = 2, SURS_OPTIM_RMSPROP = 3 };
+
+/* One parameter tensor of a surs_optim_step table; every pointer a device pointer (a host pointer for surs_optim_step_host). */
+typedef struct SursOptimItem {
+    float *p;            /* value, updated in place */
+    const float *g;      /* gradient, read only */
+    float *s0, *s1, *s2; /* state, updated in place: SGD buf (NULL with momentum 0) | ADAM m, v | AMSgrad m, v, vmax | RMSprop sq;
+                          * the ones a kind does not use are neither read nor written and may be NULL */
+    long long n;         /* elements; 0 is legal and costs nothing */
+    int chunk_end;       /* the inclusive prefix sum of surs_optim_chunks(n) over the table: how a workgroup finds its item */
+    int reserved;
+} SursOptimItem;
+
+/* The hyper-parameters of one step: kernel ARGUMENTS, not table entries - a changed learning rate or step count uploads nothing.
+ * The caller forms the step-dependent scalars in double and rounds them to fp32; the kernel takes no powers. */
+typedef struct SursOptimHyper {
+    int kind;            /* SURS_OPTIM_* */
+    int first_step;      /* SGD with momentum: 1 on the optimiser's first step (buf = g), else 0 (buf = momentum buf + g) */
+    float lr, weight_decay, momentum;
+    float beta1_c;       /* 1 - beta1 */
+    float beta2, beta2_c;/* beta2, 1 - beta2 */
+    float alpha, alpha_c;/* RMSprop: alpha, 1 - alpha */
+    float eps;
+    float step_size;     /* ADAM / AMSgrad: lr / (1 - beta1^t), t the 1-based step */
+    float bc2_sqrt;      /* ADAM / AMSgrad: sqrt(1 - beta2^t) */
+} SursOptimHyper;
+
+/* workgroup visits (chunks of 4096 elements) of an item of n elements: ceil(n / 4096), 0 for n <= 0 */
+int surs_optim_chunks(long long n);
+/* Checks a HOST copy of a table against `h`, as a caller does once when it builds the table: SURS_E_INVALID for an unknown kind, a
+ * null p or g (of an item with n > 0), a missing state pointer the kind needs, n < 0, or a chunk_end that is not the prefix sum. */
+int surs_optim_check(const SursOptimItem *items, int n_items, const SursOptimHyper *h);
+/* One launch (256-thread workgroups, at most 2048, striding over the chunks of all items) on `stream`: items a DEVICE table, h
+ * HOST.  16-byte loads and stores wherever every pointer of the item is 16-byte aligned at the chunk, scalar access otherwise and
+ * for the n % 4 tail.  No LDS, no atomics, no allocation, no synchronisation.  Refuses (nothing launched) an unknown kind, a null
+ * table and n_items < 0; n_items == 0 does nothing.  The table itself is on the device: surs_optim_check is its check. */
+int surs_optim_step(const SursOptimItem *items, int n_items, const SursOptimHyper *h, void *stream);
+/* The same arithmetic looped on the HOST (items a HOST table of HOST pointers), after surs_optim_check: nothing is written when it
+ * refuses.  What the kernel is held against bit for bit, and torch.optim without a device; not a path of the product. */
+int surs_optim_step_host(const SursOptimItem *items, int n_items, const SursOptimHyper *h);
+
 #ifdef __cplusplus
 }
 #endif

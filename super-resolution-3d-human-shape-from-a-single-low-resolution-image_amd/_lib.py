@@ -134,6 +134,20 @@ class RepackItem(C.Structure):
                 ("packed", C.c_void_p), ("x2", C.c_void_p), ("x3", C.c_void_p)]
 
 
+class OptimItem(C.Structure):
+    """SursOptimItem of include/surs.h: one parameter tensor of a surs_optim_step table (chunk_end: the inclusive prefix sum of
+    surs_optim_chunks(n) over the table)."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("s0", C.c_void_p), ("s1", C.c_void_p), ("s2", C.c_void_p), ("n", C.c_longlong),
+                ("chunk_end", C.c_int), ("reserved", C.c_int)]
+
+
+class OptimHyper(C.Structure):
+    """SursOptimHyper of include/surs.h: one step's hyper-parameters, kernel arguments."""
+    _fields_ = [("kind", C.c_int), ("first_step", C.c_int)] + [(k, C.c_float) for k in (
+        "lr", "weight_decay", "momentum", "beta1_c", "beta2", "beta2_c", "alpha", "alpha_c", "eps", "step_size", "bc2_sqrt")]
+
+
+OPTIM_SGD, OPTIM_ADAM, OPTIM_AMSGRAD, OPTIM_RMSPROP = 0, 1, 2, 3     # SURS_OPTIM_* of include/surs.h
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 _shp = C.POINTER(MlpShape)
 _SIGS = {
@@ -297,6 +311,10 @@ _SIGS = {
     "surs_mlp_repack_generic": (C.c_int, [_shp, _vp, _vp, _shp, _vp, _vp, _vp, _vp]),
     "surs_mlp_repack_host": (C.c_int, [_i, _vp, _vp, _vp, _vp, _vp]),
     "surs_mlp_repack_generic_host": (C.c_int, [_shp, _vp, _vp, _shp, _vp, _vp, _vp]),
+    "surs_optim_chunks": (C.c_int, [C.c_longlong]),
+    "surs_optim_check": (C.c_int, [_vp, _i, C.POINTER(OptimHyper)]),
+    "surs_optim_step": (C.c_int, [_vp, _i, C.POINTER(OptimHyper), _vp]),
+    "surs_optim_step_host": (C.c_int, [_vp, _i, C.POINTER(OptimHyper)]),
 }
 MESH_FACES_PER_PART, SAMPLE_SELECT_CHUNK = 4096, 1024     # SURS_MESH_FACES_PER_PART, SURS_SAMPLE_SELECT_CHUNK of include/surs.h
 EXPORTS = sorted(_SIGS)

@@ -8,7 +8,7 @@ get_errorSR(), get_error_disp_1(), forward().
 
 It is NOT a torch.nn.Module: parameters are a flat ordered dict keyed exactly like the reference's state dict
 (all 553 keys, strict; 1036 with --norm batch), and every forward method sequences hand-written HIP kernels through the C ABI.  There is
-no autograd graph and no optimiser and no CPU path: methods raise without a GPU / built library.  forward() is the
+no autograd graph and no CPU path: methods raise without a GPU / built library (the optimiser over the parameter sets is optim.Optimizer).  forward() is the
 VALIDATION forward: every kept stack's predictions and the reference's loss, without an autograd graph (SuRSNet.py:240-266).
 The one part of the backward pass that exists is the classifiers': forward_backward() / classifier_grads() return d error / d (every
 mlp_lr.* and mlp_hr.* parameter) and, with features=True, d error / d (the feature maps of im_feat_list_lr and im_feat_list_hr[0])

@@ -1078,6 +1078,66 @@ def mlp_repack_generic(params, g):
     check(lib().surs_mlp_repack_generic(C.byref(g.lr), _ptr(wl), _ptr(bl), C.byref(g.hr), _ptr(wh), _ptr(bh), _ptr(g.blob), _stream()))
 
 
+# ------------------------------------------------------------------ optimiser step
+
+OPTIM_KINDS = {"SGD": _lib.OPTIM_SGD, "ADAM": _lib.OPTIM_ADAM, "AMSgrad": _lib.OPTIM_AMSGRAD, "RMSprop": _lib.OPTIM_RMSPROP}
+OPTIM_STATES = {"SGD": ("momentum_buffer",), "ADAM": ("exp_avg", "exp_avg_sq"), "AMSgrad": ("exp_avg", "exp_avg_sq", "max_exp_avg_sq"),
+                "RMSprop": ("square_avg",)}      # torch.optim's names of s0, s1, s2 (SGD: none with momentum 0)
+
+
+def optim_hyper(kind, t, lr, weight_decay=0.0, momentum=0.0, betas=(0.9, 0.999), eps=1e-8, alpha=0.99, first_step=False):
+    """SursOptimHyper of step t (1-based) of `kind` (a name of OPTIM_KINDS, or any int: the library refuses an unknown one): the
+    step-dependent scalars lr / (1 - beta1^t), sqrt(1 - beta2^t) and the complements 1 - beta formed here in double, as torch forms
+    them, and rounded to the fp32 the kernel takes.  momentum: SGD's; the other kinds have none."""
+    h = _lib.OptimHyper()
+    h.kind = OPTIM_KINDS[kind] if kind in OPTIM_KINDS else int(kind)
+    b1, b2 = float(betas[0]), float(betas[1])
+    t = max(int(t), 1)
+    h.first_step = int(bool(first_step))
+    h.lr, h.weight_decay, h.momentum = float(lr), float(weight_decay), float(momentum) if h.kind == _lib.OPTIM_SGD else 0.0
+    h.beta1_c, h.beta2, h.beta2_c = 1.0 - b1, b2, 1.0 - b2
+    h.alpha, h.alpha_c, h.eps = float(alpha), 1.0 - float(alpha), float(eps)
+    h.step_size, h.bc2_sqrt = float(lr) / (1.0 - b1 ** t), (1.0 - b2 ** t) ** 0.5
+    return h
+
+
+def optim_items(rows):
+    """A host array of SursOptimItem over rows (p, g, s0, s1, s2, n) of raw addresses (None: NULL), chunk_end filled in."""
+    items = (_lib.OptimItem * max(len(rows), 1))()
+    end = 0
+    for it, (p, g, s0, s1, s2, n) in zip(items, rows):
+        end += lib().surs_optim_chunks(n)
+        it.p, it.g, it.s0, it.s1, it.s2, it.n, it.chunk_end = p, g, s0, s1, s2, n, end
+    return items
+
+
+def optim_check(items, n_items, hyper):
+    """surs_optim_check of a host table: SursError for what surs_optim_step could only misuse."""
+    check(lib().surs_optim_check(C.cast(items, C.c_void_p), n_items, C.byref(hyper)))
+
+
+def optim_step(table, n_items, hyper):
+    """surs_optim_step: every item of the DEVICE table `table` (the bytes of optim_items, checked by optim_check) updated in place by one
+    launch on the current stream."""
+    check(lib().surs_optim_step(_ptr(table), n_items, C.byref(hyper), _stream()))
+
+
+def optim_step_host(tensors, hyper):
+    """surs_optim_step_host over rows (p, g, s0, s1, s2) of contiguous float32 numpy arrays (states None where the kind has none; g of
+    any shape with p's element count), updated in place on the HOST: no device needed."""
+    rows = []
+    for r in tensors:
+        p, g = r[0], r[1]
+        for a in r:
+            if a is not None and (a.dtype != np.float32 or not a.flags.c_contiguous):
+                raise ValueError("optim_step_host: contiguous float32 arrays expected")
+        for a in r[1:]:
+            if a is not None and a.size != p.size:
+                raise ValueError("optim_step_host: a tensor of %d elements against a parameter of %d" % (a.size, p.size))
+        rows.append(tuple(a.ctypes.data if a is not None else None for a in r) + (p.size,))
+    check(lib().surs_optim_step_host(C.cast(optim_items(rows), C.c_void_p), len(rows), C.byref(hyper)))
+
+
 def mlp_grad_workspace_bytes(shapes):
     """surs_mlp_grad_workspace_bytes: the device workspace of mlp_grads for this pair - a function of the shapes, not of n."""
     lr, hr = (_shape_struct(*s) for s in shapes)

@@ -91,3 +91,15 @@ def gen_mesh_pipelined(opt, net, cuda, dataset, indices, save_path_of, use_octre
         decoder.shutdown(wait=True)
         writer.shutdown(wait=True)
     return results
+
+
+def adjust_learning_rate(optimizer, epoch, lr, schedule, gamma):
+    """The step schedule of the reference's training loop (/root/reference/lib/train_util.py:89-95), same signature: at an epoch listed
+    in `schedule` the rate becomes lr * gamma and is written into every group of optimizer.param_groups - a torch.optim optimiser's or
+    optim.Optimizer's, which reads it at its next step; any other epoch changes nothing.  Returns the rate to carry on with."""
+    if epoch not in schedule:
+        return lr
+    lr = lr * gamma
+    for group in optimizer.param_groups:
+        group["lr"] = lr
+    return lr
