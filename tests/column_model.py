@@ -108,10 +108,11 @@ class Rounding:
 
 
 # ------------------------------------------------------------------ accumulation
-def gemm(products, acc, order, init=None):
+def gemm(products, acc, order, init=None, kstep=16):
     """sum over k of the listed products: products = [(W [M,K], X [K,N]), ...], all added into one accumulator k-step by k-step
     in the listed order (an MFMA each).  acc = np.float64: the exact sum (to float64).  acc = np.float32: an fp32 accumulator
-    that takes every k-step of 16 as one addend, k-steps ascending (order "asc") or descending ("desc")."""
+    that takes every k-step of `kstep` (16: the 32x32x16 MFMA of the column kernels and the layer GEMM; tests/fused_model.py passes
+    the fused evaluator's 32) as one addend, k-steps ascending (order "asc") or descending ("desc")."""
     K = products[0][0].shape[1]
     if acc is np.float64:
         out = 0.0 if init is None else np.asarray(init, np.float64)
@@ -121,10 +122,10 @@ def gemm(products, acc, order, init=None):
     assert acc is np.float32 and order in ("asc", "desc")
     M, N = products[0][0].shape[0], products[0][1].shape[1]
     a = np.zeros((M, N), np.float32) if init is None else np.array(np.broadcast_to(init, (M, N)), np.float32)
-    steps = list(range(0, K, 16))
+    steps = list(range(0, K, kstep))
     for s in (steps if order == "asc" else steps[::-1]):
         for W, X in products:
-            a += (W[:, s:s + 16] @ X[s:s + 16]).astype(np.float32)
+            a += (W[:, s:s + kstep] @ X[s:s + kstep]).astype(np.float32)
     return a.astype(np.float64)
 
 
