@@ -952,6 +952,30 @@ int surs_sample_select(const float *pool, int ld, int n_pool, const unsigned cha
                        int n, float *samples_hr, float *labels_hr, float *samples_lr, float *labels_disp, int32_t *counts,
                        void *stream);
 
+/* ---------------------------------------------------------------- mesh distance
+ * How far a set of points lies from a mesh: what point-to-surface (P2S) and Chamfer distance are made of.  A mesh as in "training
+ * samples" (indices clamped to [0, nv)); brute force over all faces, no acceleration structure, no atomics: the same arguments give
+ * the same bits.
+ *
+ * dist[i] = sqrt(min_f d2(p_i, f)) (a correctly rounded square root), p_i = points[i * ld .. + 3] (ld >= 3), and face[i] (nullable)
+ * the LOWEST face index that attains that minimum in fp32.  d2 is the squared distance to the triangle in fp32 (csrc/
+ * surs_mesh_distance.h, one arithmetic for host and device): the minimum over the three edges of |x - clamp(s, 0, 1) e|^2, s = x.e /
+ * e.e, replaced by (ap.n)^2 / n.n where the triangle has an area and the point's projection falls inside it; no squared lengths are
+ * subtracted.  A zero-area triangle is its three segments, a repeated vertex a point: the result is finite for finite input.  A
+ * point with a NaN or infinite coordinate gets dist = +inf and face = -1 (the initial value: every comparison with it is false).
+ * The faces are split into surs_mesh_contains_parts(nf) parts of SURS_MESH_FACES_PER_PART - a function of nf alone -; each part
+ * keeps its minimum with a strict < in face order and writes it to workspace [parts][n] entries of (fp32 d2, int32 face), and the
+ * parts are combined in index order with a strict < again.  A point's two results do not depend on n, on ld, on its position in
+ * the array or on the other points of the call.
+ * SURS_E_INVALID, before anything is launched: n < 0, nf < 1, nv < 1, ld < 3, a NULL array, a workspace smaller than
+ * surs_mesh_distance_workspace_bytes(n, nf) (which is 0 for n < 1 or nf < 1).  n == 0 is success and launches nothing.
+ * surs_mesh_distance_host is the same header looped on the HOST (all pointers host pointers): the kernel's bits, no device. */
+size_t surs_mesh_distance_workspace_bytes(int n, int nf);
+int surs_mesh_distance(const float *points, int n, int ld, const float *verts, int nv, const int32_t *faces, int nf,
+                       void *workspace, size_t workspace_bytes, float *dist, int32_t *face, void *stream);
+int surs_mesh_distance_host(const float *points, int n, int ld, const float *verts, int nv, const int32_t *faces, int nf,
+                            float *dist, int32_t *face);
+
 /* ---------------------------------------------------------------- device repack
  * The packed images the forward reads (surs_conv_pack_weights*, the blobs of surs_mlp_pack / surs_mlp_pack_generic) rebuilt ON THE
  * DEVICE from the plain fp32 parameters an optimiser has just stepped: the bytes the host packers give for the same values, without

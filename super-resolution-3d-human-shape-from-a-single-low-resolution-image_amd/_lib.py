@@ -304,6 +304,9 @@ _SIGS = {
     "surs_mesh_sample_pool": (C.c_int, [_vp, _i, _vp, _i, _vp, C.c_ulonglong, _i, _i, _f, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                         _vp, _vp, _vp, _vp]),
     "surs_sample_select": (C.c_int, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "surs_mesh_distance_workspace_bytes": (_sz, [_i, _i]),
+    "surs_mesh_distance": (C.c_int, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp]),
+    "surs_mesh_distance_host": (C.c_int, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
     "surs_conv_repack_tiles": (C.c_int, [_i, _i, _i]),
     "surs_conv_repack": (C.c_int, [_vp, _i, _vp]),
     "surs_conv1x1_merge": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),

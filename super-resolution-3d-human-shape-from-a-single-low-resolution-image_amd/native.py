@@ -2375,3 +2375,39 @@ def sample_select(pool, inside_hr, inside_lr, n):
     check(lib().surs_sample_select(_ptr(pool), ld, P, _ptr(inside_hr), _ptr(inside_lr), int(n), _ptr(s_hr), _ptr(l_hr), _ptr(s_lr),
                                    _ptr(l_disp), _ptr(counts), _stream()))
     return s_hr, l_hr, s_lr, l_disp, counts
+
+
+# ------------------------------------------------------------------ mesh distance (include/surs.h "mesh distance")
+
+def mesh_distance(points, mesh, want_face=False):
+    """points [n, >= 3] float32 (rows may be wider than 3: the row stride is the kernel's ld) -> float32 [n], each point's distance to
+    the nearest triangle of `mesh`; with want_face also int32 [n], the lowest index among the nearest triangles.  A point with a
+    non-finite coordinate gets +inf and -1."""
+    assert points.dtype == torch.float32 and points.dim() == 2 and points.shape[1] >= 3
+    n = points.shape[0]
+    assert n == 0 or points.stride(1) == 1, "points: unit stride along a row"
+    ld = points.stride(0) if n > 1 else max(3, points.shape[1])
+    assert ld >= 3
+    dist = torch.empty(n, dtype=torch.float32, device=points.device)
+    face = torch.empty(n, dtype=torch.int32, device=points.device) if want_face else None
+    if n:
+        nbytes = lib().surs_mesh_distance_workspace_bytes(n, mesh.nf)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=points.device)
+        check(lib().surs_mesh_distance(_ptr(points), n, ld, _ptr(mesh.verts), mesh.nv, _ptr(mesh.faces), mesh.nf, _ptr(ws), nbytes,
+                                       _ptr(dist), _ptr(face), _stream()))
+    return (dist, face) if want_face else dist
+
+
+def mesh_distance_host(points, verts, faces):
+    """surs_mesh_distance_host on numpy arrays - points [n, >= 3], verts [nv, 3], faces [nf, 3] - on the HOST, no device needed:
+    (dist float32 [n], face int32 [n]), the kernel's bits."""
+    p = np.asarray(points, np.float32)
+    if p.ndim != 2 or p.shape[1] < 3:
+        raise ValueError("mesh_distance_host: points [n, >= 3] expected, not %s" % (p.shape,))
+    p = np.ascontiguousarray(p)
+    v = np.ascontiguousarray(np.asarray(verts, np.float32).reshape(-1, 3))
+    f = np.ascontiguousarray(np.asarray(faces, np.int32).reshape(-1, 3))
+    dist, face = np.empty(len(p), np.float32), np.empty(len(p), np.int32)
+    check(lib().surs_mesh_distance_host(p.ctypes.data, len(p), p.shape[1], v.ctypes.data, len(v), f.ctypes.data, len(f), dist.ctypes.data,
+                                        face.ctypes.data))
+    return dist, face

@@ -27,6 +27,36 @@ def gen_mesh(opt, net, cuda, data, save_path, use_octree=True):
     return verts_hr, faces_hr, verts_lr, faces_lr
 
 
+def gen_mesh_metrics(opt, net, cuda, data, save_path=None, use_octree=True, n=10000, seed=0, gt_hr=None, gt_lr=None):
+    """gen_mesh's reconstruction of one item, scored against the item's ground-truth scans: {"HR": metrics.mesh_metrics(the HR
+    volume's mesh, the HR scan), "LR": (the LR volume's mesh, the LR scan)}, each from n surface samples per mesh.  The predicted
+    vertices are taken into the scans' frame first (metrics.pred_to_gt_transform(data['calib']): the identity without a calib), so
+    the distances are in the dataset's units.  The scans are data['mesh_path_HR'] / ['mesh_path_LR'] (OBJ files) unless gt_hr /
+    gt_lr hand in meshes (native.Mesh or (verts, faces)).  With a save_path the two OBJ files of gen_mesh are written as well."""
+    from . import metrics
+    from .mesh_util import load_obj_mesh
+    n = metrics.check_samples(n)
+    for key, given in (("mesh_path_HR", gt_hr), ("mesh_path_LR", gt_lr)):
+        if given is None and key not in data:
+            raise ValueError("gen_mesh_metrics: the item has no %r and no ground-truth mesh was handed in" % key)
+    to_gt = metrics.pred_to_gt_transform(data.get("calib"))
+    image_tensor = data["img_LR"].to(device=cuda)
+    img_sr, feature_lr, feature_hr = net.super_res(image_tensor)
+    net.filter_hr(feature_hr)
+    net.filter_lr(feature_lr)
+    calib_tensor = gen_calib().to(device=cuda)
+    verts_hr, faces_hr, _, _, verts_lr, faces_lr, _, _ = reconstruction(
+        opt, net, cuda, calib_tensor, opt.resolution, data["b_min"], data["b_max"], use_octree=use_octree,
+        num_samples=opt.num_samples, want_normals=False)
+    if save_path is not None:
+        save_obj_mesh(save_path[:-4] + "_HR.obj", verts_hr, faces_hr)
+        save_obj_mesh(save_path[:-4] + "_LR.obj", verts_lr, faces_lr)
+    gt_hr = load_obj_mesh(data["mesh_path_HR"]) if gt_hr is None else gt_hr
+    gt_lr = load_obj_mesh(data["mesh_path_LR"]) if gt_lr is None else gt_lr
+    return {"HR": metrics.mesh_metrics((metrics.transform_verts(to_gt, verts_hr), faces_hr), gt_hr, n=n, seed=seed),
+            "LR": metrics.mesh_metrics((metrics.transform_verts(to_gt, verts_lr), faces_lr), gt_lr, n=n, seed=seed)}
+
+
 def gen_mesh_pipelined(opt, net, cuda, dataset, indices, save_path_of, use_octree=True, write=True):
     """gen_mesh for a run of subjects (the loop of /root/reference/apps/eval_SuRS.py:74-80) as a pipeline: while the GPU sweeps
     subject i, (1) a host thread decodes subject i+1's image and mask, (2) its pixels are uploaded and normalised / masked
