@@ -71,9 +71,6 @@ constexpr int V12_ZTAB = V12_CNT + 32;                   // the tile's zf [128] 
 constexpr int GRID12_LDS_BYTES = V12_ZTAB + 1024;
 static_assert(V12_LISTC % 16 == 0 && GRID12_LDS_BYTES <= 81920, "two workgroups per CU");
 
-#ifdef SURS_V12_HIST
-__device__ unsigned long long *g_v12_hist;   // diagnostic builds: tiles by residual k-steps [65]
-#endif
 #ifdef SURS_V3_TRACE
 // diagnostic builds: wave 0 of workgroup SURS_V12_TRACE_WG (default 100) sums, over every item it runs, the cycles between the
 // stamps (g_v12_acc[M][i] = phase ending at stamp i, [M][0] = items, [M][15] = residual k-steps); the single-tile stamps of the
@@ -261,9 +258,6 @@ __device__ __forceinline__ bool grid_mlp_v12(const char *__restrict__ wbase /* t
     ksteps += (unsigned)ks;
 #ifdef SURS_V3_TRACE
     if (v12_ac) g_v12_acc[M][15] += (unsigned long long)ks;
-#endif
-#ifdef SURS_V12_HIST
-    if (tid == 0 && g_v12_hist) atomicAdd(&g_v12_hist[ks < 64 ? ks : 64], 1ull);
 #endif
     {
         const unsigned long long lt = (1ull << ol) - 1ull;

@@ -142,12 +142,9 @@ extern "C" int surs_query_points_stacks(const float *points, int n, const float 
     const long long np = (long long)ceil_div(n, 256) * 256;
     SURS_REQUIRE(workspace_bytes >= fp32_ws_bytes(np), "workspace too small: need %zu bytes", fp32_ws_bytes(np));
     const MlpBlobHeader h = blob_layout(SURS_BF16);
-    PointSource src;
-    memset(&src, 0, sizeof(src));
-    src.mode = 0;
+    PointSource src = point_source(0, 0, 0, nullptr, calib, zmul, zdiv);
     src.pts = points;
     src.ld = n;
-    fill_calib(src, calib, zmul, zdiv);
     Fp32Workspace w = carve_fp32(workspace, np);
     int rc = zero_pad_rows(st, w);   // (once: no pass writes those rows)
     if (rc) return rc;

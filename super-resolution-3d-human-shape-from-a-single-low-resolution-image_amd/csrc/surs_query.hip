@@ -546,14 +546,15 @@ struct GridArgs {
     const char *core;      // SLABS_TOTAL slabs
     const char *corex;     // the same cores as two f16 parts per weight (kernel v5, fp32-grade)
     const char *b1frag;    // layer-1 biases as A fragments (kernel v3)
-    const char *w1t;       // layer-1 weights channel-major (kernel v7)
-    const char *w1tx;      // the same as two f16 parts (kernel v8)
+    const char *w1t;       // layer-1 weights channel-major (restated kernels 10 / 12)
+    const char *w1tx;      // the same as two f16 parts (restated kernel 11)
     const float *rvec_lr, *rvec_hr;   // restated kernels: R = W1 (g . [a0 | w0z | w0p]) of the batch, fp32 [column][2 | 3 vectors][512 rows]
-    long long rld_lr, rld_hr;         // (unused)
-    float zmid;            // zf at mid column: where kernel v7's per-column LeakyReLU branch g_c is taken
-    unsigned *colctr;      // kernels v7 / v8: next column to hand out (zeroed before the launch); kernel v11: one counter per pass
+    long long rld_lr, rld_hr;         // (unused and always 0.  Taking them out moves every later field: the argument offsets and the
+                                      //  code object of every column kernel change - a change of its own, with the ISA pins)
+    float zmid;            // zf at mid column: where the restated kernels take the per-column LeakyReLU branch g_c
+    unsigned *colctr;      // restated kernels: next column to hand out (zeroed before the launch); kernel 11: one counter per pass
     int phase;             // kernel v11: 0 = both classifiers per tile, 1 = the lr classifier only, 2 = the hr classifier on vol_lr
-    unsigned long long *kstat;   // profiling only: sum of kernel v7's residual k-steps (null otherwise)
+    unsigned long long *kstat;   // profiling only: sum of the restated kernels' residual k-steps (null otherwise)
     float b1_inv_scale;    // what B_ones holds: 1 / B1FRAG_SCALE of the blob's dtype
     float *vol_hr, *vol_lr;  // [ncols][rz]
     int ncols, rz;
@@ -615,10 +616,10 @@ __device__ __forceinline__ unsigned fresh_lane() {
 #include "surs_grid_v12.inc"
 #include "surs_grid_v11.inc"
 
-// Column kernel v7's per-column affine part, step 1: the vectors g . a0, g . w0z (lr) and g . a0, g . w0z, g . w0p (hr) of a
-// column batch as the split image [parts][1024 / 16][nvec * ncp][16] that the layer GEMM kernel reads as its point operand
-// (point index = column * nvec + vector).  g_c = 1 or 0.01: the LeakyReLU branch of channel c at mid column (the same
-// expression as in grid_mlp_v7).  Thread = (column, group of 16 channels).
+// The restated kernels' (10 / 11 / 12) per-column affine part, step 1: the vectors g . a0, g . w0z (lr) and g . a0, g . w0z, g . w0p
+// (hr) of a column batch as the split image [parts][1024 / 16][nvec * ncp][16] - the "g image" - that the layer GEMM kernel reads as
+// its point operand (point index = column * nvec + vector).  g_c = 1 or 0.01: the LeakyReLU branch of channel c at mid column (the
+// same expression as in the restated kernels).  Thread = (column, group of 16 channels).
 // Until round 6 a thread took (column, 16 channels) with the LANES along the columns: every lane read its own 11.8 KB-strided row
 // of the column constants - 64 cache lines per load instruction - and the kernel ran at 3 TB/s (197 us per batch of 32 768
 // columns, a quarter of a batch's preparation).  Now a WAVE takes one column and its lanes the 64 groups of 16 channels: the two
@@ -739,10 +740,20 @@ extern "C" size_t surs_query_workspace_bytes(int max_points) {
     return fp32_ws_bytes(np);
 }
 
-static void fill_calib(PointSource &s, const float *calib, float zmul, float zdiv) {
+// A PointSource of `mode` under calib: the grid ry x rz with create_grid's matrix mat, or no grid (mat null: the modes that read a
+// point array).  Everything else is zero; the caller sets what its mode reads (pts / ld / npts, base, idx, cols) and persp.
+static PointSource point_source(int mode, int ry, int rz, const double *mat, const float *calib, float zmul, float zdiv) {
+    PointSource s;
+    memset(&s, 0, sizeof(s));
+    s.mode = mode;
+    s.ry = ry;
+    s.rz = rz;
+    if (mat)
+        for (int i = 0; i < 12; ++i) s.mat[i] = mat[i];
     for (int i = 0; i < 12; ++i) s.calib[i] = calib[i];
     s.zmul = zmul;
     s.zdiv = zdiv;
+    return s;
 }
 
 extern "C" int surs_query_points(const float *points, int n, const float *calib, float zmul, float zdiv,
@@ -757,12 +768,9 @@ extern "C" int surs_query_points(const float *points, int n, const float *calib,
     const long long np = (long long)ceil_div(n, 256) * 256;
     SURS_REQUIRE(workspace_bytes >= fp32_ws_bytes(np), "workspace too small: need %zu bytes", fp32_ws_bytes(np));
     const MlpBlobHeader h = blob_layout(SURS_BF16);
-    PointSource src;
-    memset(&src, 0, sizeof(src));
-    src.mode = 0;
+    PointSource src = point_source(0, 0, 0, nullptr, calib, zmul, zdiv);
     src.pts = points;
     src.ld = n;
-    fill_calib(src, calib, zmul, zdiv);
     Fp32Workspace w = carve_fp32(workspace, np);
     int rc = zero_pad_rows(st, w);
     if (rc) return rc;
@@ -782,12 +790,9 @@ extern "C" int surs_query_points_hr(const float *points, int n, const float *cal
     const long long np = (long long)ceil_div(n, 256) * 256;
     SURS_REQUIRE(workspace_bytes >= fp32_ws_bytes(np), "workspace too small: need %zu bytes", fp32_ws_bytes(np));
     const MlpBlobHeader h = blob_layout(SURS_BF16);
-    PointSource src;
-    memset(&src, 0, sizeof(src));
-    src.mode = 0;
+    PointSource src = point_source(0, 0, 0, nullptr, calib, zmul, zdiv);
     src.pts = points;
     src.ld = n;
-    fill_calib(src, calib, zmul, zdiv);
     Fp32Workspace w = carve_fp32(workspace, np);
     int rc = zero_pad_rows(st, w);
     if (rc) return rc;
@@ -900,13 +905,10 @@ extern "C" int surs_query_points_views(const float *points, int n, int num_views
                  views_ws_bytes(np, num_views));
     std::vector<PointSource> srcs((size_t)num_views);
     for (int v = 0; v < num_views; ++v) {
-        PointSource &src = srcs[v];
-        memset(&src, 0, sizeof(src));
-        src.mode = 0;
+        PointSource &src = srcs[v] = point_source(0, 0, 0, nullptr, calibs + 12 * v, zmul, zdiv);
         src.pts = points + (size_t)v * 3 * n;
         src.ld = n;
         src.persp = projection;
-        fill_calib(src, calibs + 12 * v, zmul, zdiv);
     }
     return run_points_views(as_stream(stream), srcs.data(), n, num_views, feat_lr, hl, wl, feat_hr, hh, wh, mlp_blob, workspace, pred_hr,
                             pred_lr, logit_hr, logit_lr);
@@ -939,15 +941,9 @@ extern "C" int surs_query_grid_views(int i0, int i1, int ry, int rz, const doubl
     for (long long b0 = 0; b0 < total; b0 += VIEWS_GRID_BATCH) {
         const int nb = (int)((total - b0 < VIEWS_GRID_BATCH) ? total - b0 : VIEWS_GRID_BATCH);
         for (int v = 0; v < V; ++v) {
-            PointSource &src = srcs[v];
-            memset(&src, 0, sizeof(src));
-            src.mode = 1;
+            PointSource &src = srcs[v] = point_source(1, ry, rz, mat, calibs + 12 * v, zmul, zdiv);
             src.base = (long long)i0 * ry * rz + b0;
-            src.ry = ry;
-            src.rz = rz;
             src.persp = projection;
-            for (int i = 0; i < 12; ++i) src.mat[i] = mat[i];
-            fill_calib(src, calibs + 12 * v, zmul, zdiv);
         }
         const int rc = run_points_views(st, srcs.data(), nb, V, feat_lr, hl, wl, feat_hr, hh, wh, mlp_blob, workspace, ph, pl, nullptr,
                                         nullptr);
@@ -969,8 +965,8 @@ struct GridProf {
     bool on = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
     std::vector<double> pts;
-    std::map<int, unsigned long long *> kstat;   // per device: counter of the residual k-steps of column kernels v7 / v8 (executed-FLOP statistic)
-    double tiles = 0;                      // (z tile, MLP) pairs the timed v7 launches processed
+    std::map<int, unsigned long long *> kstat;   // per device: counter of the residual k-steps of the restated column kernels (executed-FLOP statistic)
+    double tiles = 0;                      // (z tile, MLP) pairs the timed launches of the restated kernels processed
 } g_prof;
 }  // namespace
 
@@ -1008,7 +1004,7 @@ extern "C" int surs_profile_read(double *launches, double *total_ms, double *poi
     return 0;
 }
 
-// Column kernel v7 runs a data-dependent number of layer-1 k-steps; while profiling is enabled it adds them up.  Returns the
+// The restated column kernels run a data-dependent number of layer-1 k-steps; while profiling is enabled they add them up.  Returns the
 // number of (z tile, MLP) pairs the timed launches processed and the residual k-steps (16 listed channels each) they ran -
 // the affine k-step every pair runs is not counted.  Call before surs_profile_read (which resets the counters).
 extern "C" int surs_profile_read_ksteps(double *tile_mlps, double *ksteps) {
@@ -1035,18 +1031,67 @@ static const long long GRID_BATCH = 65536;
 #endif
 static const long long COL_BATCH = SURS_COL_BATCH;
 
-static size_t col_base_bytes(long long ncb) {
-    // F rows 0..335 for the column gather + CC + mask
-    return (size_t)ncb * (C0PAD + CC_PAD + 1) * sizeof(float) + (size_t)ncb * C0PAD * 6 + 4096;   // + split image of F
+// The workspace of one column batch, for every user of it: dense sweeps, octree levels, point runs and the probe.  carve_columns is
+// the only place that knows where a region lies and how large it is; the sizes the ABI reports are what it adds up.
+struct ColumnWorkspace {
+    // the regions, in address order, each sized for COL_BATCH columns
+    float *F;                      // gathered features [C0PAD][COL_BATCH] (rows 0 .. 335 of the column gather)
+    float *CC;                     // column constants [COL_BATCH][CC_PAD]
+    float *cmask;                  // in-image mask [COL_BATCH]
+    unsigned short *Fs;            // split image of F (up to three parts), then 4096 bytes nobody uses
+    unsigned short *g_lr, *g_hr;   // the g image: split images (up to three parts) of the lr classifier's two and the hr classifier's
+                                   // three g-scaled vectors per column, written by colsum_prepare_kernel for the R GEMMs alone
+    float *r_lr, *r_hr;            // R vectors [COL_BATCH][2 | 3][D2]
+    float *zero_bias;              // [D2], the R GEMMs' bias
+    unsigned *colctr;              // 64 work counters, right behind the bias: one memset clears both
+    size_t g_image_bytes, bytes;   // g_lr + g_hr; everything
+    // overlays: regions that are free while their user runs
+    int *ovf_list;                 // over the g image from its start, after the R GEMMs have read it: kernel 12's overflow list
+    char *aimg_base;               // over the g image: kernel 12's per-workgroup fragment images, behind that list's room (v12_fragment_images)
+    unsigned long long *probe_ctr; // over the g image's first 16 bytes: the probe's two sums (it computes no R)
+};
+
+static ColumnWorkspace carve_columns(void *ws) {
+    const size_t n = (size_t)COL_BATCH;
+    ColumnWorkspace w;
+    size_t o = 0;
+    auto take = [&](auto *&p, size_t bytes) {
+        p = (std::remove_reference_t<decltype(p)>)((uintptr_t)ws + o);
+        o += bytes;
+    };
+    take(w.F, n * C0PAD * sizeof(float));
+    take(w.CC, n * CC_PAD * sizeof(float));
+    take(w.cmask, n * sizeof(float));
+    take(w.Fs, n * C0PAD * 6 + 4096);
+    const size_t g0 = o;
+    take(w.g_lr, n * 2 * D1 * 6);
+    take(w.g_hr, n * 3 * D1 * 6);
+    w.g_image_bytes = o - g0;
+    take(w.r_lr, n * 2 * D2 * sizeof(float));
+    take(w.r_hr, n * 3 * D2 * sizeof(float));
+    take(w.zero_bias, D2 * sizeof(float));
+    take(w.colctr, 256);
+    w.bytes = o;
+    w.ovf_list = (int *)w.g_lr;
+    w.aimg_base = (char *)w.g_lr;
+    w.probe_ctr = (unsigned long long *)w.g_lr;
+    return w;
 }
-// restated column kernels: split images of the five g-scaled vectors per column (up to three parts), the five R vectors, a zero bias
-static size_t col_v7_image_bytes(long long ncb) { return (size_t)ncb * 5 * D1 * 6; }
-static size_t col_v7_bytes(long long ncb) { return col_v7_image_bytes(ncb) + (size_t)ncb * 5 * D2 * 4 + D2 * 4 + 256; }
-static size_t col_ws_bytes(long long ncb) { return col_base_bytes(ncb) + col_v7_bytes(ncb); }
+static size_t col_ws_bytes() { return carve_columns(nullptr).bytes; }
+
+// Kernel 12's overlay on the g image: room for the overflow list at its fullest (every z tile of every column, two ints each, in
+// whole 4 KiB pages), then one fragment image per workgroup.
+static int v12_fragment_images(const ColumnWorkspace &w, long long nc, int items, unsigned workgroups, char *&aimg) {
+    const size_t ovf_room = ((size_t)nc * ((items + 127) / 128) * 2 * sizeof(int) + 4095) / 4096 * 4096;
+    SURS_REQUIRE(ovf_room + (size_t)workgroups * V12_AIMG_BYTES <= w.g_image_bytes,
+                 "kernel v12's overflow list and fragment images do not fit the g-scaled split image");
+    aimg = w.aimg_base + ovf_room;
+    return 0;
+}
 
 extern "C" size_t surs_query_grid_workspace_bytes(int ry, int rz, int dtype) {
     (void)ry; (void)rz;
-    const size_t col = col_ws_bytes(COL_BATCH);
+    const size_t col = col_ws_bytes();
     if (dtype == SURS_F32 || dtype == SURS_F32_GEMM) {   // column kernel v5 where the sweep allows it, the layer kernels otherwise
         const size_t gen = fp32_ws_bytes(GRID_BATCH);
         return gen > col ? gen : col;
@@ -1072,27 +1117,31 @@ static int grid_set_attributes() {
 }
 
 // Column constants of a batch of columns (src.mode = 2, src.base = first column): F = gathered features, cmask, and
-// CC[col][2944] = Wc^T F[:, col] + bc - the layer kernel in its transposed-output form on the split image of F.  Workspace
-// carved by the caller (col_base_bytes).
+// CC[col][2944] = Wc^T F[:, col] + bc - the layer kernel in its transposed-output form on the split image of F.
 static int column_constants(hipStream_t st, const PointSource &src, long long nc, long long ncp, const float *feat_lr, int hl, int wl,
-                            const float *feat_hr, int hh, int wh, const char *blob, const MlpBlobHeader &h, float *F, float *CC,
-                            float *cmask) {
+                            const float *feat_hr, int hh, int wh, const char *blob, const MlpBlobHeader &h, const ColumnWorkspace &w) {
     const int parts = split_parts();
-    unsigned short *Fs = (unsigned short *)(cmask + COL_BATCH);
     const long long fs_part = (long long)C0PAD * COL_BATCH;
     const dim3 gg((unsigned)ceil_div(nc, 64), nc <= 4096 ? 5u : 1u);
     with_parts<2, 3>(parts, [&](auto NP) {
-        hipLaunchKernelGGL(gather_kernel<NP>, gg, dim3(256), 0, st, src, nc, feat_lr, hl, wl, feat_hr, hh, wh, F, COL_BATCH, cmask,
-                           (float *)nullptr, Fs, fs_part);
+        hipLaunchKernelGGL(gather_kernel<NP>, gg, dim3(256), 0, st, src, nc, feat_lr, hl, wl, feat_hr, hh, wh, w.F, COL_BATCH, w.cmask,
+                           (float *)nullptr, w.Fs, fs_part);
     });
     SURS_LAUNCH_CHECK();
-    const SplitSeg f = {Fs, fs_part, C_G / 16}, none = {nullptr, 0, 0};
+    const SplitSeg f = {w.Fs, fs_part, C_G / 16}, none = {nullptr, 0, 0};
     return launch_layer(st, parts, G3_F32_T, blob + (parts == 2 ? h.wc2 : h.wc3), CC_PAD, f, none, COL_BATCH, ncp,
-                        (const float *)(blob + h.bc), CC, nullptr);
+                        (const float *)(blob + h.bc), w.CC, nullptr);
 }
 
-// One workgroup per column: how many layer-0 channels the restated column kernels (v7 / v8) would list per z tile - the
-// classification of grid_mlp_v7 with the hr classifier's p range taken as [0, 1] (an upper bound).  out[0] += lr, out[1] += hr.
+// zf at voxel kmid of a column: where the restated kernels take the per-column LeakyReLU branches g_c, and the probe with them (any
+// depth serves - the restated layer 1 is an identity for every choice).  mat null: no grid (point runs), world z = 0.
+static float column_zmid(const double *mat, const float *calib, int kmid, float zmul, float zdiv) {
+    const float zw = mat ? (float)(mat[10] * (double)kmid + mat[11]) : 0.0f;
+    return (calib[11] + calib[10] * zw) * zmul / zdiv;
+}
+
+// One workgroup per column: how many layer-0 channels the restated column kernels (10 / 11 / 12) would list per z tile - their
+// classification with the hr classifier's p range taken as [0, 1] (an upper bound).  out[0] += lr, out[1] += hr.
 __global__ __launch_bounds__(256) void probe_count_kernel(const float *__restrict__ cc, const float *__restrict__ zvec, int rz, int tile,
                                                           double z0, double dz, float c22, float c23, float zmul, float zdiv, float zmid,
                                                           unsigned long long *__restrict__ out) {
@@ -1138,41 +1187,8 @@ __global__ __launch_bounds__(256) void probe_count_kernel(const float *__restric
     }
 }
 
-static int query_grid_impl(int i0, int i1, int ry, int rz, const double *mat, const float *calib, float zmul,
-                           float zdiv, const float *feat_lr, int hl, int wl, const float *feat_hr, int hh, int wh,
-                           const void *mlp_blob, int dtype, void *workspace, size_t workspace_bytes, float *vol_hr,
-                           float *vol_lr, int kernel_call, void *stream);
-
-extern "C" int surs_query_grid_opt(int i0, int i1, int ry, int rz, const double *mat, const float *calib, float zmul,
-                                   float zdiv, const float *feat_lr, int hl, int wl, const float *feat_hr, int hh, int wh,
-                                   const void *mlp_blob, int dtype, void *workspace, size_t workspace_bytes, float *vol_hr,
-                                   float *vol_lr, const SursGridOptions *opt, void *stream) {
-    int kernel = 0, parts = 0;
-    if (opt) {
-        kernel = opt->kernel;
-        parts = opt->operand_parts;
-        SURS_REQUIRE(grid_kernel_known(kernel), "SursGridOptions.kernel: 0, 3, 10, 12 (reduced precision), 5, 11 (fp32-grade)");
-        SURS_REQUIRE(parts == 0 || parts == 2 || parts == 3, "SursGridOptions.operand_parts: 0, 2 or 3");
-    }
-    // the operand split is read deep inside the launch helpers: scoped to this call and this thread, the process setting
-    // (surs_set_operand_split) is neither read nor changed when the caller gave one
-    const int saved = t_split_call;
-    if (parts) t_split_call = parts;
-    const int rc = query_grid_impl(i0, i1, ry, rz, mat, calib, zmul, zdiv, feat_lr, hl, wl, feat_hr, hh, wh, mlp_blob, dtype, workspace,
-                                   workspace_bytes, vol_hr, vol_lr, kernel, stream);
-    t_split_call = saved;
-    return rc;
-}
-
-extern "C" int surs_query_grid(int i0, int i1, int ry, int rz, const double *mat, const float *calib, float zmul,
-                               float zdiv, const float *feat_lr, int hl, int wl, const float *feat_hr, int hh, int wh,
-                               const void *mlp_blob, int dtype, void *workspace, size_t workspace_bytes, float *vol_hr,
-                               float *vol_lr, void *stream) {
-    return query_grid_impl(i0, i1, ry, rz, mat, calib, zmul, zdiv, feat_lr, hl, wl, feat_hr, hh, wh, mlp_blob, dtype, workspace,
-                           workspace_bytes, vol_hr, vol_lr, 0, stream);
-}
-
-// What every column batch of one sweep shares (dense sweeps: query_grid_impl; lattice sweeps: surs_octree_level_columns).
+// What every column batch of one sweep shares (dense sweeps: query_grid_impl; lattice sweeps: surs_octree_level_columns; point runs:
+// surs_query_points_columns).  Built by begin_column_sweep.
 namespace {
 struct ColumnSweep {
     hipStream_t st;
@@ -1180,7 +1196,7 @@ struct ColumnSweep {
     MlpBlobHeader h;
     int dtype;            // SURS_F32 / SURS_BF16 / SURS_F16
     int kver, kver32;     // column kernel of the reduced precisions / of SURS_F32
-    bool restated;
+    bool restated() const { return dtype == SURS_F32 ? kver32 == 11 : (kver == 10 || kver == 12); }
     const float *feat_lr; int hl, wl;
     const float *feat_hr; int hh, wh;
     const double *mat; const float *calib; float zmul, zdiv;
@@ -1221,147 +1237,186 @@ static int device_cus() {
     return 256;
 }
 
-// One batch of nc <= COL_BATCH columns described by src (mode 2: consecutive columns from src.base; mode 4: listed columns):
-// gather + column constants, the restated kernels' per-column affine part, then the column kernel over `items` z items per column
-// (dense: the voxels 0 .. items - 1; lattice sweeps: the kcount[column] listed voxels klist[column][.] * zstride).  vol_*: [nc][items].
-static int run_column_batch(const ColumnSweep &cs, const PointSource &src, long long nc, int items, int zstride,
-                            const int *kcount, const unsigned short *klist, float *vol_hr, float *vol_lr, bool trace_this) {
+// The sweep of one call on the restated eight-wave kernels (10 / 11), kmid 0, no runs: the caller changes what differs.  Sets the
+// column kernels' LDS attributes on first use.
+static int begin_column_sweep(ColumnSweep &cs, hipStream_t st, const void *mlp_blob, int dtype, const float *feat_lr, int hl, int wl,
+                              const float *feat_hr, int hh, int wh, const double *mat, const float *calib, float zmul, float zdiv,
+                              void *workspace) {
+    cs.st = st;
+    cs.blob = (const char *)mlp_blob;
+    cs.h = blob_layout((uint32_t)dtype);
+    cs.dtype = dtype; cs.kver = 10; cs.kver32 = 11;
+    cs.feat_lr = feat_lr; cs.hl = hl; cs.wl = wl;
+    cs.feat_hr = feat_hr; cs.hh = hh; cs.wh = wh;
+    cs.mat = mat; cs.calib = calib; cs.zmul = zmul; cs.zdiv = zdiv;
+    cs.workspace = workspace;
+    cs.cus = device_cus();
+    cs.kmid = 0;
+    return grid_set_attributes();
+}
+
+// f(DT) with the sweep's 16-bit dtype as a compile-time constant (with_parts' way)
+template <class F> static void with_half(int dtype, F &&f) {
+    if (dtype == SURS_BF16) f(std::integral_constant<int, SURS_BF16>());
+    else f(std::integral_constant<int, SURS_F16>());
+}
+
+// Step 2 of a restated batch, the affine part of layer 1: R = W1 (g . [a0 | w0z | w0p]) of the batch's columns into w.r_lr / w.r_hr,
+// behind a memset that clears the work counters (and the zero bias where a GEMM reads it).  Three paths, the same bits.
+static int column_affine_part(const ColumnSweep &cs, const ColumnWorkspace &w, long long ncp, float zmid) {
     hipStream_t st = cs.st;
     const char *blob = cs.blob;
     const MlpBlobHeader &h = cs.h;
-    const int dtype = cs.dtype, kver = cs.kver, kver32 = cs.kver32;
-    const bool restated = cs.restated;
-    const double *mat = cs.mat;
-    const float *calib = cs.calib;
-    void *workspace = cs.workspace;
-    float *F = (float *)workspace;
-    float *CC = F + (size_t)C0PAD * COL_BATCH;
-    float *cmask = CC + (size_t)CC_PAD * COL_BATCH;
     int rc = 0;
-    const long long ncp = (long long)ceil_div(nc, 256) * 256;   // <= COL_BATCH; rows nc.. of CC are never read
-    const int parts = split_parts();
-    if ((rc = column_constants(st, src, nc, ncp, cs.feat_lr, cs.hl, cs.wl, cs.feat_hr, cs.hh, cs.wh, blob, h, F, CC, cmask))) return rc;
-    GridArgs a;
-    a.cc = CC;
-    a.colmask = cmask;
-    a.zvec = (const float *)(blob + h.zvec);
-    a.core = blob + h.core;
-    a.corex = blob + h.corex;
-    a.b1frag = blob + h.b1frag;
-    a.b1_inv_scale = 1.0f / (dtype == SURS_F16 ? B1FRAG_SCALE_F16 : B1FRAG_SCALE_BF16);
-    a.w1t = blob + h.w1t;
-    a.w1tx = blob + h.w1tx;
-    a.rvec_lr = a.rvec_hr = nullptr;
-    a.rld_lr = a.rld_hr = 0;
-    a.colctr = nullptr;
-    a.phase = 0;
-    a.zmid = 0.0f;
-    a.zstride = zstride;
-    a.kcount = kcount;
-    a.klist = klist;
-    a.ovf_count = nullptr;
-    a.ovf_list = nullptr;
-    a.aimg = nullptr;
-    a.tile_list = cs.run_tiles;
-    a.tile_count = cs.run_ntiles;
-    a.colstart = cs.run_colstart;
-    a.zpts = cs.run_z;
-    if (restated) {
-        // the affine part of layer 1: R = W1 (g . [a0 | w0z | w0p]) for the batch's columns, on the layer GEMM kernel
-        char *v7 = (char *)workspace + col_base_bytes(COL_BATCH);
-        unsigned short *g_lr = (unsigned short *)v7, *g_hr = g_lr + (size_t)COL_BATCH * 2 * D1 * 3;
-        float *r_lr = (float *)(v7 + col_v7_image_bytes(COL_BATCH)), *r_hr = r_lr + (size_t)COL_BATCH * 2 * D2;
-        float *zero_bias = r_hr + (size_t)COL_BATCH * 3 * D2;
-        a.colctr = (unsigned *)(zero_bias + D2);
-        {
-            // (any depth serves - the restated layer 1 is an identity for every choice -; point runs have no grid: world z = 0)
-            const float zw = cs.run_z ? 0.0f : (float)(mat[10] * (double)cs.kmid + mat[11]);
-            a.zmid = (calib[11] + calib[10] * zw) * cs.zmul / cs.zdiv;
-        }
-        const long long part_lr = 2LL * ncp * D1, part_hr = 3LL * ncp * D1;
-        const dim3 pg((unsigned)(ncp / 4));   // four columns per workgroup, a wave per column
-        // operand parts of this GEMM: the sweep's split (two f16 / three bf16 parts: fp32 grade) for the fp32-grade and the f16
-        // kernel; ONE f16 part for the bf16 kernel - 11 significant bits, 8x what bf16 gives the rest of the classifier, a third
-        // of the MFMA work, no measurable change of the bf16 sweep's error (SURS_R_PARTS=0: the split's parts there too)
-        const int r_parts_env = option(OPT_R_PARTS);
-        const int rparts = (dtype == SURS_BF16 && r_parts_env == 1) ? 1 : parts;
+    const float *zvec = (const float *)(blob + h.zvec);
+    // operand parts of this GEMM: the sweep's split (two f16 / three bf16 parts: fp32 grade) for the fp32-grade and the f16
+    // kernel; ONE f16 part for the bf16 kernel - 11 significant bits, 8x what bf16 gives the rest of the classifier, a third
+    // of the MFMA work, no measurable change of the bf16 sweep's error (SURS_R_PARTS=0: the split's parts there too)
+    const int rparts = (cs.dtype == SURS_BF16 && option(OPT_R_PARTS) == 1) ? 1 : split_parts();
+    if (rparts == 1 && ncp > 1024 && option(OPT_R_FUSED)) {
         // the bf16 sweep's large batches: one kernel forms the g-scaled operand itself (rvec_fused_kernel; r_fused = 0: the image +
         // two GEMM launches, same bits); it needs neither the image nor the zero bias, only the column counters behind it
-        const bool fused = rparts == 1 && ncp > 1024 && option(OPT_R_FUSED);
-        if (fused) SURS_HIP_CHECK(hipMemsetAsync(a.colctr, 0, 256, st));
-        else SURS_HIP_CHECK(hipMemsetAsync(zero_bias, 0, D2 * 4 + 256, st));   // + the column counters behind it
-        if (!fused) {
-            with_parts<1, 2, 3>(rparts, [&](auto NP) {
-                hipLaunchKernelGGL(colsum_prepare_kernel<NP>, pg, dim3(256), 0, st, CC, (const float *)(blob + h.zvec), (int)ncp, a.zmid,
-                                   g_lr, part_lr, g_hr, part_hr);
-            });
-            SURS_LAUNCH_CHECK();
+        SURS_HIP_CHECK(hipMemsetAsync(w.colctr, 0, 256, st));
+        RvecFusedArgs fa;
+        fa.cc = w.CC;
+        fa.zvec = zvec;
+        fa.zmid = zmid;
+        fa.tiles = (int)(ncp / RVF_COLS);   // (ncp is a multiple of 256)
+        for (int m = 0; m < 2; ++m) {
+            fa.w[m] = (const unsigned short *)(blob + h.wt2[m][1]);
+            fa.r[m] = m ? w.r_hr : w.r_lr;
         }
-        if (fused) {
-            RvecFusedArgs fa;
-            fa.cc = CC;
-            fa.zvec = (const float *)(blob + h.zvec);
-            fa.zmid = a.zmid;
-            fa.tiles = (int)(ncp / RVF_COLS);   // (ncp is a multiple of 256)
-            for (int m = 0; m < 2; ++m) {
-                fa.w[m] = (const unsigned short *)(blob + h.wt2[m][1]);
-                fa.r[m] = m ? r_hr : r_lr;
-            }
-            if ((rc = g3_set_attributes())) return rc;
-            hipLaunchKernelGGL(rvec_fused_kernel, dim3(gemm_grid(D2 / RVF_ROWS, fa.tiles)), dim3(RVF_THREADS), RVF_LDS_BYTES, st, fa);
-            SURS_LAUNCH_CHECK();
-        } else if (ncp <= 1024 && option(OPT_RVEC_SMALL)) {
-            // small batches (the ~ 100 runs of a point-runs call, small slabs, coarse octree levels): both classifiers in one launch of
-            // 64-point x 128-row workgroups (rvec_small_kernel: the same bits as the 256 x 256-tile GEMM below, 4 - 6 workgroups of which
-            // walk K = 1024 in 34 - 62 us each here)
-            RvecSmallArgs ra;
-            for (int m = 0; m < 2; ++m) {
-                const int nvec = m ? 3 : 2;
-                ra.w[m] = (const unsigned short *)(blob + (rparts == 3 ? h.wt3[m][1] : h.wt2[m][1]));
-                ra.g[m] = m ? g_hr : g_lr;
-                ra.g_part[m] = m ? part_hr : part_lr;
-                ra.npm[m] = (long long)nvec * ncp;
-                ra.r[m] = m ? r_hr : r_lr;
-            }
-            ra.wgs0 = (int)(ra.npm[0] / 64) * 4;
-            const unsigned wgs = (unsigned)(ra.wgs0 + (ra.npm[1] / 64) * 4);
-            with_parts<1, 2, 3>(rparts, [&](auto NP) { hipLaunchKernelGGL(rvec_small_kernel<NP>, dim3(wgs), dim3(256), 0, st, ra); });
-            SURS_LAUNCH_CHECK();
-        } else {
-            // output R[column][vector][512] (transposed; the kernel swaps the MFMA operands so that its stores run along the rows);
-            // one part: the first plane of the two-part weight image is f16(w)
-            const SplitSeg none = {nullptr, 0, 0};
-            for (int m = 0; m < 2; ++m) {
-                const long long npm = (m ? 3LL : 2LL) * ncp;   // points = vectors x columns
-                const SplitSeg g = {m ? g_hr : g_lr, m ? part_hr : part_lr, D1 / 16};
-                if ((rc = launch_layer(st, rparts, G3_F32_T, blob + (rparts == 3 ? h.wt3[m][1] : h.wt2[m][1]), D2, g, none, npm, npm,
-                                       zero_bias, m ? r_hr : r_lr, nullptr)))
-                    return rc;
-            }
-        }
-        a.rvec_lr = r_lr;
-        a.rvec_hr = r_hr;
-        a.rld_lr = a.rld_hr = 0;
+        if ((rc = g3_set_attributes())) return rc;
+        hipLaunchKernelGGL(rvec_fused_kernel, dim3(gemm_grid(D2 / RVF_ROWS, fa.tiles)), dim3(RVF_THREADS), RVF_LDS_BYTES, st, fa);
+        SURS_LAUNCH_CHECK();
+        return 0;
     }
-    a.vol_hr = vol_hr;
-    a.vol_lr = vol_lr;
-    a.ncols = (int)nc;
-    a.rz = items;
-    a.z0 = mat ? mat[11] : 0.0;
-    a.dz = mat ? mat[10] : 0.0;
-    a.c22 = calib[10];
-    a.c23 = calib[11];
-    a.zmul = cs.zmul;
-    a.zdiv = cs.zdiv;
-    const long long nwork = cs.run_tiles ? cs.run_ntiles_host : nc;   // work items the column counter hands out
-    const unsigned grid = (unsigned)((nwork < cs.cus) ? nwork : cs.cus);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    bool prof;
-    a.kstat = nullptr;
+    SURS_HIP_CHECK(hipMemsetAsync(w.zero_bias, 0, D2 * 4 + 256, st));   // + the column counters behind it
+    const long long part_lr = 2LL * ncp * D1, part_hr = 3LL * ncp * D1;
+    const dim3 pg((unsigned)(ncp / 4));   // four columns per workgroup, a wave per column
+    with_parts<1, 2, 3>(rparts, [&](auto NP) {
+        hipLaunchKernelGGL(colsum_prepare_kernel<NP>, pg, dim3(256), 0, st, w.CC, zvec, (int)ncp, zmid, w.g_lr, part_lr, w.g_hr, part_hr);
+    });
+    SURS_LAUNCH_CHECK();
+    if (ncp <= 1024 && option(OPT_RVEC_SMALL)) {
+        // small batches (the ~ 100 runs of a point-runs call, small slabs, coarse octree levels): both classifiers in one launch of
+        // 64-point x 128-row workgroups (rvec_small_kernel: the same bits as the 256 x 256-tile GEMM below, 4 - 6 workgroups of which
+        // walk K = 1024 in 34 - 62 us each here)
+        RvecSmallArgs ra;
+        for (int m = 0; m < 2; ++m) {
+            const int nvec = m ? 3 : 2;
+            ra.w[m] = (const unsigned short *)(blob + (rparts == 3 ? h.wt3[m][1] : h.wt2[m][1]));
+            ra.g[m] = m ? w.g_hr : w.g_lr;
+            ra.g_part[m] = m ? part_hr : part_lr;
+            ra.npm[m] = (long long)nvec * ncp;
+            ra.r[m] = m ? w.r_hr : w.r_lr;
+        }
+        ra.wgs0 = (int)(ra.npm[0] / 64) * 4;
+        const unsigned wgs = (unsigned)(ra.wgs0 + (ra.npm[1] / 64) * 4);
+        with_parts<1, 2, 3>(rparts, [&](auto NP) { hipLaunchKernelGGL(rvec_small_kernel<NP>, dim3(wgs), dim3(256), 0, st, ra); });
+        SURS_LAUNCH_CHECK();
+        return 0;
+    }
+    // the layer GEMM kernel: output R[column][vector][512] (transposed; the kernel swaps the MFMA operands so that its stores run
+    // along the rows); one part: the first plane of the two-part weight image is f16(w)
+    const SplitSeg none = {nullptr, 0, 0};
+    for (int m = 0; m < 2; ++m) {
+        const long long npm = (m ? 3LL : 2LL) * ncp;   // points = vectors x columns
+        const SplitSeg g = {m ? w.g_hr : w.g_lr, m ? part_hr : part_lr, D1 / 16};
+        if ((rc = launch_layer(st, rparts, G3_F32_T, blob + (rparts == 3 ? h.wt3[m][1] : h.wt2[m][1]), D2, g, none, npm, npm, w.zero_bias,
+                               m ? w.r_hr : w.r_lr, nullptr)))
+            return rc;
+    }
+    return 0;
+}
+
+// Step 3: the column kernels' arguments.  Everything a sweep does not use stays zero / null.
+static GridArgs column_grid_args(const ColumnSweep &cs, const ColumnWorkspace &w, float zmid, long long nc, int items, int zstride,
+                                 const int *kcount, const unsigned short *klist, float *vol_hr, float *vol_lr) {
+    const char *blob = cs.blob;
+    const MlpBlobHeader &h = cs.h;
+    GridArgs a = {};
+    a.cc = w.CC; a.colmask = w.cmask;
+    a.zvec = (const float *)(blob + h.zvec);
+    a.core = blob + h.core; a.corex = blob + h.corex;
+    a.b1frag = blob + h.b1frag;
+    a.b1_inv_scale = 1.0f / (cs.dtype == SURS_F16 ? B1FRAG_SCALE_F16 : B1FRAG_SCALE_BF16);
+    a.w1t = blob + h.w1t; a.w1tx = blob + h.w1tx;
+    if (cs.restated()) {
+        a.rvec_lr = w.r_lr; a.rvec_hr = w.r_hr;
+        a.zmid = zmid;
+        a.colctr = w.colctr;
+    }
+    a.vol_hr = vol_hr; a.vol_lr = vol_lr;
+    a.ncols = (int)nc; a.rz = items;
+    a.zstride = zstride; a.kcount = kcount; a.klist = klist;
+    a.colstart = cs.run_colstart; a.zpts = cs.run_z;
+    a.tile_list = cs.run_tiles; a.tile_count = cs.run_ntiles;
+    a.z0 = cs.mat ? cs.mat[11] : 0.0; a.dz = cs.mat ? cs.mat[10] : 0.0;
+    a.c22 = cs.calib[10]; a.c23 = cs.calib[11];
+    a.zmul = cs.zmul; a.zdiv = cs.zdiv;
+    return a;
+}
+
+// workgroups of a column launch: one per compute unit, or per work item the column counter hands out where those are fewer
+static unsigned column_grid(const ColumnSweep &cs, long long nc) {
+    const long long nwork = cs.run_tiles ? cs.run_ntiles_host : nc;
+    return (unsigned)((nwork < cs.cus) ? nwork : cs.cus);
+}
+
+// Step 4: the column kernel of (dtype, kver / kver32) over the batch.
+static int launch_column_kernel(const ColumnSweep &cs, const ColumnWorkspace &w, GridArgs a, long long nc, int items) {
+    hipStream_t st = cs.st;
+    const unsigned grid = column_grid(cs, nc);
+    if (cs.dtype == SURS_F32) {
+        if (cs.kver32 == 11) {
+            // two passes over the batch (lr, then hr on the lr occupancies just written): each pass streams ONE classifier's
+            // split weights (2.6 MiB), which an XCD's 4 MiB L2 holds; both together do not fit and 8 % of the stream came from
+            // HBM.  Only with whole 64-voxel tiles (the hr pass reads its tile's lr occupancies back from vol_lr, which has no
+            // room for the voxels beyond the column's end that the one-pass form computes and classifies on); same bits.
+            const bool two = option(OPT_GRID_F32_PASSES) == 2 && items % 64 == 0 && !cs.run_tiles;
+            for (int ph = two ? 1 : 0; ph <= (two ? 2 : 0); ++ph) {
+                a.phase = ph;
+                hipLaunchKernelGGL(grid_mlp_kernel_v11, dim3(grid), dim3(V11_THREADS), GRID11_LDS_BYTES, st, a);
+            }
+        } else
+            hipLaunchKernelGGL(grid_mlp_kernel_v5, dim3(grid), dim3(256), GRID5_LDS_BYTES, st, a);
+    } else if (cs.kver == 12) {
+        // two workgroups of four waves per compute unit; its overflow list and fragment images lie over the g image, which the R
+        // GEMMs of step 2 were the last to read
+        const unsigned grid12 = (unsigned)((nc < 2 * cs.cus) ? nc : 2 * cs.cus);
+        a.ovf_count = a.colctr + 1;
+        a.ovf_list = w.ovf_list;
+        const int rc = v12_fragment_images(w, nc, items, grid12, a.aimg);
+        if (rc) return rc;
+        with_half(cs.dtype, [&](auto DT) { hipLaunchKernelGGL(grid_mlp_kernel_v12<DT>, dim3(grid12), dim3(V12_THREADS), GRID12_LDS_BYTES, st, a); });
+        SURS_LAUNCH_CHECK();
+        // the tiles it left: kernel v10 over the list (an empty list costs one launch of workgroups that leave at once)
+        GridArgs b = a;
+        b.tile_list = a.ovf_list;
+        b.tile_count = a.ovf_count;
+        b.colctr = a.colctr + 2;
+        with_half(cs.dtype, [&](auto DT) { hipLaunchKernelGGL(grid_mlp_kernel_v10<DT>, dim3(grid), dim3(V10_THREADS), GRID10_LDS_BYTES, st, b); });
+    } else if (cs.kver == 10) {
+        with_half(cs.dtype, [&](auto DT) { hipLaunchKernelGGL(grid_mlp_kernel_v10<DT>, dim3(grid), dim3(V10_THREADS), GRID10_LDS_BYTES, st, a); });
+    } else {
+        with_half(cs.dtype, [&](auto DT) { hipLaunchKernelGGL(grid_mlp_kernel_v3<DT>, dim3(grid), dim3(256), GRID3_LDS_BYTES, st, a); });
+    }
+    SURS_LAUNCH_CHECK();
+    return 0;
+}
+
+// The profiling bracket of a dense batch's column launches (surs_profile_enable; the bench's per-launch figures are those of dense
+// sweeps): a pair of events on the sweep's stream and, for the restated kernels, the device's k-step counter in a.kstat.
+struct LaunchTimer {
+    hipEvent_t e0 = nullptr, e1 = nullptr;   // null: profiling is off
+};
+
+static int prof_begin(LaunchTimer &t, const ColumnSweep &cs, bool dense, long long nc, int items, GridArgs &a) {
     {
         std::lock_guard<std::mutex> lock(g_prof.mu);
-        prof = g_prof.on && !kcount;   // (the bench's per-launch figures are those of dense sweeps)
-        if (prof && restated) {
+        if (!(g_prof.on && dense)) return 0;
+        if (cs.restated()) {
             int dev = 0;
             SURS_HIP_CHECK(hipGetDevice(&dev));
             unsigned long long *&ctr = g_prof.kstat[dev];
@@ -1370,139 +1425,91 @@ static int run_column_batch(const ColumnSweep &cs, const PointSource &src, long 
                 SURS_HIP_CHECK(hipMemset(ctr, 0, sizeof(unsigned long long)));
             }
             a.kstat = ctr;
-            g_prof.tiles += 2.0 * (double)nc * (dtype == SURS_F32 ? (items + 63) / 64 : (items + 127) / 128);
+            g_prof.tiles += 2.0 * (double)nc * (cs.dtype == SURS_F32 ? (items + 63) / 64 : (items + 127) / 128);
         }
     }
-    if (prof) {
-        SURS_HIP_CHECK(hipEventCreate(&e0));
-        SURS_HIP_CHECK(hipEventCreate(&e1));
-        SURS_HIP_CHECK(hipEventRecord(e0, st));
-    }
-    if (dtype == SURS_F32) {
-        if (kver32 == 11) {
-            // two passes over the batch (lr, then hr on the lr occupancies just written): each pass streams ONE classifier's
-            // split weights (2.6 MiB), which an XCD's 4 MiB L2 holds; both together do not fit and 8 % of the stream came from
-            // HBM.  Only with whole 64-voxel tiles (the hr pass reads its tile's lr occupancies back from vol_lr, which has no
-            // room for the voxels beyond the column's end that the one-pass form computes and classifies on); same bits.
-            const int passes_env = option(OPT_GRID_F32_PASSES);
-            const bool two = passes_env == 2 && items % 64 == 0 && !cs.run_tiles;
-            for (int ph = two ? 1 : 0; ph <= (two ? 2 : 0); ++ph) {
-                a.phase = ph;
-                hipLaunchKernelGGL(grid_mlp_kernel_v11, dim3(grid), dim3(V11_THREADS), GRID11_LDS_BYTES, st, a);
-            }
-        } else
-            hipLaunchKernelGGL(grid_mlp_kernel_v5, dim3(grid), dim3(256), GRID5_LDS_BYTES, st, a);
-    } else if (kver == 12) {
-        // two workgroups of four waves per compute unit
-        // (its overflow list lies over the g-scaled vectors' split image, which the R GEMMs above were the last to read)
-#ifdef SURS_V12_ONE_WG
-        const unsigned grid12 = (unsigned)((nc < cs.cus) ? nc : cs.cus);
-#else
-        const unsigned grid12 = (unsigned)((nc < 2 * cs.cus) ? nc : 2 * cs.cus);
-#endif
-        a.ovf_count = a.colctr + 1;
-        a.ovf_list = (int *)((char *)workspace + col_base_bytes(COL_BATCH));
-        // (and behind the room that list can need - every z tile of every column -, the workgroups' fragment images)
-        const size_t ovf_room = ((size_t)nc * ((items + 127) / 128) * 2 * sizeof(int) + 4095) / 4096 * 4096;
-        SURS_REQUIRE(ovf_room + (size_t)grid12 * V12_AIMG_BYTES <= col_v7_image_bytes(COL_BATCH),
-                     "kernel v12's overflow list and fragment images do not fit the g-scaled split image");
-        a.aimg = (char *)a.ovf_list + ovf_room;
-        const int lds12 = GRID12_LDS_BYTES;
-        if (dtype == SURS_BF16)
-            hipLaunchKernelGGL(grid_mlp_kernel_v12<SURS_BF16>, dim3(grid12), dim3(V12_THREADS), lds12, st, a);
-        else
-            hipLaunchKernelGGL(grid_mlp_kernel_v12<SURS_F16>, dim3(grid12), dim3(V12_THREADS), lds12, st, a);
-        SURS_LAUNCH_CHECK();
-        // the tiles it left: kernel v10 over the list (an empty list costs one launch of workgroups that leave at once)
-        GridArgs b = a;
-        b.tile_list = a.ovf_list;
-        b.tile_count = a.ovf_count;
-        b.colctr = a.colctr + 2;
-        if (dtype == SURS_BF16)
-            hipLaunchKernelGGL(grid_mlp_kernel_v10<SURS_BF16>, dim3(grid), dim3(V10_THREADS), GRID10_LDS_BYTES, st, b);
-        else
-            hipLaunchKernelGGL(grid_mlp_kernel_v10<SURS_F16>, dim3(grid), dim3(V10_THREADS), GRID10_LDS_BYTES, st, b);
-    } else if (kver == 10) {
-        if (dtype == SURS_BF16)
-            hipLaunchKernelGGL(grid_mlp_kernel_v10<SURS_BF16>, dim3(grid), dim3(V10_THREADS), GRID10_LDS_BYTES, st, a);
-        else
-            hipLaunchKernelGGL(grid_mlp_kernel_v10<SURS_F16>, dim3(grid), dim3(V10_THREADS), GRID10_LDS_BYTES, st, a);
-    } else {
-        if (dtype == SURS_BF16)
-            hipLaunchKernelGGL(grid_mlp_kernel_v3<SURS_BF16>, dim3(grid), dim3(256), GRID3_LDS_BYTES, st, a);
-        else
-            hipLaunchKernelGGL(grid_mlp_kernel_v3<SURS_F16>, dim3(grid), dim3(256), GRID3_LDS_BYTES, st, a);
-    }
-    SURS_LAUNCH_CHECK();
-#ifdef SURS_V12_HIST
-    if (kver == 12 && dtype != SURS_F32) {
-        static unsigned long long *hist = nullptr;
-        if (!hist) {
-            SURS_HIP_CHECK(hipMalloc((void **)&hist, 65 * 8));
-            SURS_HIP_CHECK(hipMemset(hist, 0, 65 * 8));
-            SURS_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_v12_hist), &hist, sizeof(hist)));
-            static unsigned long long *h2 = hist;
-            atexit([] {
-                unsigned long long v[65];
-                if (hipMemcpy(v, h2, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return;
-                unsigned long long tot = 0;
-                for (int i = 0; i < 65; ++i) tot += v[i];
-                fprintf(stderr, "v12 tiles by residual k-steps (total %llu):", tot);
-                for (int i = 0; i < 65; ++i) if (v[i]) fprintf(stderr, " %d:%.4f", i, (double)v[i] / (double)tot);
-                fprintf(stderr, "\n");
-            });
-        }
-    }
-#endif
+    SURS_HIP_CHECK(hipEventCreate(&t.e0));
+    SURS_HIP_CHECK(hipEventCreate(&t.e1));
+    SURS_HIP_CHECK(hipEventRecord(t.e0, cs.st));
+    return 0;
+}
+
+static int prof_end(LaunchTimer &t, const ColumnSweep &cs, long long nc, int items) {
+    if (!t.e0) return 0;
+    SURS_HIP_CHECK(hipEventRecord(t.e1, cs.st));
+    std::lock_guard<std::mutex> lock(g_prof.mu);
+    g_prof.ev.emplace_back(t.e0, t.e1);
+    g_prof.pts.push_back((double)nc * items);
+    return 0;
+}
+
 #ifdef SURS_V3_TRACE
-    if (trace_this && option(OPT_V3_TRACE)) {
-        unsigned long long t[64];
-        SURS_HIP_CHECK(hipStreamSynchronize(st));
-        SURS_HIP_CHECK(hipMemcpyFromSymbol(t, HIP_SYMBOL(g_v3_trace), sizeof(t)));
-        for (int m = 0; m < 2; ++m) {
-            fprintf(stderr, "v3 trace MLP %d:", m);
-            for (int i = 1; i < 10; ++i) fprintf(stderr, " %llu", t[16 * m + i] - t[16 * m + i - 1]);
-            fprintf(stderr, "  total %llu\n", t[16 * m + 9] - t[16 * m]);
-            if (restated) {
-                fprintf(stderr, "   v7 layer 1 (since start): init issued %llu, list %llu, chunk 0: gathered %llu, residuals %llu, barrier %llu, mfma+barrier %llu; listed %llu\n",
-                        t[16 * m + 10] - t[16 * m], t[16 * m + 1] - t[16 * m], t[16 * m + 11] - t[16 * m], t[16 * m + 12] - t[16 * m],
-                        t[16 * m + 13] - t[16 * m], t[16 * m + 14] - t[16 * m], t[48 + m]);
-            }
+// Diagnostic builds (tools/build_trace.sh): the cycle stamps the traced workgroup left, after the sweep's first batch.  Synchronises.
+static int report_trace(const ColumnSweep &cs, long long nc, int items) {
+    if (!option(OPT_V3_TRACE)) return 0;
+    const unsigned grid = column_grid(cs, nc);
+    unsigned long long t[64];
+    SURS_HIP_CHECK(hipStreamSynchronize(cs.st));
+    SURS_HIP_CHECK(hipMemcpyFromSymbol(t, HIP_SYMBOL(g_v3_trace), sizeof(t)));
+    for (int m = 0; m < 2; ++m) {
+        fprintf(stderr, "v3 trace MLP %d:", m);
+        for (int i = 1; i < 10; ++i) fprintf(stderr, " %llu", t[16 * m + i] - t[16 * m + i - 1]);
+        fprintf(stderr, "  total %llu\n", t[16 * m + 9] - t[16 * m]);
+        if (cs.restated()) {
+            fprintf(stderr, "   restated layer 1 (since start): init issued %llu, list %llu, chunk 0: gathered %llu, residuals %llu, barrier %llu, mfma+barrier %llu; listed %llu\n",
+                    t[16 * m + 10] - t[16 * m], t[16 * m + 1] - t[16 * m], t[16 * m + 11] - t[16 * m], t[16 * m + 12] - t[16 * m],
+                    t[16 * m + 13] - t[16 * m], t[16 * m + 14] - t[16 * m], t[48 + m]);
         }
-        fprintf(stderr, "v3 trace between MLPs: %llu\n", t[16] - t[9]);
-        if (kver == 12 && dtype != SURS_F32) {
-            unsigned long long acc[2][16];
-            SURS_HIP_CHECK(hipMemcpyFromSymbol(acc, HIP_SYMBOL(g_v12_acc), sizeof(acc)));
-            for (int m = 0; m < 2; ++m) {
-                const double n = (double)(acc[m][0] ? acc[m][0] : 1);
-                double tot = 0;
-                fprintf(stderr, "v12 mean cycles per item, MLP %d (%llu items, %.2f residual k-steps): ", m, acc[m][0], (double)acc[m][15] / n);
-                for (int i = 1; i < 10; ++i) {
-                    fprintf(stderr, " %.0f", (double)acc[m][i] / n);
-                    tot += (double)acc[m][i] / n;
-                }
-                fprintf(stderr, "  total %.0f  [list | residuals + slices | acc2 init + barrier | stages 0-8 | stages 9-16 | y2 publish | barrier | layer 3 | layer 4]\n", tot);
-            }
-            fprintf(stderr, "v12 traced workgroup: %.0f cycles in %.1f us = %.3f GHz\n", (double)acc[0][13], (double)acc[0][14] / 100.0,
-                    (double)acc[0][13] / ((double)acc[0][14] / 100.0) * 1e-3);
-            unsigned long long zero[2][16] = {};
-            SURS_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_v12_acc), zero, sizeof(zero)));
-        }
-        const double cyc = (double)(t[42] - t[40]), us = (double)(t[43] - t[41]) / 100.0;
-        const int tile = dtype == SURS_F32 ? 64 : 128;
-        fprintf(stderr, "workgroup 0: %.0f cycles in %.1f us = %.3f GHz; %.0f cycles per %d-point tile\n", cyc, us,
-                cyc / us * 1e-3, cyc / ((double)((nc + grid - 1) / grid) * ((items + tile - 1) / tile)), tile);
     }
+    fprintf(stderr, "v3 trace between MLPs: %llu\n", t[16] - t[9]);
+    if (cs.kver == 12 && cs.dtype != SURS_F32) {
+        unsigned long long acc[2][16];
+        SURS_HIP_CHECK(hipMemcpyFromSymbol(acc, HIP_SYMBOL(g_v12_acc), sizeof(acc)));
+        for (int m = 0; m < 2; ++m) {
+            const double n = (double)(acc[m][0] ? acc[m][0] : 1);
+            double tot = 0;
+            fprintf(stderr, "v12 mean cycles per item, MLP %d (%llu items, %.2f residual k-steps): ", m, acc[m][0], (double)acc[m][15] / n);
+            for (int i = 1; i < 10; ++i) {
+                fprintf(stderr, " %.0f", (double)acc[m][i] / n);
+                tot += (double)acc[m][i] / n;
+            }
+            fprintf(stderr, "  total %.0f  [list | residuals + slices | acc2 init + barrier | stages 0-8 | stages 9-16 | y2 publish | barrier | layer 3 | layer 4]\n", tot);
+        }
+        fprintf(stderr, "v12 traced workgroup: %.0f cycles in %.1f us = %.3f GHz\n", (double)acc[0][13], (double)acc[0][14] / 100.0,
+                (double)acc[0][13] / ((double)acc[0][14] / 100.0) * 1e-3);
+        unsigned long long zero[2][16] = {};
+        SURS_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_v12_acc), zero, sizeof(zero)));
+    }
+    const double cyc = (double)(t[42] - t[40]), us = (double)(t[43] - t[41]) / 100.0;
+    const int tile = cs.dtype == SURS_F32 ? 64 : 128;
+    fprintf(stderr, "workgroup 0: %.0f cycles in %.1f us = %.3f GHz; %.0f cycles per %d-point tile\n", cyc, us,
+            cyc / us * 1e-3, cyc / ((double)((nc + grid - 1) / grid) * ((items + tile - 1) / tile)), tile);
+    return 0;
+}
+#endif
+
+// One batch of nc <= COL_BATCH columns described by src (mode 2: consecutive columns from src.base; mode 4: listed columns; mode 5:
+// point runs): gather + column constants, the restated kernels' per-column affine part, then the column kernel over `items` z items
+// per column (dense: the voxels 0 .. items - 1; lattice sweeps: the kcount[column] listed voxels klist[column][.] * zstride).
+// vol_*: [nc][items].
+static int run_column_batch(const ColumnSweep &cs, const PointSource &src, long long nc, int items, int zstride,
+                            const int *kcount, const unsigned short *klist, float *vol_hr, float *vol_lr, bool trace_this) {
+    const ColumnWorkspace w = carve_columns(cs.workspace);
+    const long long ncp = (long long)ceil_div(nc, 256) * 256;   // <= COL_BATCH; rows nc.. of CC are never read
+    const float zmid = cs.restated() ? column_zmid(cs.mat, cs.calib, cs.kmid, cs.zmul, cs.zdiv) : 0.0f;
+    int rc = 0;
+    if ((rc = column_constants(cs.st, src, nc, ncp, cs.feat_lr, cs.hl, cs.wl, cs.feat_hr, cs.hh, cs.wh, cs.blob, cs.h, w))) return rc;
+    if (cs.restated() && (rc = column_affine_part(cs, w, ncp, zmid))) return rc;
+    GridArgs a = column_grid_args(cs, w, zmid, nc, items, zstride, kcount, klist, vol_hr, vol_lr);
+    LaunchTimer timer;
+    if ((rc = prof_begin(timer, cs, !kcount, nc, items, a))) return rc;
+    if ((rc = launch_column_kernel(cs, w, a, nc, items))) return rc;
+#ifdef SURS_V3_TRACE
+    if (trace_this && (rc = report_trace(cs, nc, items))) return rc;
 #else
     (void)trace_this;
 #endif
-    if (prof) {
-        SURS_HIP_CHECK(hipEventRecord(e1, st));
-        std::lock_guard<std::mutex> lock(g_prof.mu);
-        g_prof.ev.emplace_back(e0, e1);
-        g_prof.pts.push_back((double)nc * items);
-    }
-    return 0;
+    return prof_end(timer, cs, nc, items);
 }
 
 // column mode needs: projected X,Y independent of k; world z a function of k only
@@ -1526,12 +1533,6 @@ static int query_grid_impl(int i0, int i1, int ry, int rz, const double *mat, co
     hipStream_t st = as_stream(stream);
     const MlpBlobHeader h = blob_layout((uint32_t)dtype);
     int rc = 0;
-    PointSource src;
-    memset(&src, 0, sizeof(src));
-    src.ry = ry;
-    src.rz = rz;
-    for (int i = 0; i < 12; ++i) src.mat[i] = mat[i];
-    fill_calib(src, calib, zmul, zdiv);
     const char *blob = (const char *)mlp_blob;
     const bool columns = sweep_has_columns(mat, calib);
 
@@ -1540,7 +1541,7 @@ static int query_grid_impl(int i0, int i1, int ry, int rz, const double *mat, co
         const long long total = (long long)(i1 - i0) * ry * rz;
         Fp32Workspace w = carve_fp32(workspace, GRID_BATCH);
         if ((rc = zero_pad_rows(st, w))) return rc;
-        src.mode = 1;
+        PointSource src = point_source(1, ry, rz, mat, calib, zmul, zdiv);
         for (long long b0 = 0; b0 < total; b0 += GRID_BATCH) {
             const long long nb = (total - b0 < GRID_BATCH) ? total - b0 : GRID_BATCH;
             src.base = (long long)i0 * ry * rz + b0;
@@ -1556,26 +1557,45 @@ static int query_grid_impl(int i0, int i1, int ry, int rz, const double *mat, co
                     "column kernel needs an axis-aligned orthographic sweep (X,Y independent of k); use SURS_F32");
     const long long ncols = (long long)(i1 - i0) * ry;
     ColumnSweep cs;
-    cs.st = st;
-    cs.blob = blob;
-    cs.h = h;
-    cs.dtype = dtype;
+    if ((rc = begin_column_sweep(cs, st, mlp_blob, dtype, feat_lr, hl, wl, feat_hr, hh, wh, mat, calib, zmul, zdiv, workspace))) return rc;
     resolve_column_kernels(kernel_call, cs.kver, cs.kver32);
-    cs.restated = dtype == SURS_F32 ? cs.kver32 == 11 : (cs.kver == 10 || cs.kver == 12);
-    cs.feat_lr = feat_lr; cs.hl = hl; cs.wl = wl;
-    cs.feat_hr = feat_hr; cs.hh = hh; cs.wh = wh;
-    cs.mat = mat; cs.calib = calib; cs.zmul = zmul; cs.zdiv = zdiv;
-    cs.workspace = workspace;
-    cs.cus = device_cus();
     cs.kmid = rz / 2;
-    if ((rc = grid_set_attributes())) return rc;
-    src.mode = 2;
+    PointSource src = point_source(2, ry, rz, mat, calib, zmul, zdiv);
     for (long long c0 = 0; c0 < ncols; c0 += COL_BATCH) {
         const long long nc = (ncols - c0 < COL_BATCH) ? ncols - c0 : COL_BATCH;
         src.base = (long long)i0 * ry + c0;
         if ((rc = run_column_batch(cs, src, nc, rz, 1, nullptr, nullptr, vol_hr + (size_t)c0 * rz, vol_lr + (size_t)c0 * rz, c0 == 0))) return rc;
     }
     return 0;
+}
+
+extern "C" int surs_query_grid_opt(int i0, int i1, int ry, int rz, const double *mat, const float *calib, float zmul,
+                                   float zdiv, const float *feat_lr, int hl, int wl, const float *feat_hr, int hh, int wh,
+                                   const void *mlp_blob, int dtype, void *workspace, size_t workspace_bytes, float *vol_hr,
+                                   float *vol_lr, const SursGridOptions *opt, void *stream) {
+    int kernel = 0, parts = 0;
+    if (opt) {
+        kernel = opt->kernel;
+        parts = opt->operand_parts;
+        SURS_REQUIRE(grid_kernel_known(kernel), "SursGridOptions.kernel: 0, 3, 10, 12 (reduced precision), 5, 11 (fp32-grade)");
+        SURS_REQUIRE(parts == 0 || parts == 2 || parts == 3, "SursGridOptions.operand_parts: 0, 2 or 3");
+    }
+    // the operand split is read deep inside the launch helpers: scoped to this call and this thread, the process setting
+    // (surs_set_operand_split) is neither read nor changed when the caller gave one
+    const int saved = t_split_call;
+    if (parts) t_split_call = parts;
+    const int rc = query_grid_impl(i0, i1, ry, rz, mat, calib, zmul, zdiv, feat_lr, hl, wl, feat_hr, hh, wh, mlp_blob, dtype, workspace,
+                                   workspace_bytes, vol_hr, vol_lr, kernel, stream);
+    t_split_call = saved;
+    return rc;
+}
+
+extern "C" int surs_query_grid(int i0, int i1, int ry, int rz, const double *mat, const float *calib, float zmul,
+                               float zdiv, const float *feat_lr, int hl, int wl, const float *feat_hr, int hh, int wh,
+                               const void *mlp_blob, int dtype, void *workspace, size_t workspace_bytes, float *vol_hr,
+                               float *vol_lr, void *stream) {
+    return query_grid_impl(i0, i1, ry, rz, mat, calib, zmul, zdiv, feat_lr, hl, wl, feat_hr, hh, wh, mlp_blob, dtype, workspace,
+                           workspace_bytes, vol_hr, vol_lr, 0, stream);
 }
 
 
@@ -1592,33 +1612,22 @@ extern "C" int surs_query_grid_probe(int i_plane, int ry, int rz, int tile, cons
     SURS_REQUIRE(mat && calib && feat_lr && feat_hr && mlp_blob && workspace && listed, "null argument");
     SURS_REQUIRE(ry > 0 && rz > 0 && i_plane >= 0 && (tile == 64 || tile == 128), "bad probe arguments");
     SURS_REQUIRE(ry <= COL_BATCH, "probe plane wider than a column batch");
-    SURS_REQUIRE(workspace_bytes >= col_ws_bytes(COL_BATCH), "workspace too small");
+    SURS_REQUIRE(workspace_bytes >= col_ws_bytes(), "workspace too small");
     listed[0] = listed[1] = -1.0f;
-    const float cX = (float)(calib[0] * mat[2] + calib[1] * mat[6] + calib[2] * mat[10]);
-    const float cY = (float)(calib[4] * mat[2] + calib[5] * mat[6] + calib[6] * mat[10]);
-    if (cX != 0.0f || cY != 0.0f || mat[8] != 0.0 || mat[9] != 0.0 || calib[8] != 0.0f || calib[9] != 0.0f) return 0;
+    if (!sweep_has_columns(mat, calib)) return 0;
     hipStream_t st = as_stream(stream);
     const MlpBlobHeader h = blob_layout(SURS_BF16);
     const char *blob = (const char *)mlp_blob;
-    PointSource src;
-    memset(&src, 0, sizeof(src));
-    src.ry = ry;
-    src.rz = rz;
-    for (int i = 0; i < 12; ++i) src.mat[i] = mat[i];
-    fill_calib(src, calib, zmul, zdiv);
-    src.mode = 2;
+    PointSource src = point_source(2, ry, rz, mat, calib, zmul, zdiv);
     src.base = (long long)i_plane * ry;
-    float *F = (float *)workspace;
-    float *CC = F + (size_t)C0PAD * COL_BATCH;
-    float *cmask = CC + (size_t)CC_PAD * COL_BATCH;
+    const ColumnWorkspace w = carve_columns(workspace);
     const long long nc = ry, ncp = (long long)ceil_div(nc, 256) * 256;
-    int rc = column_constants(st, src, nc, ncp, feat_lr, hl, wl, feat_hr, hh, wh, blob, h, F, CC, cmask);
+    int rc = column_constants(st, src, nc, ncp, feat_lr, hl, wl, feat_hr, hh, wh, blob, h, w);
     if (rc) return rc;
-    unsigned long long *ctr = (unsigned long long *)((char *)workspace + col_base_bytes(COL_BATCH));
+    unsigned long long *ctr = w.probe_ctr;
     SURS_HIP_CHECK(hipMemsetAsync(ctr, 0, 16, st));
-    const float zw = (float)(mat[10] * (double)(rz / 2) + mat[11]);
-    const float zmid = (calib[11] + calib[10] * zw) * zmul / zdiv;
-    hipLaunchKernelGGL(probe_count_kernel, dim3((unsigned)nc), dim3(256), 0, st, CC, (const float *)(blob + h.zvec), rz, tile, mat[11], mat[10],
+    const float zmid = column_zmid(mat, calib, rz / 2, zmul, zdiv);
+    hipLaunchKernelGGL(probe_count_kernel, dim3((unsigned)nc), dim3(256), 0, st, w.CC, (const float *)(blob + h.zvec), rz, tile, mat[11], mat[10],
                        calib[10], calib[11], zmul, zdiv, zmid, ctr);
     SURS_LAUNCH_CHECK();
     unsigned long long v[2] = {0, 0};
@@ -1645,14 +1654,8 @@ extern "C" int surs_query_grid_indexed(const long long *idx, int n, int ry, int 
     const long long np = (long long)ceil_div(n, 256) * 256;
     SURS_REQUIRE(workspace_bytes >= fp32_ws_bytes(np), "workspace too small: need %zu bytes", fp32_ws_bytes(np));
     const MlpBlobHeader h = blob_layout(SURS_BF16);
-    PointSource src;
-    memset(&src, 0, sizeof(src));
-    src.mode = 3;
+    PointSource src = point_source(3, ry, rz, mat, calib, zmul, zdiv);
     src.idx = idx;
-    src.ry = ry;
-    src.rz = rz;
-    for (int i = 0; i < 12; ++i) src.mat[i] = mat[i];
-    fill_calib(src, calib, zmul, zdiv);
     Fp32Workspace w = carve_fp32(workspace, np);
     int rc = zero_pad_rows(st, w);
     if (rc) return rc;
@@ -1769,23 +1772,10 @@ __global__ __launch_bounds__(256) void lattice_scatter_kernel(const int *__restr
 static size_t lattice_list_bytes(int R) { return align_up((size_t)R * R * 8 + 64, 256); }
 
 extern "C" size_t surs_octree_columns_workspace_bytes(int R) {
-    return col_ws_bytes(COL_BATCH) + lattice_list_bytes(R) + (size_t)COL_BATCH * R * (2 * sizeof(float) + sizeof(unsigned short)) + 512;
+    return col_ws_bytes() + lattice_list_bytes(R) + (size_t)COL_BATCH * R * (2 * sizeof(float) + sizeof(unsigned short)) + 512;
 }
 
-extern "C" int surs_octree_level_columns_dt(double *sdf_hr, double *sdf_lr, unsigned char *dirty, int R, int reso, int kmid,
-                                            const double *mat, const float *calib, float zmul, float zdiv, const float *feat_lr, int hl,
-                                            int wl, const float *feat_hr, int hh, int wh, const void *mlp_blob, int dtype, void *workspace,
-                                            size_t workspace_bytes, long long *counts, void *stream);
-
-extern "C" int surs_octree_level_columns(double *sdf_hr, double *sdf_lr, unsigned char *dirty, int R, int reso, int kmid,
-                                         const double *mat, const float *calib, float zmul, float zdiv, const float *feat_lr, int hl,
-                                         int wl, const float *feat_hr, int hh, int wh, const void *mlp_blob, void *workspace,
-                                         size_t workspace_bytes, long long *counts, void *stream) {
-    return surs_octree_level_columns_dt(sdf_hr, sdf_lr, dirty, R, reso, kmid, mat, calib, zmul, zdiv, feat_lr, hl, wl, feat_hr, hh, wh,
-                                        mlp_blob, SURS_F32, workspace, workspace_bytes, counts, stream);
-}
-
-// ... with the arithmetic of the level's evaluator chosen: SURS_F32 = kernel v11 (fp32-grade: the default of surs_octree_level_columns);
+// The level with the arithmetic of its evaluator chosen: SURS_F32 = kernel v11 (fp32-grade: what surs_octree_level_columns, below, asks for);
 // SURS_BF16 / SURS_F16 = kernel v10 on the blob's 16-bit cores (tiles of 128 listed points) - the octree sweep of `--precision bf16 |
 // fp16`, whose dense sweep runs the same arithmetic.
 extern "C" int surs_octree_level_columns_dt(double *sdf_hr, double *sdf_lr, unsigned char *dirty, int R, int reso, int kmid,
@@ -1803,7 +1793,7 @@ extern "C" int surs_octree_level_columns_dt(double *sdf_hr, double *sdf_lr, unsi
                                         "surs_query_grid_indexed + surs_octree_scatter");
     hipStream_t st = as_stream(stream);
     int rc = 0;
-    char *base = (char *)workspace + col_ws_bytes(COL_BATCH);
+    char *base = (char *)workspace + col_ws_bytes();
     int *cols = (int *)base;
     int *kcnt = cols + (size_t)nl * nl;
     unsigned long long *ctr = (unsigned long long *)(base + lattice_list_bytes(R) - 64);
@@ -1823,28 +1813,12 @@ extern "C" int surs_octree_level_columns_dt(double *sdf_hr, double *sdf_lr, unsi
     }
     const long long ncols = (long long)host[0];
     if (ncols == 0) return 0;
+    // kernels 10 / 11: the streamed kernel v12 and its overflow hand-over have not been run on lattice lists, the dense-layer-1
+    // kernels v3 / v5 have no strided / masked form
     ColumnSweep cs;
-    cs.st = st;
-    cs.blob = (const char *)mlp_blob;
-    cs.h = blob_layout((uint32_t)dtype);
-    cs.dtype = dtype;
-    cs.kver = 10;     // (the eight-wave kernel: the streamed kernel v12 and its overflow hand-over have not been run on lattice lists)
-    cs.kver32 = 11;   // (the dense-layer-1 kernels v3 / v5 have no strided / masked form)
-    cs.restated = true;
-    cs.feat_lr = feat_lr; cs.hl = hl; cs.wl = wl;
-    cs.feat_hr = feat_hr; cs.hh = hh; cs.wh = wh;
-    cs.mat = mat; cs.calib = calib; cs.zmul = zmul; cs.zdiv = zdiv;
-    cs.workspace = workspace;
-    cs.cus = device_cus();
+    if ((rc = begin_column_sweep(cs, st, mlp_blob, dtype, feat_lr, hl, wl, feat_hr, hh, wh, mat, calib, zmul, zdiv, workspace))) return rc;
     cs.kmid = kmid;
-    if ((rc = grid_set_attributes())) return rc;
-    PointSource src;
-    memset(&src, 0, sizeof(src));
-    src.mode = 4;
-    src.ry = R;
-    src.rz = R;
-    for (int i = 0; i < 12; ++i) src.mat[i] = mat[i];
-    fill_calib(src, calib, zmul, zdiv);
+    PointSource src = point_source(4, R, R, mat, calib, zmul, zdiv);
     for (long long c0 = 0; c0 < ncols; c0 += COL_BATCH) {
         const long long nc = (ncols - c0 < COL_BATCH) ? ncols - c0 : COL_BATCH;
         src.cols = cols + c0;
@@ -1858,6 +1832,14 @@ extern "C" int surs_octree_level_columns_dt(double *sdf_hr, double *sdf_lr, unsi
         SURS_LAUNCH_CHECK();
     }
     return 0;
+}
+
+extern "C" int surs_octree_level_columns(double *sdf_hr, double *sdf_lr, unsigned char *dirty, int R, int reso, int kmid,
+                                         const double *mat, const float *calib, float zmul, float zdiv, const float *feat_lr, int hl,
+                                         int wl, const float *feat_hr, int hh, int wh, const void *mlp_blob, void *workspace,
+                                         size_t workspace_bytes, long long *counts, void *stream) {
+    return surs_octree_level_columns_dt(sdf_hr, sdf_lr, dirty, R, reso, kmid, mat, calib, zmul, zdiv, feat_lr, hl, wl, feat_hr, hh, wh,
+                                        mlp_blob, SURS_F32, workspace, workspace_bytes, counts, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2106,7 +2088,7 @@ extern "C" int surs_point_runs(const float *points, long long ld, int n, int til
     return 0;
 }
 
-extern "C" size_t surs_query_points_columns_workspace_bytes(void) { return col_ws_bytes(COL_BATCH) + point_runs_list_bytes(); }
+extern "C" size_t surs_query_points_columns_workspace_bytes(void) { return col_ws_bytes() + point_runs_list_bytes(); }
 
 extern "C" int surs_query_points_columns(const float *points, long long ld, int n, const float *calib, float zmul, float zdiv,
                                          const float *feat_lr, int hl, int wl, const float *feat_hr, int hh, int wh,
@@ -2124,7 +2106,7 @@ extern "C" int surs_query_points_columns(const float *points, long long ld, int 
     if (n < 2048) return 0;   // (the per-call preparation outweighs the point kernels' work below that)
     hipStream_t st = as_stream(stream);
     int rc = 0;
-    char *lists = (char *)workspace + col_ws_bytes(COL_BATCH);
+    char *lists = (char *)workspace + col_ws_bytes();
     int *colstart = (int *)lists, *kcount = colstart + PR_CHUNK, *tiles = kcount + PR_CHUNK;
     int *meta = (int *)(lists + point_runs_list_bytes() - 256);
     const int tile = dtype == SURS_F32 ? 64 : 128;
@@ -2154,33 +2136,18 @@ extern "C" int surs_query_points_columns(const float *points, long long ld, int 
     host[0] = host[1] = host[2] = host[3] = 0;
     SURS_HIP_CHECK(hipMemcpyAsync(host, meta, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
     SURS_HIP_CHECK(hipEventRecord(sp.ev, st));
+    // kernels 10 / 11 in tile mode: the work items are (column, z tile) pairs - a call holds ~ 100 columns, fewer than the chip has CUs
     ColumnSweep cs;
-    cs.st = st;
-    cs.blob = (const char *)mlp_blob;
-    cs.h = blob_layout((uint32_t)dtype);
-    cs.dtype = dtype;
-    cs.kver = 10;    // (tile mode: the work items are (column, z tile) pairs - a call holds ~ 100 columns, fewer than the chip has CUs)
-    cs.kver32 = 11;
-    cs.restated = true;
-    cs.feat_lr = feat_lr; cs.hl = hl; cs.wl = wl;
-    cs.feat_hr = feat_hr; cs.hh = hh; cs.wh = wh;
-    cs.mat = nullptr; cs.calib = calib; cs.zmul = zmul; cs.zdiv = zdiv;
-    cs.workspace = workspace;
-    cs.cus = device_cus();
-    cs.kmid = 0;
+    if ((rc = begin_column_sweep(cs, st, mlp_blob, dtype, feat_lr, hl, wl, feat_hr, hh, wh, nullptr, calib, zmul, zdiv, workspace))) return rc;
     cs.run_colstart = colstart;
     cs.run_z = points + 2 * ld;
     cs.run_tiles = tiles;
     cs.run_ntiles = (const unsigned *)(meta + 1);
-    if ((rc = grid_set_attributes())) return rc;
-    PointSource src;
-    memset(&src, 0, sizeof(src));
-    src.mode = 5;
+    PointSource src = point_source(5, 0, 0, nullptr, calib, zmul, zdiv);
     src.pts = points;
     src.ld = ld;
     src.cols = colstart;
     src.npts = n;
-    fill_calib(src, calib, zmul, zdiv);
     const bool speculate = option(OPT_POINT_RUNS_SPECULATE) != 0;
     long long guessed = 0;
     if (speculate && sp.n == n && sp.tile == tile && sp.ncols > 0) {
