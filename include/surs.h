@@ -976,6 +976,53 @@ int surs_mesh_distance(const float *points, int n, int ld, const float *verts, i
 int surs_mesh_distance_host(const float *points, int n, int ld, const float *verts, int nv, const int32_t *faces, int nf,
                             float *dist, int32_t *face);
 
+/* ---------------------------------------------------------------- mesh raster
+ * Which triangle of a mesh each pixel of an orthographic view sees, with its depth and barycentric coordinates, and the normal map
+ * made from them: what the normal reprojection error of the papers (metrics.normal_error) is made of.  The reference renders these
+ * maps with OpenGL (lib/renderer/gl); the camera conventions are those of its orthographic camera (lib/renderer/camera.py:149-156,
+ * the ortho_ratio branch of get_gl_matrix) and of the calib product in lib/data/TrainDataset_LR_v2.py:242-254 and :315-316
+ * (calib = trans_intrinsic . uv_intrinsic . scale_intrinsic . extrinsic; scale_intrinsic = diag(s, -s, s): y' downwards, a POSITIVE
+ * z entry; --random_flip negates its x entry, :274).  A mesh as in
+ * "training samples" (indices clamped to [0, nv)); brute force over all faces, no lists, no atomics: the same arguments give the same
+ * bits.  The arithmetic is csrc/surs_mesh_raster.h, one for host and device.
+ *
+ * view[12] is a row-major 3 x 4 matrix, the top three rows of such a calib: (x', y', z') = view . (x, y, z, 1), orthographic, x' and
+ * y' in [-1, 1] over the image, y' growing DOWNWARDS.  The camera looks from the +z' side: of two surfaces over a pixel the one with
+ * the LARGER z' is seen.  The image has h rows and w columns; pixel (i, j) is sampled at its centre x' = (2j + 1) / w - 1, y' =
+ * (2i + 1) / h - 1.  A pixel is covered by a triangle where all three barycentric coordinates of its centre are >= 0 (edges
+ * inclusive, either winding, no culling); a triangle with zero projected area, a non-finite coordinate or no pixel centre in its
+ * bounding box covers nothing.  The winner of a pixel is the covering triangle with the largest z', the LOWEST face index among equal
+ * z' (a strict > over the faces in order).
+ *   face  [h, w]     int32   the winner, -1 on background
+ *   depth [h, w]     fp32    its z' at the pixel centre, NaN on background (nullable)
+ *   bary  [h, w, 2]  fp32    the weights (b1, b2) of the winner's vertices with the middle and the largest INDEX (a face's three
+ *                            vertices are taken in ascending index order, so a mesh and its copy with every face turned round
+ *                            give the same bits); (0, 0) on background (nullable)
+ * The faces are split into surs_mesh_raster_parts(nf) parts of the option raster_part (a multiple of 256) - a function of nf and the
+ * option alone; the workspace holds a 16-byte pixel box per face and [parts][h * w] entries of (z', face, b1, b2), combined in index
+ * order with the strict > again.  A pixel's results do not depend on the image it sits in, on the part size or on the workspace.
+ *
+ * surs_mesh_shade_normals writes out [h, w, 3] fp32: on a covered pixel the colour 0.5 n + 0.5 of the winner's unit normal n in the
+ * VIEW frame, turned to face the camera (n_z' >= 0, whatever the triangle's orientation and the view's handedness); (0, 0, 0) on
+ * background.  Without vertex_normals n is the cross product of the triangle's projected edges (flat); with vertex_normals [nv, 3] it
+ * is normal_matrix[9] (row-major 3 x 3) times the barycentric blend of the three vertices' normals (smooth; bary is then needed).
+ * SURS_E_INVALID, before anything is launched or written: a NULL array (depth, bary of the raster and vertex_normals are nullable;
+ * normal_matrix and bary of the shading only where vertex_normals is NULL), w or h outside [1, 8192], nf < 1, nv < 1, an option
+ * raster_part that is no positive multiple of 256, more than 65535 parts, a workspace smaller than
+ * surs_mesh_raster_workspace_bytes(w, h, nf) (which is 0 for w, h or nf < 1).
+ * The _host entries are the same header looped on the HOST (all pointers host pointers): the kernels' bits, no device. */
+int surs_mesh_raster_parts(int nf);
+size_t surs_mesh_raster_workspace_bytes(int w, int h, int nf);
+int surs_mesh_raster(const float *verts, int nv, const int32_t *faces, int nf, const float *view, int w, int h, void *workspace,
+                     size_t workspace_bytes, int32_t *face, float *depth, float *bary, void *stream);
+int surs_mesh_shade_normals(const float *verts, int nv, const int32_t *faces, int nf, const float *view, const float *vertex_normals,
+                            const float *normal_matrix, const int32_t *face, const float *bary, int w, int h, float *out, void *stream);
+int surs_mesh_raster_host(const float *verts, int nv, const int32_t *faces, int nf, const float *view, int w, int h, int32_t *face,
+                          float *depth, float *bary);
+int surs_mesh_shade_normals_host(const float *verts, int nv, const int32_t *faces, int nf, const float *view,
+                                 const float *vertex_normals, const float *normal_matrix, const int32_t *face, const float *bary, int w,
+                                 int h, float *out);
+
 /* ---------------------------------------------------------------- device repack
  * The packed images the forward reads (surs_conv_pack_weights*, the blobs of surs_mlp_pack / surs_mlp_pack_generic) rebuilt ON THE
  * DEVICE from the plain fp32 parameters an optimiser has just stepped: the bytes the host packers give for the same values, without

@@ -307,6 +307,12 @@ _SIGS = {
     "surs_mesh_distance_workspace_bytes": (_sz, [_i, _i]),
     "surs_mesh_distance": (C.c_int, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp]),
     "surs_mesh_distance_host": (C.c_int, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    "surs_mesh_raster_parts": (C.c_int, [_i]),
+    "surs_mesh_raster_workspace_bytes": (_sz, [_i, _i, _i]),
+    "surs_mesh_raster": (C.c_int, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "surs_mesh_shade_normals": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "surs_mesh_raster_host": (C.c_int, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    "surs_mesh_shade_normals_host": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "surs_conv_repack_tiles": (C.c_int, [_i, _i, _i]),
     "surs_conv_repack": (C.c_int, [_vp, _i, _vp]),
     "surs_conv1x1_merge": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),

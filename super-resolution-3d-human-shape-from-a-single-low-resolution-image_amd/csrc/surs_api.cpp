@@ -49,6 +49,7 @@ const OptionRow kOptions[surs::OPT_COUNT] = {
     {"mc_ring", "SURS_MC_RING", 258, 0, 0, "planes of marching cubes' edge -> vertex-id ring = layers per chunk of a one-piece extraction + 1 (66: round 5's)"},
     {"rvec_small", "SURS_RVEC_SMALL", 1, 0, 0, "0: the affine part's GEMM of batches of <= 1024 columns on the 256 x 256-tile kernel (A/B; same bits)"},
     {"r_fused", "SURS_R_FUSED", 1, 0, 0, "0: the bf16 sweep's R vectors of batches of > 1024 columns from the g-scaled image and two GEMM launches (A/B; same bits)"},
+    {"raster_part", "SURS_RASTER_PART", 65536, 0, 0, "faces per part of the mesh raster, a multiple of 256: the workspace holds h x w x 16 bytes per part (same bits)"},
 };
 std::atomic<int> g_option[surs::OPT_COUNT];
 std::once_flag g_option_once;

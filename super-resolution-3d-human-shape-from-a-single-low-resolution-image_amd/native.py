@@ -2411,3 +2411,106 @@ def mesh_distance_host(points, verts, faces):
     check(lib().surs_mesh_distance_host(p.ctypes.data, len(p), p.shape[1], v.ctypes.data, len(v), f.ctypes.data, len(f), dist.ctypes.data,
                                         face.ctypes.data))
     return dist, face
+
+
+# ------------------------------------------------------------------ mesh raster (include/surs.h "mesh raster")
+
+def _view12(view):
+    """A view - [3,4] or [4,4], tensor or array - as its top three rows: float32 [3,4] on the host."""
+    v = view.detach().cpu().numpy() if isinstance(view, torch.Tensor) else np.asarray(view)
+    if v.shape not in ((3, 4), (4, 4)):
+        raise ValueError("view: [3,4] or [4,4] expected, not %s" % (v.shape,))
+    return np.ascontiguousarray(np.asarray(v, np.float64)[:3].astype(np.float32))
+
+
+def _image_size(size):
+    """size - an int (square) or (h, w) - as (h, w)."""
+    if isinstance(size, (int, np.integer)) and not isinstance(size, bool):
+        return int(size), int(size)
+    h, w = size
+    return int(h), int(w)
+
+
+def normal_matrix(view):
+    """The row-major 3 x 3 matrix that takes world normals into the frame of `view`: the inverse transpose of its linear part,
+    scaled to a largest entry of 1 (float64 on the host, rounded to float32)."""
+    a = np.asarray(_view12(view), np.float64)[:, :3]
+    n = np.linalg.inv(a).T
+    return np.ascontiguousarray((n / np.abs(n).max()).astype(np.float32))
+
+
+def mesh_raster(mesh, view, size, want_depth=False, want_bary=False):
+    """The mesh seen through `view` (see _view12) on an image of `size` (see _image_size): face int32 [h,w], the triangle each pixel
+    centre sees (-1: background); with want_depth also its z' (float32 [h,w], NaN on background), with want_bary the weights of
+    its second and third vertex (float32 [h,w,2]).  Device tensors, no host synchronisation."""
+    h, w = _image_size(size)
+    dev = mesh.verts.device
+    m = _view12(view)
+    face = torch.empty((h, w), dtype=torch.int32, device=dev)
+    depth = torch.empty((h, w), dtype=torch.float32, device=dev) if want_depth else None
+    bary = torch.empty((h, w, 2), dtype=torch.float32, device=dev) if want_bary else None
+    nbytes = lib().surs_mesh_raster_workspace_bytes(w, h, mesh.nf)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    check(lib().surs_mesh_raster(_ptr(mesh.verts), mesh.nv, _ptr(mesh.faces), mesh.nf, m.ctypes.data, w, h, _ptr(ws), nbytes, _ptr(face),
+                                 _ptr(depth), _ptr(bary), _stream()))
+    out = (face,) + ((depth,) if want_depth else ()) + ((bary,) if want_bary else ())
+    return out if len(out) > 1 else face
+
+
+def _host_mesh(verts, faces):
+    return (np.ascontiguousarray(np.asarray(verts, np.float32).reshape(-1, 3)),
+            np.ascontiguousarray(np.asarray(faces, np.int32).reshape(-1, 3)))
+
+
+def mesh_raster_host(verts, faces, view, size):
+    """surs_mesh_raster_host on numpy arrays, on the HOST, no device needed: (face int32 [h,w], depth float32 [h,w], bary float32
+    [h,w,2]), the kernels' bits."""
+    h, w = _image_size(size)
+    v, f = _host_mesh(verts, faces)
+    m = _view12(view)
+    face, depth, bary = np.empty((h, w), np.int32), np.empty((h, w), np.float32), np.empty((h, w, 2), np.float32)
+    check(lib().surs_mesh_raster_host(v.ctypes.data, len(v), f.ctypes.data, len(f), m.ctypes.data, w, h, face.ctypes.data,
+                                      depth.ctypes.data, bary.ctypes.data))
+    return face, depth, bary
+
+
+def normal_map(mesh, view, size, vertex_normals=None):
+    """The mesh's normal map through `view`: (float32 [h,w,3] - 0.5 n + 0.5 of the unit normal in the view frame, turned towards the
+    camera, (0, 0, 0) on background -, bool [h,w], the covered pixels).  Flat normals of the faces, or - vertex_normals [nv,3], tensor
+    or array in the mesh's frame - their barycentric blend.  Device tensors, no host synchronisation."""
+    h, w = _image_size(size)
+    dev = mesh.verts.device
+    m = _view12(view)
+    vn = nm = None
+    if vertex_normals is not None:
+        vn = vertex_normals if isinstance(vertex_normals, torch.Tensor) else torch.from_numpy(np.asarray(vertex_normals, np.float32))
+        vn = vn.to(device=dev, dtype=torch.float32).contiguous()
+        if tuple(vn.shape) != (mesh.nv, 3):
+            raise ValueError("vertex_normals: [%d, 3] expected, not %s" % (mesh.nv, tuple(vn.shape)))
+        nm = normal_matrix(view)
+        face, bary = mesh_raster(mesh, view, (h, w), want_bary=True)
+    else:
+        face, bary = mesh_raster(mesh, view, (h, w)), None
+    out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+    check(lib().surs_mesh_shade_normals(_ptr(mesh.verts), mesh.nv, _ptr(mesh.faces), mesh.nf, m.ctypes.data, _ptr(vn),
+                                        nm.ctypes.data if nm is not None else None, _ptr(face), _ptr(bary), w, h, _ptr(out), _stream()))
+    return out, face >= 0
+
+
+def normal_map_host(verts, faces, view, size, vertex_normals=None):
+    """normal_map on numpy arrays, on the HOST: (float32 [h,w,3], bool [h,w]), the kernels' bits."""
+    h, w = _image_size(size)
+    v, f = _host_mesh(verts, faces)
+    m = _view12(view)
+    face, _, bary = mesh_raster_host(v, f, view, (h, w))
+    vn = nm = None
+    if vertex_normals is not None:
+        vn = np.ascontiguousarray(np.asarray(vertex_normals, np.float32))
+        if vn.shape != (len(v), 3):
+            raise ValueError("vertex_normals: [%d, 3] expected, not %s" % (len(v), vn.shape))
+        nm = normal_matrix(view)
+    out = np.empty((h, w, 3), np.float32)
+    check(lib().surs_mesh_shade_normals_host(v.ctypes.data, len(v), f.ctypes.data, len(f), m.ctypes.data,
+                                             vn.ctypes.data if vn is not None else None, nm.ctypes.data if nm is not None else None,
+                                             face.ctypes.data, bary.ctypes.data, w, h, out.ctypes.data))
+    return out, face >= 0

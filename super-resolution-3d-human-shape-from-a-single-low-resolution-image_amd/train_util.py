@@ -27,18 +27,24 @@ def gen_mesh(opt, net, cuda, data, save_path, use_octree=True):
     return verts_hr, faces_hr, verts_lr, faces_lr
 
 
-def gen_mesh_metrics(opt, net, cuda, data, save_path=None, use_octree=True, n=10000, seed=0, gt_hr=None, gt_lr=None):
+def gen_mesh_metrics(opt, net, cuda, data, save_path=None, use_octree=True, n=10000, seed=0, gt_hr=None, gt_lr=None,
+                     normal_views=None, normal_size=512):
     """gen_mesh's reconstruction of one item, scored against the item's ground-truth scans: {"HR": metrics.mesh_metrics(the HR
     volume's mesh, the HR scan), "LR": (the LR volume's mesh, the LR scan)}, each from n surface samples per mesh.  The predicted
     vertices are taken into the scans' frame first (metrics.pred_to_gt_transform(data['calib']): the identity without a calib), so
     the distances are in the dataset's units.  The scans are data['mesh_path_HR'] / ['mesh_path_LR'] (OBJ files) unless gt_hr /
-    gt_lr hand in meshes (native.Mesh or (verts, faces)).  With a save_path the two OBJ files of gen_mesh are written as well."""
+    gt_lr hand in meshes (native.Mesh or (verts, faces)).  With a save_path the two OBJ files of gen_mesh are written as well.
+    normal_views: a tuple of turntable degrees, e.g. (0, 90, 180, 270), adds the normal reprojection error to each of the two
+    (metrics.normal_error at normal_size through metrics.turntable_views(data['calib'][0], degrees, the centre of the scan's
+    bounding box); the item needs its calib then): normal_error, normal_per_view, mask_iou.  None: today's keys."""
     from . import metrics
     from .mesh_util import load_obj_mesh
     n = metrics.check_samples(n)
     for key, given in (("mesh_path_HR", gt_hr), ("mesh_path_LR", gt_lr)):
         if given is None and key not in data:
             raise ValueError("gen_mesh_metrics: the item has no %r and no ground-truth mesh was handed in" % key)
+    if normal_views is not None and data.get("calib") is None:
+        raise ValueError("gen_mesh_metrics: normal_views needs the item's calib")
     to_gt = metrics.pred_to_gt_transform(data.get("calib"))
     image_tensor = data["img_LR"].to(device=cuda)
     img_sr, feature_lr, feature_hr = net.super_res(image_tensor)
@@ -53,8 +59,18 @@ def gen_mesh_metrics(opt, net, cuda, data, save_path=None, use_octree=True, n=10
         save_obj_mesh(save_path[:-4] + "_LR.obj", verts_lr, faces_lr)
     gt_hr = load_obj_mesh(data["mesh_path_HR"]) if gt_hr is None else gt_hr
     gt_lr = load_obj_mesh(data["mesh_path_LR"]) if gt_lr is None else gt_lr
-    return {"HR": metrics.mesh_metrics((metrics.transform_verts(to_gt, verts_hr), faces_hr), gt_hr, n=n, seed=seed),
-            "LR": metrics.mesh_metrics((metrics.transform_verts(to_gt, verts_lr), faces_lr), gt_lr, n=n, seed=seed)}
+    scores = {}
+    for key, verts, faces, gt in (("HR", verts_hr, faces_hr, gt_hr), ("LR", verts_lr, faces_lr, gt_lr)):
+        pred = (metrics.transform_verts(to_gt, verts), faces)
+        if normal_views is None:
+            scores[key] = metrics.mesh_metrics(pred, gt, n=n, seed=seed)
+            continue
+        pred, gt = metrics.as_mesh(pred), metrics.as_mesh(gt)
+        scores[key] = metrics.mesh_metrics(pred, gt, n=n, seed=seed)
+        views = metrics.turntable_views(data["calib"], tuple(normal_views), metrics.box_centre(gt))
+        ne = metrics.normal_error(pred, gt, views, size=normal_size)
+        scores[key].update(normal_error=ne["normal_error"], normal_per_view=ne["per_view"], mask_iou=ne["mask_iou"])
+    return scores
 
 
 def gen_mesh_pipelined(opt, net, cuda, dataset, indices, save_path_of, use_octree=True, write=True):
