@@ -1120,6 +1120,92 @@ int surs_optim_step(const SursOptimItem *items, int n_items, const SursOptimHype
  * refuses.  What the kernel is held against bit for bit, and torch.optim without a device; not a path of the product. */
 int surs_optim_step_host(const SursOptimItem *items, int n_items, const SursOptimHyper *h);
 
+/* ---------------------------------------------------------------- training images
+ * The image half of a training item (lib/data/TrainDataset_LR_v2.py:258-342) from the decoded uint8 pixels of one view: pad, flip,
+ * --random_scale resize, crop, torchvision's ColorJitter, --aug_blur, the BICUBIC / NEAREST half-size pair and the float32 step of
+ * surs_image_prepare.  Every 8-bit intermediate is byte for byte what Pillow gives for the same parameters (INTEGRATION.md "Training
+ * images" names the version checked); the arithmetic is csrc/surs_train_image.h, one for host and device.  What Pillow computes per
+ * image in double - filter weights, nearest indices, box lengths - is computed by surs_train_image_plan on the HOST, into a plan (a
+ * plain struct, a kernel argument) and a block of tables the caller copies to the device.  No float atomics, no host
+ * synchronisation: equal arguments give equal bits.
+ *
+ * Images are tightly packed: rgb [h][w][3], mask [h][w], uint8.  Stages:
+ *   geometry  ImageOps.expand(pad, fill 0), the horizontal flip and crop((x0, y0, x0 + out_w, y0 + out_h)) are index maps of the
+ *             source fetch; in between, the render goes through Pillow's two-pass fixed-point resample (filter BILINEAR) to
+ *             full_w x full_h and the mask through NEAREST (the affine-scale path).  Only the window is computed; it is 0 where it
+ *             lies outside the resized image.  full size == padded size is a copy (weights 2^22 and 0), as in Pillow.
+ *   jitter    n_ops of brightness / contrast / saturation (Image.blend with the degenerate image) and hue (8-bit HSV and back), in
+ *             the plan's order.  The contrast mean is the exact integer sum of L over the image as it stands: one uint32 partial sum
+ *             per workgroup of 1024 pixels into the workspace, added up by every workgroup of the second pass.
+ *   blur      GaussianBlur(radius): three extended-box passes along x, then three along y, each rounded to 8 bits.
+ *   pair      render_LR = BICUBIC to (w / 2, h / 2), mask_LR = NEAREST, fused with the float32 step; surs_image_prepare for HR.
+ * With augment == 0 (phase test) only the pair runs, on the source as it is. */
+enum { SURS_FILTER_NEAREST = 0, SURS_FILTER_BILINEAR = 2, SURS_FILTER_BICUBIC = 3 };   /* Pillow's numbers */
+enum { SURS_JITTER_BRIGHTNESS = 0, SURS_JITTER_CONTRAST = 1, SURS_JITTER_SATURATION = 2, SURS_JITTER_HUE = 3 };
+
+/* One resample: source, index maps, target size, window, and where its tables lie (byte offsets into the plan's table block).
+ * Per axis: bounds [out][2] (first source index, count), weights [out][ksize], nearest [out] (-1: outside), tile spans [tiles][2]
+ * (first and one-past-last source index any output of a 32-pixel tile reads); all int32. */
+typedef struct SursImageResample {
+    int src_w, src_h;          /* the stored source image */
+    int pad, flip;             /* a zero border of pad pixels on every side, then a horizontal flip */
+    int full_w, full_h;        /* the size the padded image is resampled to */
+    int x0, y0, out_w, out_h;  /* the window of the resampled image that is computed */
+    int filter;                /* SURS_FILTER_BILINEAR or SURS_FILTER_BICUBIC (the render); the mask is always NEAREST */
+    int ksize_x, ksize_y;
+    int off_xb, off_xk, off_xn, off_xt, off_yb, off_yk, off_yn, off_yt;
+    int reserved;
+} SursImageResample;
+
+typedef struct SursTrainImagePlan {
+    int augment;               /* 1: geometry, jitter, blur, pair; 0: pair only (geo is not read) */
+    int w, h;                  /* the HR image: geo's window, or the source with augment 0 */
+    SursImageResample geo, lr;
+    int n_ops;                 /* jitter ops in the order applied */
+    int op_kind[4];            /* SURS_JITTER_* */
+    float op_factor[4];        /* the blend factor of the first three kinds */
+    int hue_shift;             /* (int)(hue_factor * 255) & 255 */
+    int blur_radius;           /* per box pass: integer part, ww and fw of BoxBlur.c; ww == 0: no blur */
+    unsigned blur_ww, blur_fw;
+    unsigned long long tables_bytes;
+} SursTrainImagePlan;
+
+/* Fills *r and, where `tables` is not NULL, its tables from byte `base` of the block on (a HOST block of tables_bytes); returns the
+ * bytes the tables take through *used (nullable).  SURS_E_INVALID: sizes < 1, a filter other than the two above, a block too small,
+ * or a tile that needs more than 80 source pixels along an axis (a reduction beyond about 2.2 for BICUBIC). */
+int surs_image_resample_plan(int src_w, int src_h, int pad, int flip, int full_w, int full_h, int filter, int x0, int y0, int out_w,
+                             int out_h, SursImageResample *r, void *tables, size_t tables_bytes, size_t base, size_t *used);
+/* The plan of one view.  order[4]: torchvision's fn_idx; factor[4]: brightness, contrast, saturation, hue; bit k of active: op k
+ * has a non-zero amount (the others are skipped, as torchvision skips None).  blur_radius: GaussianBlur's (0: none).  With augment 0
+ * everything but src_w, src_h is ignored.  tables NULL: only *plan (with tables_bytes) is filled.  SURS_E_INVALID also for a box
+ * radius per pass above 20 (a Gaussian radius above about 21.4) and an order that is no permutation. */
+int surs_train_image_plan(int src_w, int src_h, int augment, int pad, int flip, int full_w, int full_h, int x0, int y0, int out_w,
+                          int out_h, const int *order, const double *factor, int active, double blur_radius,
+                          SursTrainImagePlan *plan, void *tables, size_t tables_bytes);
+/* Two HR renders, the HR mask and the partial sums; 0 for a NULL plan */
+size_t surs_train_images_workspace_bytes(const SursTrainImagePlan *plan);
+/* The whole chain of one view on `stream`: tables, rgb, mask, workspace DEVICE.  img_hr [h][w][3], img_lr [h/2][w/2][3] fp32. */
+int surs_train_images(const SursTrainImagePlan *plan, const void *tables, const unsigned char *rgb, const unsigned char *mask,
+                      void *workspace, size_t workspace_bytes, float *img_hr, float *img_lr, void *stream);
+/* The stages alone, for tests and tools.  jitter: workspace of surs_train_images_workspace_bytes; in == out is allowed.  blur: tmp
+ * [h][w][3], in, tmp and out distinct. */
+int surs_image_resample(const SursImageResample *r, const void *tables, const unsigned char *rgb, unsigned char *out, void *stream);
+int surs_image_nearest(const SursImageResample *r, const void *tables, const unsigned char *mask, unsigned char *out, void *stream);
+int surs_image_jitter(const SursTrainImagePlan *plan, const unsigned char *rgb, int w, int h, void *workspace, size_t workspace_bytes,
+                      unsigned char *out, void *stream);
+int surs_image_blur(const SursTrainImagePlan *plan, const unsigned char *rgb, int w, int h, unsigned char *tmp, unsigned char *out,
+                    void *stream);
+/* The same header looped on the HOST (every pointer a host pointer, no workspace): what the kernels are held against bit for bit,
+ * and what is held against Pillow. */
+int surs_train_images_host(const SursTrainImagePlan *plan, const void *tables, const unsigned char *rgb, const unsigned char *mask,
+                           float *img_hr, float *img_lr);
+int surs_image_resample_host(const SursImageResample *r, const void *tables, const unsigned char *rgb, unsigned char *out);
+int surs_image_nearest_host(const SursImageResample *r, const void *tables, const unsigned char *mask, unsigned char *out);
+int surs_image_jitter_host(const SursTrainImagePlan *plan, const unsigned char *rgb, int w, int h, unsigned char *out);
+int surs_image_blur_host(const SursTrainImagePlan *plan, const unsigned char *rgb, int w, int h, unsigned char *out);
+/* RGB -> Pillow's 8-bit HSV and back on n pixels of 3 bytes, host: the exhaustive check of the hue op's two conversions */
+int surs_image_hsv_host(const unsigned char *in, long long n, int inverse, unsigned char *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -147,8 +147,25 @@ class OptimHyper(C.Structure):
         "lr", "weight_decay", "momentum", "beta1_c", "beta2", "beta2_c", "alpha", "alpha_c", "eps", "step_size", "bc2_sqrt")]
 
 
+class ImageResample(C.Structure):
+    """SursImageResample of include/surs.h: one resample's source, index maps, target, window and table offsets."""
+    _fields_ = [(k, C.c_int) for k in ("src_w", "src_h", "pad", "flip", "full_w", "full_h", "x0", "y0", "out_w", "out_h", "filter",
+                                       "ksize_x", "ksize_y", "off_xb", "off_xk", "off_xn", "off_xt", "off_yb", "off_yk", "off_yn",
+                                       "off_yt", "reserved")]
+
+
+class TrainImagePlan(C.Structure):
+    """SursTrainImagePlan of include/surs.h: one view's drawn parameters, a kernel argument."""
+    _fields_ = [("augment", C.c_int), ("w", C.c_int), ("h", C.c_int), ("geo", ImageResample), ("lr", ImageResample), ("n_ops", C.c_int),
+                ("op_kind", C.c_int * 4), ("op_factor", C.c_float * 4), ("hue_shift", C.c_int), ("blur_radius", C.c_int),
+                ("blur_ww", C.c_uint), ("blur_fw", C.c_uint), ("tables_bytes", C.c_ulonglong)]
+
+
 OPTIM_SGD, OPTIM_ADAM, OPTIM_AMSGRAD, OPTIM_RMSPROP = 0, 1, 2, 3     # SURS_OPTIM_* of include/surs.h
+FILTER_NEAREST, FILTER_BILINEAR, FILTER_BICUBIC = 0, 2, 3            # SURS_FILTER_* of include/surs.h (Pillow's numbers)
+JITTER_BRIGHTNESS, JITTER_CONTRAST, JITTER_SATURATION, JITTER_HUE = 0, 1, 2, 3     # SURS_JITTER_*
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
+_rsp, _tip = C.POINTER(ImageResample), C.POINTER(TrainImagePlan)
 _shp = C.POINTER(MlpShape)
 _SIGS = {
     "surs_abi_version": (C.c_int, []),
@@ -324,6 +341,21 @@ _SIGS = {
     "surs_optim_check": (C.c_int, [_vp, _i, C.POINTER(OptimHyper)]),
     "surs_optim_step": (C.c_int, [_vp, _i, C.POINTER(OptimHyper), _vp]),
     "surs_optim_step_host": (C.c_int, [_vp, _i, C.POINTER(OptimHyper)]),
+    "surs_image_resample_plan": (C.c_int, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _rsp, _vp, _sz, _sz, C.POINTER(_sz)]),
+    "surs_train_image_plan": (C.c_int, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_double), _i,
+                                        C.c_double, _tip, _vp, _sz]),
+    "surs_train_images_workspace_bytes": (_sz, [_tip]),
+    "surs_train_images": (C.c_int, [_tip, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "surs_image_resample": (C.c_int, [_rsp, _vp, _vp, _vp, _vp]),
+    "surs_image_nearest": (C.c_int, [_rsp, _vp, _vp, _vp, _vp]),
+    "surs_image_jitter": (C.c_int, [_tip, _vp, _i, _i, _vp, _sz, _vp, _vp]),
+    "surs_image_blur": (C.c_int, [_tip, _vp, _i, _i, _vp, _vp, _vp]),
+    "surs_train_images_host": (C.c_int, [_tip, _vp, _vp, _vp, _vp, _vp]),
+    "surs_image_resample_host": (C.c_int, [_rsp, _vp, _vp, _vp]),
+    "surs_image_nearest_host": (C.c_int, [_rsp, _vp, _vp, _vp]),
+    "surs_image_jitter_host": (C.c_int, [_tip, _vp, _i, _i, _vp]),
+    "surs_image_blur_host": (C.c_int, [_tip, _vp, _i, _i, _vp]),
+    "surs_image_hsv_host": (C.c_int, [_vp, C.c_longlong, _i, _vp]),
 }
 MESH_FACES_PER_PART, SAMPLE_SELECT_CHUNK = 4096, 1024     # SURS_MESH_FACES_PER_PART, SURS_SAMPLE_SELECT_CHUNK of include/surs.h
 EXPORTS = sorted(_SIGS)

@@ -110,6 +110,83 @@ class DeviceInputStage:
         return out.permute(0, 3, 1, 2)
 
 
+JITTER_OPTIONS = ("aug_bri", "aug_con", "aug_sat", "aug_hue")
+
+
+def jitter_params(opt):
+    """torchvision's ColorJitter.get_params for --aug_bri / --aug_con / --aug_sat / --aug_hue, drawn from torch's global generator:
+    (order, b, c, s, h).  First order = torch.randperm(4); then, in the order brightness, contrast, saturation, hue, one
+    float(torch.empty(1).uniform_(lo, hi)) for each op whose amount a is non-zero - [max(0, 1 - a), 1 + a] for the first three,
+    [-a, a] for hue -; an op with amount 0 draws nothing and is None (skipped).  The ops are applied in `order` (0 brightness,
+    1 contrast, 2 saturation, 3 hue).  0 <= a <= 0.5."""
+    amounts = [float(getattr(opt, k, 0.0) or 0.0) for k in JITTER_OPTIONS]
+    for k, a in zip(JITTER_OPTIONS, amounts):
+        if not 0.0 <= a <= 0.5:
+            raise ValueError("--%s %g: an amount in [0, 0.5] is needed" % (k, a))
+    order = tuple(int(i) for i in torch.randperm(4))
+    vals = []
+    for k, a in enumerate(amounts):
+        if a == 0.0:
+            vals.append(None)
+            continue
+        lo, hi = (-a, a) if k == 3 else (max(0.0, 1.0 - a), 1.0 + a)
+        vals.append(float(torch.empty(1).uniform_(lo, hi)))
+    return (order,) + tuple(vals)
+
+
+class TrainImageStage:
+    """Decoded uint8 pixels of one view -> (img_HR [3,H,W], img_LR [3,H/2,W/2]) float32 through native.train_images: NHWC in
+    memory, NCHW-shaped views, as DeviceInputStage gives them.  Pixels and the plan's tables go through pinned staging buffers
+    (reused, grown on demand) and asynchronous uploads on the current stream; the workspace is reused.  device=None runs the host
+    twins and returns host tensors."""
+
+    def __init__(self, device):
+        self.device = device
+        self._pin = {}
+        self._ws = None
+
+    def _staged(self, key, a):
+        a = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+        ent = self._pin.get(key)
+        if ent is None or ent[0].numel() < a.size:
+            if ent is not None and ent[1] is not None:
+                ent[1].synchronize()
+            ent = self._pin[key] = [torch.empty(max(a.size, 1), dtype=torch.uint8, pin_memory=True), None]
+        buf, uploaded = ent
+        if uploaded is not None:
+            uploaded.synchronize()   # the previous view's upload has read the buffer: only now may the host overwrite it
+        buf.numpy()[:a.size] = a
+        d = buf[:a.size].to(self.device, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        ent[1] = ev
+        return d
+
+    def empty(self, shape):
+        """An uninitialised float32 tensor where run() writes: on the stage's device, or on the host."""
+        return torch.empty(shape, dtype=torch.float32, device=self.device if self.device is not None else "cpu")
+
+    def run(self, plan, rgb, mask, out=None):
+        """out: (img_hr [H,W,3], img_lr [H/2,W/2,3]) contiguous float32 tensors to write into, e.g. one view's slices of an item's
+        [V,H,W,3] tensors; they are returned as the [3,H,W] views."""
+        from . import native
+        if out is None:
+            h, w = plan.size
+            out = (self.empty((h, w, 3)), self.empty((h // 2, w // 2, 3)))
+        if self.device is None:
+            native.train_images(plan, rgb, mask, host=True, out=(out[0].numpy(), out[1].numpy()))
+            return out[0].permute(2, 0, 1), out[1].permute(2, 0, 1)
+        h, w = mask.shape
+        assert rgb.shape == (h, w, 3) and rgb.dtype == np.uint8 and mask.dtype == np.uint8
+        d_rgb, d_mask = self._staged("rgb", rgb).view(h, w, 3), self._staged("mask", mask).view(h, w)
+        d_tables = self._staged("tables", plan.tables)
+        nbytes = native.lib().surs_train_images_workspace_bytes(plan.plan)
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        native.train_images(plan, d_rgb, d_mask, tables=d_tables, workspace=self._ws, out=out)
+        return out[0].permute(2, 0, 1), out[1].permute(2, 0, 1)
+
+
 class SyntheticDataset:
     """Stand-in with the same item contract when there is no dataroot (--synthetic): seeded images."""
 
@@ -158,16 +235,25 @@ class TrainDataset:
     answer.  Meshes are parsed and uploaded once per subject, at their first use.  Phase 'test' draws every item's samples
     from seed 1991 (the reference re-seeds with 1991 before each item); phase 'train' derives the seed from (seed, index, how
     many items this object has drawn).  The samples are made on the GPU of the calling process, so the dataset refuses to run
-    in a DataLoader worker: use --num_threads 0.  get_color_sampling is not built (SuRS trains with --num_sample_color 0)."""
+    in a DataLoader worker: use --num_threads 0.  get_color_sampling is not built (SuRS trains with --num_sample_color 0).
 
-    _JITTER = ("aug_bri", "aug_con", "aug_sat", "aug_hue")
+    images=None is the PIL path above.  images='device' builds img_LR / img_HR on the device from the decoded pixels
+    (native.train_images through a TrainImageStage: DEVICE tensors, NHWC in memory, NCHW-shaped), images='cpu' through the same
+    chain's host twins (host tensors); both take the colour jitter, drawn by jitter_params, and with jitter 0 give the bits of the
+    PIL path for the same `random` / `np.random` state."""
+
+    _JITTER = JITTER_OPTIONS
     TEST_SEED = 1991
 
-    def __init__(self, opt, phase="train", seed=0):
+    def __init__(self, opt, phase="train", seed=0, images=None):
+        if images not in (None, "device", "cpu"):
+            raise ValueError("images=%r: None (PIL on the host), 'device' or 'cpu' (the native chain) is needed" % (images,))
         for k in self._JITTER:
-            if float(getattr(opt, k, 0.0)) != 0.0:
+            if images is None and float(getattr(opt, k, 0.0)) != 0.0:
                 raise NotImplementedError("--%s %g: colour jitter (torchvision ColorJitter) is not built; only 0 is accepted"
                                           % (k, getattr(opt, k)))
+        self.images = images
+        self._stage = None
         self.opt = opt
         self.projection_mode = "orthogonal"
         self.root = opt.dataroot
@@ -212,6 +298,8 @@ class TrainDataset:
         import random
         from PIL import Image, ImageOps
         from PIL.ImageFilter import GaussianBlur
+        if self.images is not None:
+            return self._get_render_native(subject, num_views, yid, pid, random_sample)
         pitch = self.pitch_list[pid]
         view_ids = [self.yaw_list[(yid + len(self.yaw_list) // num_views * offset) % len(self.yaw_list)] for offset in range(num_views)]
         if random_sample:
@@ -285,6 +373,89 @@ class TrainDataset:
             out["calib"].append(torch.from_numpy(calib))
             out["extrinsic"].append(torch.from_numpy(extrinsic.astype(np.float32)))
         return {k: torch.stack(v, dim=0) for k, v in out.items()}
+
+    def _get_render_native(self, subject, num_views, yid=0, pid=0, random_sample=False):
+        """get_render with images='device' / 'cpu': PIL decodes the files and nothing else; the draws from `random` / `np.random`
+        are get_render's, same calls in the same order, the colour jitter's are jitter_params' (torch's generator, where the
+        reference calls aug_trans); the pixel work is native.train_images through a TrainImageStage."""
+        import random
+        from PIL import Image
+        from . import native
+        if self._stage is None:
+            self._stage = TrainImageStage(native.require_gpu() if self.images == "device" else None)
+        pitch = self.pitch_list[pid]
+        view_ids = [self.yaw_list[(yid + len(self.yaw_list) // num_views * offset) % len(self.yaw_list)] for offset in range(num_views)]
+        if random_sample:
+            view_ids = np.random.choice(self.yaw_list, num_views, replace=False)
+        half = float(self.opt.loadSize // 2)
+        out = {"calib": [], "extrinsic": []}
+        img_hr = img_lr = None
+        for vid in view_ids:
+            stem = "%d_%d_%02d" % (vid, pitch, 0)
+            param_path = os.path.join(self.PARAM, subject, stem + ".npy")
+            render_path = EvalDataset._first_existing(os.path.join(self.RENDER, subject, stem + ".jpg"),
+                                                      os.path.join(self.RENDER, subject, stem + ".png"))
+            mask_path = EvalDataset._first_existing(os.path.join(self.MASK, subject, stem + ".png"),
+                                                    os.path.join(self.MASK, subject, stem + ".jpg"))
+            param = np.load(param_path, allow_pickle=True).item()
+            ortho_ratio, scale, center, R = param.get("ortho_ratio"), param.get("scale"), param.get("center"), param.get("R")
+            translate = -np.matmul(R, center).reshape(3, 1)
+            extrinsic = np.concatenate([R, translate], axis=1)
+            extrinsic = np.concatenate([extrinsic, np.array([0, 0, 0, 1]).reshape(1, 4)], 0)
+            scale_intrinsic = np.identity(4)
+            scale_intrinsic[0, 0] = scale / ortho_ratio
+            scale_intrinsic[1, 1] = -scale / ortho_ratio
+            scale_intrinsic[2, 2] = scale / ortho_ratio
+            uv_intrinsic = np.identity(4)
+            uv_intrinsic[0, 0] = uv_intrinsic[1, 1] = uv_intrinsic[2, 2] = 1.0 / half
+            trans_intrinsic = np.identity(4)
+            mask8 = np.ascontiguousarray(np.asarray(Image.open(mask_path).convert("L"), np.uint8))
+            rgb8 = np.ascontiguousarray(np.asarray(Image.open(render_path).convert("RGB"), np.uint8))
+            if mask8.shape != rgb8.shape[:2]:
+                raise ValueError("%s is %s and %s is %s: a render and its mask must have one size"
+                                 % (render_path, rgb8.shape[:2], mask_path, mask8.shape))
+            if self.is_train:
+                pad_size = int(0.1 * self.load_size)
+                w, h = rgb8.shape[1] + 2 * pad_size, rgb8.shape[0] + 2 * pad_size
+                th, tw = self.load_size, self.load_size
+                flip = bool(self.opt.random_flip and np.random.rand() > 0.5)
+                if flip:
+                    scale_intrinsic[0, 0] *= -1
+                if self.opt.random_scale:
+                    rand_scale = random.uniform(0.9, 1.1)
+                    w = int(rand_scale * w)
+                    h = int(rand_scale * h)
+                    scale_intrinsic *= rand_scale
+                    scale_intrinsic[3, 3] = 1
+                if self.opt.random_trans:
+                    dx = random.randint(-int(round((w - tw) / 10.)), int(round((w - tw) / 10.)))
+                    dy = random.randint(-int(round((h - th) / 10.)), int(round((h - th) / 10.)))
+                else:
+                    dx = dy = 0
+                trans_intrinsic[0, 3] = -dx / half
+                trans_intrinsic[1, 3] = -dy / half
+                x1 = int(round((w - tw) / 2.)) + dx
+                y1 = int(round((h - th) / 2.)) + dy
+                jitter = jitter_params(self.opt)
+                blur = np.random.uniform(0, self.opt.aug_blur) if self.opt.aug_blur > 0.00001 else 0.0
+                plan = native.train_image_plan(mask8.shape, pad=pad_size, flip=flip, full=(h, w), window=(x1, y1, tw, th), jitter=jitter,
+                                               blur=blur)
+            else:
+                plan = native.train_image_plan(mask8.shape, augment=False)
+            intrinsic = np.matmul(trans_intrinsic, np.matmul(uv_intrinsic, scale_intrinsic))
+            calib = np.matmul(intrinsic, extrinsic).astype(np.float32)
+            if img_hr is None:   # [V,H,W,3] and [V,H/2,W/2,3]: every view is written into its slice, NHWC in memory
+                h_hr, w_hr = plan.size
+                img_hr = self._stage.empty((len(view_ids), h_hr, w_hr, 3))
+                img_lr = self._stage.empty((len(view_ids), h_hr // 2, w_hr // 2, 3))
+            elif plan.size != tuple(img_hr.shape[1:3]):
+                raise ValueError("%s makes an image of %s, the views before it one of %s" % (render_path, plan.size, tuple(img_hr.shape[1:3])))
+            self._stage.run(plan, rgb8, mask8, out=(img_hr[len(out["calib"])], img_lr[len(out["calib"])]))
+            out["calib"].append(torch.from_numpy(calib))
+            out["extrinsic"].append(torch.from_numpy(extrinsic.astype(np.float32)))
+        res = {"img_LR": img_lr.permute(0, 3, 1, 2), "img_HR": img_hr.permute(0, 3, 1, 2)}
+        res.update({k: torch.stack(v, dim=0) for k, v in out.items()})
+        return res
 
     def item_seed(self, index=0):
         """The counter PRNG's seed of the next item's samples."""

@@ -2514,3 +2514,186 @@ def normal_map_host(verts, faces, view, size, vertex_normals=None):
                                              vn.ctypes.data if vn is not None else None, nm.ctypes.data if nm is not None else None,
                                              face.ctypes.data, bary.ctypes.data, w, h, out.ctypes.data))
     return out, face >= 0
+
+
+# ------------------------------------------------------------------ training images
+
+class ImagePlan:
+    """A SursTrainImagePlan (`.plan`, the ctypes struct) with its HOST tables (`.tables`, numpy uint8): what
+    surs_train_image_plan fills from one view's drawn parameters."""
+
+    def __init__(self, plan, tables):
+        self.plan, self.tables = plan, tables
+
+    @property
+    def size(self):
+        """(h, w) of the HR image."""
+        return self.plan.h, self.plan.w
+
+
+def _jitter_args(jitter):
+    order, vals = ((0, 1, 2, 3), (None,) * 4) if jitter is None else (tuple(jitter[0]), tuple(jitter[1:]))
+    if len(order) != 4 or len(vals) != 4:
+        raise ValueError("jitter: (order, brightness, contrast, saturation, hue) expected, a factor None where the op is off")
+    factors = (C.c_double * 4)(*[0.0 if v is None else float(v) for v in vals])
+    return (C.c_int * 4)(*[int(k) for k in order]), factors, sum(1 << k for k, v in enumerate(vals) if v is not None)
+
+
+def train_image_plan(src_size, augment=True, pad=0, flip=False, full=None, window=None, jitter=None, blur=0.0):
+    """The plan of one view (surs_train_image_plan).  src_size (h, w) of the decoded image; pad, flip; full (h, w): the size the
+    padded image is resized to (default: its own); window (x0, y0, w, h): the crop (default: all of it); jitter: what
+    data.jitter_params returns, (order, b, c, s, h) with None for an op that is off; blur: GaussianBlur's radius.  augment False:
+    the half-size pair only (phase test)."""
+    h, w = (int(v) for v in src_size)
+    full_h, full_w = (h + 2 * pad, w + 2 * pad) if full is None else (int(v) for v in full)
+    x0, y0, ow, oh = (0, 0, full_w, full_h) if window is None else (int(v) for v in window)
+    order, factors, active = _jitter_args(jitter)
+    plan = _lib.TrainImagePlan()
+    args = (w, h, int(bool(augment)), int(pad), int(bool(flip)), full_w, full_h, x0, y0, ow, oh, order, factors, active, float(blur))
+    check(lib().surs_train_image_plan(*args, C.byref(plan), None, 0))
+    tables = np.zeros(int(plan.tables_bytes), np.uint8)
+    check(lib().surs_train_image_plan(*args, C.byref(plan), tables.ctypes.data, tables.nbytes))
+    return ImagePlan(plan, tables)
+
+
+def _u8_host(a, shape_tail):
+    a = np.ascontiguousarray(np.asarray(a, np.uint8))
+    if a.ndim != 2 + len(shape_tail) or a.shape[2:] != shape_tail:
+        raise ValueError("uint8 image of shape [h, w%s] expected, not %s" % ("".join(", %d" % s for s in shape_tail), a.shape))
+    return a
+
+
+def _u8_dev(t, shape_tail):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == 2 + len(shape_tail)
+            and tuple(t.shape[2:]) == shape_tail):
+        raise ValueError("contiguous uint8 device tensor of shape [h, w%s] expected" % "".join(", %d" % s for s in shape_tail))
+    return t
+
+
+def _dev_tables(tables, device):
+    return torch.from_numpy(tables).to(device)
+
+
+def _check_pair(hr, lr, h, w, dtype):
+    if tuple(hr.shape) != (h, w, 3) or tuple(lr.shape) != (h // 2, w // 2, 3) or hr.dtype != dtype or lr.dtype != dtype:
+        raise ValueError("out: float32 (img_hr [%d,%d,3], img_lr [%d,%d,3]) expected" % (h, w, h // 2, w // 2))
+
+
+def train_images(plan, rgb, mask, host=False, tables=None, workspace=None, out=None):
+    """surs_train_images: (img_hr float32 [h,w,3], img_lr float32 [h/2,w/2,3]) of one view, NHWC.  rgb [H,W,3], mask [H,W] uint8:
+    device tensors (tables: the plan's tables on the device, uploaded here when None; workspace: a uint8 device tensor to reuse),
+    or with host=True numpy arrays through surs_train_images_host.  out: (img_hr, img_lr) to write into, contiguous, of the kind
+    returned."""
+    p = plan.plan
+    h, w = plan.size
+    src = (p.geo.src_h, p.geo.src_w) if p.augment else (h, w)
+    if host:
+        rgb, mask = _u8_host(rgb, (3,)), _u8_host(mask, ())
+        if rgb.shape[:2] != src or mask.shape != src:
+            raise ValueError("the plan is for a source of %s, not rgb %s / mask %s" % (src, rgb.shape, mask.shape))
+        hr, lr = (np.empty((h, w, 3), np.float32), np.empty((h // 2, w // 2, 3), np.float32)) if out is None else out
+        _check_pair(hr, lr, h, w, np.float32)
+        if not (hr.flags.c_contiguous and lr.flags.c_contiguous):
+            raise ValueError("out: contiguous arrays expected")
+        check(lib().surs_train_images_host(C.byref(p), plan.tables.ctypes.data, rgb.ctypes.data, mask.ctypes.data, hr.ctypes.data,
+                                           lr.ctypes.data))
+        return hr, lr
+    rgb, mask = _u8_dev(rgb, (3,)), _u8_dev(mask, ())
+    if tuple(rgb.shape[:2]) != src or tuple(mask.shape) != src:
+        raise ValueError("the plan is for a source of %s, not rgb %s / mask %s" % (src, tuple(rgb.shape), tuple(mask.shape)))
+    dev = rgb.device
+    if tables is None:
+        tables = _dev_tables(plan.tables, dev)
+    nbytes = lib().surs_train_images_workspace_bytes(C.byref(p))
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = (torch.empty((h, w, 3), dtype=torch.float32, device=dev), torch.empty((h // 2, w // 2, 3), dtype=torch.float32, device=dev))
+    hr, lr = out
+    _check_pair(hr, lr, h, w, torch.float32)
+    if not (hr.is_cuda and lr.is_cuda and hr.is_contiguous() and lr.is_contiguous()):
+        raise ValueError("out: contiguous device tensors expected")
+    check(lib().surs_train_images(C.byref(p), _ptr(tables), _ptr(rgb), _ptr(mask), _ptr(workspace), workspace.numel(), _ptr(hr), _ptr(lr),
+                                  _stream()))
+    return hr, lr
+
+
+def _resample_plan(src_size, size, filter, window, pad, flip):
+    h, w = (int(v) for v in src_size)
+    full_h, full_w = (int(v) for v in size)
+    x0, y0, ow, oh = (0, 0, full_w, full_h) if window is None else (int(v) for v in window)
+    r, used = _lib.ImageResample(), C.c_size_t(0)
+    args = (w, h, int(pad), int(bool(flip)), full_w, full_h, int(filter), x0, y0, ow, oh)
+    check(lib().surs_image_resample_plan(*args, C.byref(r), None, 0, 0, C.byref(used)))
+    tables = np.zeros(used.value, np.uint8)
+    check(lib().surs_image_resample_plan(*args, C.byref(r), tables.ctypes.data, tables.nbytes, 0, None))
+    return r, tables
+
+
+def _resample_stage(name, tail, img, size, filter, window, pad, flip, host):
+    img = _u8_host(img, tail) if host else _u8_dev(img, tail)
+    r, tables = _resample_plan(img.shape[:2], size, filter, window, pad, flip)
+    shape = (r.out_h, r.out_w) + tail
+    if host:
+        out = np.empty(shape, np.uint8)
+        check(getattr(lib(), name + "_host")(C.byref(r), tables.ctypes.data, img.ctypes.data, out.ctypes.data))
+        return out
+    out = torch.empty(shape, dtype=torch.uint8, device=img.device)
+    d_tables = _dev_tables(tables, img.device)
+    check(getattr(lib(), name)(C.byref(r), _ptr(d_tables), _ptr(img), _ptr(out), _stream()))
+    return out
+
+
+def image_resample(img, size, filter=_lib.FILTER_BILINEAR, window=None, pad=0, flip=False, host=False):
+    """Pillow's img.resize(size, filter) of an RGB image [h,w,3] uint8 (after a zero border of `pad` and a horizontal flip), of
+    which only window (x0, y0, w, h) is computed - zeros where it lies outside.  size (h, w); FILTER_BILINEAR or FILTER_BICUBIC.
+    A device tensor, or with host=True a numpy array through the host twin."""
+    return _resample_stage("surs_image_resample", (3,), img, size, filter, window, pad, flip, host)
+
+
+def image_nearest(img, size, window=None, pad=0, flip=False, host=False):
+    """Pillow's img.resize(size, NEAREST) of an 8-bit mask [h,w], with the window, pad and flip of image_resample."""
+    return _resample_stage("surs_image_nearest", (), img, size, _lib.FILTER_BILINEAR, window, pad, flip, host)
+
+
+def image_jitter(img, jitter, host=False):
+    """torchvision's ColorJitter with drawn parameters on an RGB image [h,w,3] uint8: jitter = (order, b, c, s, h), a factor None
+    where the op is off (data.jitter_params)."""
+    img = _u8_host(img, (3,)) if host else _u8_dev(img, (3,))
+    h, w = img.shape[:2]
+    plan = train_image_plan((h, w), jitter=jitter)
+    if host:
+        out = np.empty((h, w, 3), np.uint8)
+        check(lib().surs_image_jitter_host(C.byref(plan.plan), img.ctypes.data, w, h, out.ctypes.data))
+        return out
+    out = torch.empty((h, w, 3), dtype=torch.uint8, device=img.device)
+    nbytes = lib().surs_train_images_workspace_bytes(C.byref(plan.plan))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=img.device)
+    check(lib().surs_image_jitter(C.byref(plan.plan), _ptr(img), w, h, _ptr(ws), nbytes, _ptr(out), _stream()))
+    return out
+
+
+def image_blur(img, radius, host=False):
+    """Pillow's img.filter(GaussianBlur(radius)) of an RGB image [h,w,3] uint8."""
+    img = _u8_host(img, (3,)) if host else _u8_dev(img, (3,))
+    h, w = img.shape[:2]
+    plan = train_image_plan((h, w), blur=radius)
+    if host:
+        out = np.empty((h, w, 3), np.uint8)
+        check(lib().surs_image_blur_host(C.byref(plan.plan), img.ctypes.data, w, h, out.ctypes.data))
+        return out
+    out, tmp = torch.empty((h, w, 3), dtype=torch.uint8, device=img.device), torch.empty((h, w, 3), dtype=torch.uint8, device=img.device)
+    check(lib().surs_image_blur(C.byref(plan.plan), _ptr(img), w, h, _ptr(tmp), _ptr(out), _stream()))
+    return out
+
+
+def image_hsv_host(pixels, inverse=False):
+    """RGB -> Pillow's 8-bit HSV (inverse: back) on [..., 3] uint8, on the host."""
+    a = np.ascontiguousarray(np.asarray(pixels, np.uint8))
+    out = np.empty_like(a)
+    check(lib().surs_image_hsv_host(a.ctypes.data, a.size // 3, int(bool(inverse)), out.ctypes.data))
+    return out
+
+
+# TI_TILE (the side of a resample and of a blur tile) and TI_JITTER_PIXELS (pixels of one partial sum) of csrc/surs_train_image.h
+IMAGE_TILE, JITTER_GROUP_PIXELS = 32, 1024
