@@ -227,8 +227,13 @@ __device__ __forceinline__ void split3(float x, unsigned short &a, unsigned shor
 }
 
 // Operand split of the 3x3 kernel: NP = 3 bf16 parts (six products per MAC, fp32's exponent range) or NP = 2 f16 parts
-// (hi = f16(x), lo = f16(x - hi); products hi*hi + hi*lo + lo*hi: half the MFMA work, 22 significant bits, |x| < 65504 - the
-// split of the fp32-grade column kernel).  Both pass the encoder's 1e-4 parity tests; two parts is the default.
+// (hi = f16(x), lo = f16(x - hi); products hi*hi + hi*lo + lo*hi: half the MFMA work - the split of the fp32-grade column kernel,
+// DESIGN.md 4.1b).  Both pass the encoder's 1e-4 parity tests; two parts is the default.  Its window has two ends (DESIGN.md 4.5,
+// tests/conv_model.py): above, |x| < 65504 (f16 infinity beyond; the callers repeat on three parts); below, lo is a subnormal f16
+// once |x| < 2^-3 and gone below 2^-14, so an operand carries 22 significant bits down to 2^-3 and an ABSOLUTE error of 2^-25
+// under it.  Against the exact convolution that is fp32 grade (2e-5 of the output range) for a weight tensor with
+// max |w| >= W_MIN = 2^-8 and activations of magnitude >= 2^-9; smaller tensors lose 2^-25 / max |operand| of the range
+// (native.ConvWeights warns).  Three bf16 parts have fp32's exponent range: no window.
 template <int NP> struct ConvSplit;
 template <> struct ConvSplit<3> {
     typedef bf16x8 vec8;

@@ -328,8 +328,12 @@ def reconstruction(opt, net, cuda, calib_tensor, resolution, b_min, b_max, use_o
     """-> verts_hr, faces_hr, normals_hr, values_hr, verts_lr, faces_lr, normals_lr, values_lr  (numpy).
     features / after_enqueue: see reconstruction_streamed (single view only).
 
-    Range: with `--precision fp32` every fp32-grade product runs on two f16 parts per operand (|x| < 65504); the reference is
-    plain fp32.  A field that comes out non-finite (marching cubes reports it: NonFiniteVolumeError) is computed again on three
+    Range: with `--precision fp32` every fp32-grade product runs on two f16 parts per operand; the reference is plain fp32.  That
+    form has a window with two ends.  Above, |x| < 65504.  Below, an operand under 2^-3 carries an absolute error of 2^-25 (its
+    second part is a subnormal f16), so a tensor of magnitude m loses about 2^-25 / m of the output range: the encoder's
+    convolutions are fp32 grade (2e-5 of the range) for weight tensors with max |w| >= 2^-8 (native.CONV_W_MIN; ConvWeights warns
+    below it) and activations of magnitude >= 2^-9.  Nothing repeats a computation for the lower end; the upper
+    end shows itself: a field that comes out non-finite (marching cubes reports it: NonFiniteVolumeError) is computed again on three
     bf16 parts - fp32's exponent range - in every branch: the dense sweep on the per-point layer kernels ('fp32x'), the octree and
     multi-view sweeps under native.wide_operands(), and the encoder re-run the same way when its features are what overflowed."""
     called = []

@@ -121,6 +121,24 @@ def reduced_point_operands(on=True):
         check(lib().surs_set_operand_split_local(3 if wide_operands_active() else 0))
 
 
+# The lower edge of the two-f16-part convolutions' window for weights: the second part of an operand below 2^-3 is a subnormal f16, so
+# a weight carries an absolute error of 2^-25 and a tensor with max |w| = m loses 2^-25 / m of the output range.  CONV_W_MIN is the
+# smallest power of two from which that stays under half the fp32-grade bound of 2e-5 (the grade table of DESIGN.md 4.5, derived in
+# tests/conv_model.py and pinned by tests/test_conv_model_host.py).
+CONV_W_MIN = 2.0 ** -8
+
+
+def _warn_small_weights(w):
+    """One RuntimeWarning for a weight tensor whose two-part image is not fp32 grade (ConvWeights; host only)."""
+    peak = float(np.abs(w).max()) if w.size else 0.0
+    if 0.0 < peak < CONV_W_MIN:
+        import warnings
+        warnings.warn("convolution weights %s with max |w| = %.3g < %.3g: as two f16 parts per operand they lose about %.1e of the "
+                      "output range (2^-25 / max |w|; fp32 grade is 2e-5).  Pack them with SURS_CONV_SPLIT=bf16x3 or run the "
+                      "computation inside native.wide_operands()." % (tuple(w.shape), peak, CONV_W_MIN, 2.0 ** -25 / peak),
+                      RuntimeWarning, stacklevel=3)
+
+
 class ConvWeights:
     """Packed conv weights ([tap][cin_pad][cout_pad]) + bias on the device."""
 
@@ -146,6 +164,8 @@ class ConvWeights:
             buf = np.empty(nb, np.uint8)
             pack(w.ctypes.data_as(C.c_void_p), self.cout, self.cin, self.k, buf.ctypes.data_as(C.c_void_p))
             self.w3 = torch.from_numpy(buf).to(device)
+            if self.parts == 2 and not self.reduced:
+                _warn_small_weights(w)
 
     def split_image(self):
         """(packed split weights, parts) for the 3x3 / stride-1 kernel; inside wide_operands() the bf16 x 3 image, packed on first use."""
