@@ -10,11 +10,9 @@
 //                 db += sum_points dZ;  dW += dZ^T In (reduction over the points, split into fixed parts);
 //                 dZ_prev = (dZ W[:, :k1]) * LeakyReLU'(H_prev);  the skip part is needed for the q column only (d q)
 //
-// Arithmetic: ONE GEMM kernel, v_mfma_f32_32x32x2_f32 on fp32 operands with fp32 accumulation - fp32-grade whatever --precision
-// says: gradient operands reach 1e-12 and below, where an f16 split flushes them; fp32 inputs keep fp32's exponent range and all 24
-// bits.  64 x 64 output tile per workgroup of 4 waves (32 x 32 each), k step 16 through LDS (k-major, row stride 68 words),
-// operands addressed by two strides each so that X W^T, dZ W and dZ^T In are the same code; edges are zero-filled, so no width
-// has to be a multiple of anything.
+// Arithmetic: ONE GEMM kernel on the fp32-MFMA tile of surs_grad_tile.h (its arithmetic, LDS layout, pipeline and edge rule are
+// described there) - fp32-grade whatever --precision says; fp32 inputs keep fp32's exponent range and all 24 bits.  Operands are
+// addressed by two strides each so that X W^T, dZ W and dZ^T In are the same code.
 // Determinism: no float atomics.  The reduction over the points of a chunk is split into parts of GR_CHUNK / splits points (splits
 // depends on the layer's shape only), every part's product goes to its own slab of the workspace, and a second kernel adds the slabs
 // in order to the output; chunks, stacks and (accumulate = 1) images follow each other on the stream in a fixed order.
@@ -35,16 +33,14 @@
 #include <hip/hip_runtime.h>
 
 #include "surs_common.h"
+#include "surs_grad_tile.h"
 #include "surs_mlp_generic.h"
 
 namespace surs {
 namespace grad {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int GR_CHUNK = 2048;       // points per chunk
 constexpr int GR_MAX_SPLITS = 16;    // parts of the point reduction (GR_CHUNK / 16 = 128 points at least)
-constexpr int GR_TILE = 64, GR_KT = 16, GR_LDS = 68;
 constexpr int GR_MAX_STACKS = 64;
 
 // ------------------------------------------------------------------------------------------------ gather
@@ -123,17 +119,14 @@ struct GemmArgs {
     int add;              // EPI_ACC: C += the product (0: C = the product)
 };
 
-// AK: A's k index is the contiguous one (else its m index); BK: the same for B (else its n index) - which way the 64 x 16 tile is
-// walked by the 256 threads, so that neighbouring threads read neighbouring addresses
+// AK: A's k index is the contiguous one (else its m index); BK: the same for B (else its n index) - walk_k or walk_rows
 template <bool AK, bool BK, int EPI>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
-    __shared__ float As[GR_KT][GR_LDS], Bs[GR_KT][GR_LDS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1, kh = lane >> 5, li = lane & 31;
-    const int m0 = blockIdx.y * GR_TILE, n0 = blockIdx.x * GR_TILE;
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    __shared__ float As[GT_KT][GT_LDS], Bs[GT_KT][GT_LDS];
+    const TileLanes t = tile_lanes();
+    const int m0 = blockIdx.y * GT_TILE, n0 = blockIdx.x * GT_TILE;
+    constexpr auto walk_a = AK ? walk_k : walk_rows, walk_b = BK ? walk_k : walk_rows;
+    f32x16 acc = zero16();
     for (int s = 0; s < g.nseg; ++s) {
         const GemmSeg sg = g.seg[s];
         int kbeg = 0, kend = sg.K;
@@ -145,59 +138,37 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
         auto fetch = [&](int k0) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const int e = tid + 256 * j;
-                const int ma = AK ? e >> 4 : e & 63, ka = AK ? e & 15 : e >> 6;
-                const int nb = BK ? e >> 4 : e & 63, kb = BK ? e & 15 : e >> 6;
-                ra[j] = (m0 + ma < g.M && k0 + ka < kend) ? sg.A[(long long)(m0 + ma) * sg.a_rs + (long long)(k0 + ka) * sg.a_cs] : 0.0f;
-                rb[j] = (n0 + nb < g.N && k0 + kb < kend) ? sg.B[(long long)(k0 + kb) * sg.b_rs + (long long)(n0 + nb) * sg.b_cs] : 0.0f;
+                const TileCell ca = walk_a(t.tid, j), cb = walk_b(t.tid, j);
+                const int m = m0 + ca.row, ka = k0 + ca.k, n = n0 + cb.row, kb = k0 + cb.k;
+                ra[j] = (m < g.M && ka < kend) ? sg.A[(long long)m * sg.a_rs + (long long)ka * sg.a_cs] : 0.0f;
+                rb[j] = (n < g.N && kb < kend) ? sg.B[(long long)kb * sg.b_rs + (long long)n * sg.b_cs] : 0.0f;
             }
         };
-        if (kbeg < kend) fetch(kbeg);
-        for (int k0 = kbeg; k0 < kend; k0 += GR_KT) {
-            __syncthreads();   // the previous step's fragments have been read
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int e = tid + 256 * j;
-                As[AK ? e & 15 : e >> 6][AK ? e >> 4 : e & 63] = ra[j];
-                Bs[BK ? e & 15 : e >> 6][BK ? e >> 4 : e & 63] = rb[j];
-            }
-            __syncthreads();
-            if (k0 + GR_KT < kend) fetch(k0 + GR_KT);   // in flight while the matrix pipe works on this step
-#pragma unroll
-            for (int kk = 0; kk < GR_KT; kk += 2)
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[kk + kh][wm * 32 + li], Bs[kk + kh][wn * 32 + li], acc, 0, 0, 0);
-        }
+        acc = tile_product<AK, BK>(As, Bs, acc, t, kbeg, kend, ra, rb, fetch);
     }
-    // acc[4 q + r] = row 8 q + 4 kh + r, column li of the wave's 32 x 32 tile
     float *C = g.C;
     if (EPI == EPI_PART) C += (long long)blockIdx.z * g.c_slab;
-    const int col = n0 + wn * 32 + li;
+    const int col = n0 + t.wn * 32 + t.li;
     if (col >= g.N) return;
     const float bias = EPI == EPI_FWD ? g.aux[col] : 0.0f;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = m0 + wm * 32 + 8 * q + 4 * kh + r;
-            if (row >= g.M) continue;
-            float v = acc[4 * q + r];
-            if (EPI == EPI_FWD) {
-                v += bias;
-                if (g.leaky) v = v > 0.0f ? v : 0.01f * v;
-            } else if (EPI == EPI_DIN) {
-                // H = LeakyReLU(Z) has Z's sign; at exactly 0 the derivative is the negative side's slope, as torch
-                v = g.aux[(long long)row * g.ld_aux + col] > 0.0f ? v : 0.01f * v;
-            } else if (EPI == EPI_ACC) {
-                if (g.add) v += C[(long long)row * g.ldc + col];
-            }
-            C[(long long)row * g.ldc + col] = v;
+    for_each_acc(acc, t, m0 + t.wm * 32, [&](int row, float v) {
+        if (row >= g.M) return;
+        if (EPI == EPI_FWD) {
+            v += bias;
+            if (g.leaky) v = v > 0.0f ? v : 0.01f * v;
+        } else if (EPI == EPI_DIN) {
+            v = dleaky(v, g.aux[(long long)row * g.ld_aux + col], 0.01f);
+        } else if (EPI == EPI_ACC) {
+            if (g.add) v += C[(long long)row * g.ldc + col];
         }
+        C[(long long)row * g.ldc + col] = v;
+    });
 }
 
 template <bool AK, bool BK, int EPI>
 static int launch_gemm(hipStream_t st, const GemmArgs &g, int slabs) {
     if (g.M <= 0 || g.N <= 0) return 0;
-    hipLaunchKernelGGL((gemm_kernel<AK, BK, EPI>), dim3(ceil_div(g.N, GR_TILE), ceil_div(g.M, GR_TILE), slabs), dim3(256), 0, st, g);
+    hipLaunchKernelGGL((gemm_kernel<AK, BK, EPI>), dim3(ceil_div(g.N, GT_TILE), ceil_div(g.M, GT_TILE), slabs), dim3(256), 0, st, g);
     SURS_LAUNCH_CHECK();
     return 0;
 }
@@ -207,9 +178,7 @@ __global__ __launch_bounds__(256) void add_slabs_kernel(const float *__restrict_
                                                         float *__restrict__ out) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= count) return;
-    float s = part[i];
-    for (int z = 1; z < slabs; ++z) s += part[z * slab + i];
-    out[i] += s;
+    out[i] += sum_slabs(part, slab, slabs, i);
 }
 
 // db[o] += sum over the chunk's points of dZ[p][o]: 64 columns per workgroup, 4 row groups (row = group, group + 4, ...) summed in order
@@ -426,7 +395,7 @@ static void net_of(const SursMlpShape &s, Net &n) {
 
 // parts of the point reduction of a [m][k] weight gradient: enough workgroups to fill the chip, a function of the shape only
 static int splits_of(int m, int k) {
-    const int tiles = ceil_div(m, GR_TILE) * ceil_div(k, GR_TILE);
+    const int tiles = ceil_div(m, GT_TILE) * ceil_div(k, GT_TILE);
     int s = 1;
     while (s < GR_MAX_SPLITS && tiles * s < 768) s *= 2;
     return s;

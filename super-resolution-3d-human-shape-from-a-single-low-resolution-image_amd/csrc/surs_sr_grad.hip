@@ -7,13 +7,8 @@
 // no activation derivative is a pass of its own.
 //
 // Arithmetic: v_mfma_f32_32x32x2_f32 on fp32 operands with fp32 accumulation, whatever --precision says (gradient operands reach
-// 1e-12, where an f16 operand split flushes to zero).  Both products are implicit GEMMs on the tile of surs_mlp_grad.hip's kernel:
-// 64 x 64 outputs per workgroup of four waves (32 x 32 each), k step 16 through LDS, k-major rows of 68 words.  Conflicts count per
-// 32-lane half over 64 banks: a half's fragment read is 32 consecutive words of one row; a staging write along the row is 64
-// consecutive words; the k-contiguous staging write of the input gradient (16 rows x 2 columns per half) lands on banks 4 k + column,
-// all different because of the 68-word pitch.  The next step's operands are in flight in registers while the matrix pipe works on
-// this one.  Edges are zero-filled: no size has to be a multiple
-// of anything.
+// 1e-12, where an f16 operand split flushes to zero).  Both products are implicit GEMMs on the tile of surs_grad_tile.h, which
+// describes its LDS layout, bank conflicts, pipeline and edge rule; the input gradient stages A k-contiguously (walk_k).
 //   weight gradient   rows: co;  columns: n = tap * cin + ci, plus ONE column (n = k k cin) whose B operand is 1: the bias gradient is
 //                     a column of the same product, in the same order.  Reduction: the output pixels, in parts of SG_PART = 1024
 //                     pixels in row-major order (parts = ceil(ho wo / 1024): a function of the map size alone).  Part z writes its
@@ -27,13 +22,11 @@
 #include <hip/hip_runtime.h>
 
 #include "surs_common.h"
+#include "surs_grad_tile.h"
 
 namespace surs {
 namespace srgrad {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int SG_TILE = 64, SG_KT = 16, SG_LDS = 68;
 constexpr int SG_PART = 1024;   // output pixels per part of the weight gradient's reduction (include/surs.h)
 
 struct WArgs {
@@ -44,38 +37,29 @@ struct WArgs {
     int N;                    // ks ks cin + 1
 };
 
-__device__ __forceinline__ f32x16 zero16() {
-    f32x16 a;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) a[r] = 0.0f;
-    return a;
-}
-
 // grid: (column tiles, row tiles, parts)
 __global__ __launch_bounds__(256) void wgrad_kernel(WArgs a) {
-    __shared__ float As[SG_KT][SG_LDS], Bs[SG_KT][SG_LDS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1, kh = lane >> 5, li = lane & 31;
-    const int m0 = blockIdx.y * SG_TILE, n0 = blockIdx.x * SG_TILE;
+    __shared__ float As[GT_KT][GT_LDS], Bs[GT_KT][GT_LDS];
+    const TileLanes t = tile_lanes();
+    const int m0 = blockIdx.y * GT_TILE, n0 = blockIdx.x * GT_TILE;
     const int P = a.ho * a.wo;
     const int kbeg = (int)blockIdx.z * SG_PART, kend = min(P, kbeg + SG_PART);
-    // this thread stages row / column (tid & 63) of both operands at k = (tid >> 6) + 4 j
-    const int co = m0 + (tid & 63), n = n0 + (tid & 63), kq = tid >> 6;
+    // both operands are staged along the row (walk_rows): this thread's row / column is the same for every j
+    const int co = m0 + walk_rows(t.tid, 0).row, n = n0 + walk_rows(t.tid, 0).row;
     const bool co_ok = co < a.cout;
     const int nw = a.ks * a.ks * a.cin;
     const int tap = n < nw ? n / a.cin : 0, ci = n < nw ? n - tap * a.cin : 0;
     const int ky = tap / a.ks - a.pad, kx = tap % a.ks - a.pad;
-    f32x16 acc = zero16();
     float ra[4], rb[4];
     auto fetch = [&](int k0) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const int p = k0 + kq + 4 * j;
+            const int p = k0 + walk_rows(t.tid, j).k;
             float va = 0.0f, vb = 0.0f;
             if (p < kend) {
                 if (co_ok) {
                     va = a.g[(long long)p * a.g_ld + co];
-                    if (a.y) va = a.y[(long long)p * a.y_ld + co] > 0.0f ? va : a.slope * va;
+                    if (a.y) va = dleaky(va, a.y[(long long)p * a.y_ld + co], a.slope);
                 }
                 if (n < nw) {
                     const int oy = p / a.wo, ox = p - oy * a.wo;
@@ -89,31 +73,13 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WArgs a) {
             rb[j] = vb;
         }
     };
-    if (kbeg < kend) fetch(kbeg);
-    for (int k0 = kbeg; k0 < kend; k0 += SG_KT) {
-        __syncthreads();   // the previous step's fragments have been read
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            As[kq + 4 * j][tid & 63] = ra[j];
-            Bs[kq + 4 * j][tid & 63] = rb[j];
-        }
-        __syncthreads();
-        if (k0 + SG_KT < kend) fetch(k0 + SG_KT);
-#pragma unroll
-        for (int kk = 0; kk < SG_KT; kk += 2)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[kk + kh][wm * 32 + li], Bs[kk + kh][wn * 32 + li], acc, 0, 0, 0);
-    }
-    // acc[4 q + r] = row 8 q + 4 kh + r, column li of the wave's 32 x 32 tile
-    const int col = n0 + wn * 32 + li;
+    const f32x16 acc = tile_product<false, false>(As, Bs, zero16(), t, kbeg, kend, ra, rb, fetch);
+    const int col = n0 + t.wn * 32 + t.li;
     if (col >= a.N) return;
     float *C = a.part + (long long)blockIdx.z * a.cout * a.N;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = m0 + wm * 32 + 8 * q + 4 * kh + r;
-            if (row < a.cout) C[(long long)row * a.N + col] = acc[4 * q + r];
-        }
+    for_each_acc(acc, t, m0 + t.wm * 32, [&](int row, float v) {
+        if (row < a.cout) C[(long long)row * a.N + col] = v;
+    });
 }
 
 // second stage: slab 0 + slab 1 + ... in this order, into the plain layout [cout][cin][ks][ks] and db [cout]
@@ -121,8 +87,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float *__restri
                                                            float *__restrict__ dw, float *__restrict__ db, int accumulate) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x, count = (long long)cout * N;
     if (i >= count) return;
-    float s = part[i];
-    for (int z = 1; z < parts; ++z) s += part[(long long)z * count + i];
+    const float s = sum_slabs(part, count, parts, i);
     const int m = (int)(i / N), n = (int)(i - (long long)m * N);
     float *dst;
     if (n == kk * cin) {
@@ -145,24 +110,22 @@ struct DArgs {
 
 // grid: (row tiles over the input pixels, column tiles over cin)
 __global__ __launch_bounds__(256) void dgrad_kernel(DArgs a) {
-    __shared__ float As[SG_KT][SG_LDS], Bs[SG_KT][SG_LDS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1, kh = lane >> 5, li = lane & 31;
-    const int m0 = blockIdx.x * SG_TILE, n0 = blockIdx.y * SG_TILE;
+    __shared__ float As[GT_KT][GT_LDS], Bs[GT_KT][GT_LDS];
+    const TileLanes t = tile_lanes();
+    const int m0 = blockIdx.x * GT_TILE, n0 = blockIdx.y * GT_TILE;
     const int M = a.h * a.w, K = a.ks * a.ks * a.cout, kk2 = a.ks * a.ks;
-    // A: k is the contiguous index (co): this thread stages k = tid & 15 of rows (tid >> 4) + 16 j
-    const int ka = tid & 15;
+    // A: k is the contiguous index (co), walk_k: this thread's k is the same for every j, its rows are 16 apart
+    const int ka = walk_k(t.tid, 0).k;
     int qy[4], qx[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const int m = m0 + (tid >> 4) + 16 * j;
+        const int m = m0 + walk_k(t.tid, j).row;
         qy[j] = m < M ? m / a.w : -(1 << 20);   // (a row past the map matches no output pixel)
         qx[j] = m < M ? m - qy[j] * a.w : 0;
     }
-    // B: column tid & 63 (ci) at k = (tid >> 6) + 4 j
-    const int ci = n0 + (tid & 63), kq = tid >> 6;
+    // B: walk_rows: this thread's column (ci) is the same for every j
+    const int ci = n0 + walk_rows(t.tid, 0).row;
     const bool ci_ok = ci < a.cin;
-    f32x16 acc = zero16();
     float ra[4], rb[4];
     auto fetch = [&](int k0) {
         const int k = k0 + ka;
@@ -177,11 +140,11 @@ __global__ __launch_bounds__(256) void dgrad_kernel(DArgs a) {
                 if (oy < a.ho && ox < a.wo) {
                     const long long p = (long long)oy * a.wo + ox;
                     va = a.g[p * a.g_ld + co];
-                    if (a.y) va = a.y[p * a.y_ld + co] > 0.0f ? va : a.slope * va;
+                    if (a.y) va = dleaky(va, a.y[p * a.y_ld + co], a.slope);
                 }
             }
             ra[j] = va;
-            const int kb = k0 + kq + 4 * j;
+            const int kb = k0 + walk_rows(t.tid, j).k;
             float vb = 0.0f;
             if (kb < K && ci_ok) {
                 const int tb = kb / a.cout, cb = kb - tb * a.cout;
@@ -190,31 +153,14 @@ __global__ __launch_bounds__(256) void dgrad_kernel(DArgs a) {
             rb[j] = vb;
         }
     };
-    fetch(0);
-    for (int k0 = 0; k0 < K; k0 += SG_KT) {
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            As[ka][(tid >> 4) + 16 * j] = ra[j];
-            Bs[kq + 4 * j][tid & 63] = rb[j];
-        }
-        __syncthreads();
-        if (k0 + SG_KT < K) fetch(k0 + SG_KT);
-#pragma unroll
-        for (int kk = 0; kk < SG_KT; kk += 2)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[kk + kh][wm * 32 + li], Bs[kk + kh][wn * 32 + li], acc, 0, 0, 0);
-    }
-    const int col = n0 + wn * 32 + li;
+    const f32x16 acc = tile_product<true, false>(As, Bs, zero16(), t, 0, K, ra, rb, fetch);
+    const int col = n0 + t.wn * 32 + t.li;
     if (col >= a.cin) return;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = m0 + wm * 32 + 8 * q + 4 * kh + r;
-            if (row >= M) continue;
-            float *d = a.dx + (long long)row * a.dx_ld + col;
-            *d = a.add ? *d + acc[4 * q + r] : acc[4 * q + r];
-        }
+    for_each_acc(acc, t, m0 + t.wm * 32, [&](int row, float v) {
+        if (row >= M) return;
+        float *d = a.dx + (long long)row * a.dx_ld + col;
+        *d = a.add ? *d + v : v;
+    });
 }
 
 // dz[y][x][4 c + 2 dy + dx] = g[2 y + dy][2 x + dx][c] * (o[2 y + dy][2 x + dx][c] > 0 ? 1 : slope); one thread per element of dz
@@ -228,8 +174,7 @@ __global__ __launch_bounds__(256) void unshuffle2_grad_kernel(const float *__res
     const int x = (int)(pix % w), y = (int)(pix / w);
     const int ch = k >> 2, dy = (k >> 1) & 1, dx = k & 1;
     const long long op = (long long)(2 * y + dy) * (2 * w) + 2 * x + dx;
-    const float v = g[op * g_ld + ch];
-    dz[pix * dz_ld + k] = o[op * o_ld + ch] > 0.0f ? v : slope * v;
+    dz[pix * dz_ld + k] = dleaky(g[op * g_ld + ch], o[op * o_ld + ch], slope);
 }
 
 static int check_conv(int ho, int wo, int h, int w, int cin, int cout, int ks, int stride) {
@@ -267,8 +212,8 @@ extern "C" int surs_conv_grad_weight(const float *g, int ho, int wo, int cout, i
     SURS_REQUIRE(need - 256 + (size_t)(base - (char *)workspace) <= workspace_bytes, "convolution weight gradient: workspace too small: %zu bytes needed", need);
     const int parts = ceil_div((long long)ho * wo, SG_PART), kk = ksize * ksize, N = kk * cin + 1;
     WArgs a{g, y, x, ho, wo, cout, g_ld, y_ld, h, w, cin, x_ld, ksize, stride, ksize / 2, slope, (float *)base, N};
-    SURS_REQUIRE(parts <= 65535 && ceil_div(cout, SG_TILE) <= 65535, "convolution weight gradient: shape too large");
-    hipLaunchKernelGGL(wgrad_kernel, dim3(ceil_div(N, SG_TILE), ceil_div(cout, SG_TILE), parts), dim3(256), 0, as_stream(stream), a);
+    SURS_REQUIRE(parts <= 65535 && ceil_div(cout, GT_TILE) <= 65535, "convolution weight gradient: shape too large");
+    hipLaunchKernelGGL(wgrad_kernel, dim3(ceil_div(N, GT_TILE), ceil_div(cout, GT_TILE), parts), dim3(256), 0, as_stream(stream), a);
     SURS_LAUNCH_CHECK();
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(ceil_div((long long)cout * N, 256)), dim3(256), 0, as_stream(stream), (const float *)base,
                        parts, cout, cin, kk, N, dw, db, accumulate ? 1 : 0);
@@ -283,8 +228,8 @@ extern "C" int surs_conv_grad_input(const float *g, int ho, int wo, int cout, in
     if (int rc = check_conv(ho, wo, h, w, cin, cout, ksize, stride)) return rc;
     SURS_REQUIRE(g_ld >= cout && dx_ld >= cin && (!y || y_ld >= cout), "convolution input gradient: a pitch below the channel count");
     DArgs a{g, y, weight, ho, wo, cout, g_ld, y_ld, h, w, cin, ksize, stride, ksize / 2, slope, dx, dx_ld, add ? 1 : 0};
-    SURS_REQUIRE(ceil_div(cin, SG_TILE) <= 65535, "convolution input gradient: shape too large");
-    hipLaunchKernelGGL(dgrad_kernel, dim3(ceil_div((long long)h * w, SG_TILE), ceil_div(cin, SG_TILE)), dim3(256), 0, as_stream(stream), a);
+    SURS_REQUIRE(ceil_div(cin, GT_TILE) <= 65535, "convolution input gradient: shape too large");
+    hipLaunchKernelGGL(dgrad_kernel, dim3(ceil_div((long long)h * w, GT_TILE), ceil_div(cin, GT_TILE)), dim3(256), 0, as_stream(stream), a);
     SURS_LAUNCH_CHECK();
     return 0;
 }

@@ -25,11 +25,11 @@
 #include <hip/hip_runtime.h>
 
 #include "surs_common.h"
+#include "surs_grad_tile.h"   // f32x16, zero16, the accumulator layout (for_each_acc)
 
 namespace surs {
 namespace tailgrad {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TJ_C = 256;            // channels of a, next, previous
@@ -43,13 +43,6 @@ struct JArgs {
     float *d_out, *d_a;
     int do_ld, da_ld;
 };
-
-__device__ __forceinline__ f32x16 zero16() {
-    f32x16 a;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) a[r] = 0.0f;
-    return a;
-}
 
 // acc[b] += A[32 b + row][0 .. K) W[0 .. K)[n0 + column], k ascending.  A: LDS, pitch lda, columns up to the next multiple of 16 of K
 // readable, and finite in the rows that count; W: [K][N] in memory, pitch ldw; rows k >= K and columns >= N count as zero.  The loads
@@ -94,7 +87,8 @@ template <int RB>
 __global__ __launch_bounds__(TJ_THREADS) void tail_joint_kernel(JArgs a) {
     extern __shared__ __attribute__((aligned(16))) float tj_smem[];
     constexpr int ROWS = 32 * RB;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kh = lane >> 5, li = lane & 31;
+    const TileLanes t = tile_lanes();
+    const int tid = t.tid, wave = tid >> 6, kh = t.kh, li = t.li;
     const int D = a.D, D16 = (D + 15) / 16 * 16, ldo = D16 + 1;
     float *Gs = tj_smem, *Os = tj_smem + ROWS * TJ_LDG;
     const long long m0 = (long long)blockIdx.x * ROWS;
@@ -142,7 +136,7 @@ __global__ __launch_bounds__(TJ_THREADS) void tail_joint_kernel(JArgs a) {
                 for (int q = 0; q < 4; ++q)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const int row = 32 * b + 8 * q + 4 * kh + r;   // acc[4 q + r]: row 8 q + 4 kh + r, column li
+                        const int row = 32 * b + 8 * q + 4 * kh + r;   // for_each_acc written out: as a lambda, 159 VGPRs at RB = 2, not 141
                         float v = acc[b][4 * q + r];
                         if (has_out) {
                             const float g = Os[row * ldo + col];
@@ -166,13 +160,9 @@ __global__ __launch_bounds__(TJ_THREADS) void tail_joint_kernel(JArgs a) {
         float *da = a.d_a + m0 * a.da_ld;
 #pragma unroll
         for (int b = 0; b < RB; ++b)
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = 32 * b + 8 * q + 4 * kh + r;
-                    if (row < valid) da[row * a.da_ld + col] = acc[b][4 * q + r];
-                }
+            for_each_acc(acc[b], t, 32 * b, [&](int row, float v) {
+                if (row < valid) da[row * a.da_ld + col] = v;
+            });
     }
 }
 
