@@ -1120,6 +1120,50 @@ int surs_optim_step(const SursOptimItem *items, int n_items, const SursOptimHype
  * refuses.  What the kernel is held against bit for bit, and torch.optim without a device; not a path of the product. */
 int surs_optim_step_host(const SursOptimItem *items, int n_items, const SursOptimHyper *h);
 
+/* ---------------------------------------------------------------- training step
+ * What one iteration of the reference's training loop (apps/train_SuRS.py:122-148) needs besides the taped forwards, their backwards
+ * and the optimiser step: the loss with the gradient of its image term, and a guard against non-finite gradients
+ * (csrc/surs_train_step.hip).
+ *
+ * surs_forward_losses_grad: surs_forward_losses on images in the layouts a training step has them in - img_sr [batch][height][width]
+ * [channels], the model's own NHWC memory; img_hr [batch][channels][height][width], as the dataset hands it - with k = batch channels
+ * height width.  terms and total are bit for bit what surs_forward_losses gives on the same values flattened in NCHW order: the same
+ * partition over the NCHW index, the same float64 partial sums and second stage; only the address of img_sr differs.  d_img_sr
+ * (nullable; [batch][height][width][channels], needs weights and both images, not img_sr itself): the gradient of weights[2] terms[2],
+ * ((float)weights[2] * (1.0f / (float)k)) sign(img_sr - img_hr) - the fp32 reciprocal of k and one fp32 product, which is how torch
+ * divides a device tensor by a host scalar, so these are the bits of weights[2] * l1_loss(img_sr, img_hr).backward(); the difference in
+ * fp32, 0 at equality; a NaN difference gives NaN (torch.sign gives 0 there).  No atomics, no synchronisation. */
+size_t surs_forward_losses_grad_workspace_bytes(void);
+int surs_forward_losses_grad(const float *pred_lr, const float *pred_hr, int num_stacks, long long m, const float *lab_lr,
+                             const float *lab_hr, const float *img_sr, const float *img_hr, int batch, int channels, int height,
+                             int width, const float *weights, void *workspace, size_t workspace_bytes, float *terms, float *total,
+                             float *d_img_sr, void *stream);
+/* d_img_sr alone, looped on the HOST from the same per-element rule (every pointer a host pointer) */
+int surs_forward_losses_grad_host(const float *img_sr, const float *img_hr, int batch, int channels, int height, int width, float w_sr,
+                                  float *d_img_sr);
+
+/* One tensor of a surs_tensors_nonfinite table: a device pointer (a host pointer for the host twin). */
+typedef struct SursTensorRef {
+    const float *p;
+    long long n;         /* elements; 0 is legal and costs nothing */
+    int chunk_end;       /* the inclusive prefix sum of surs_optim_chunks(n) over the table, as in SursOptimItem */
+    int reserved;
+} SursTensorRef;
+
+/* Checks a HOST copy of a table (n < 0, a null pointer with n > 0, a chunk_end that is no prefix sum: SURS_E_INVALID) and returns
+ * its chunk count through *total_chunks (nullable). */
+int surs_tensors_nonfinite_check(const SursTensorRef *items, int n_items, long long *total_chunks);
+size_t surs_tensors_nonfinite_workspace_bytes(long long total_chunks);
+/* *result (device) = the lowest index of the DEVICE table `items` whose tensor holds a NaN or an infinity, or -1.  Two launches on
+ * `stream`: 256-thread workgroups striding over the 4096-element chunks of all items (the chunking of surs_optim_step; 16-byte loads
+ * where the chunk is 16-byte aligned) leave one int per chunk in the workspace, one workgroup takes their minimum in chunk order.
+ * total_chunks: what surs_tensors_nonfinite_check returned for the table - the kernel visits no chunk beyond it.  No atomics, no
+ * synchronisation; the caller reads the 4 bytes of *result when it needs the answer. */
+int surs_tensors_nonfinite(const SursTensorRef *items, int n_items, long long total_chunks, void *workspace, size_t workspace_bytes,
+                           int *result, void *stream);
+/* The same predicate looped on the HOST (items a HOST table of HOST pointers, *result a host int), after the table's check. */
+int surs_tensors_nonfinite_host(const SursTensorRef *items, int n_items, int *result);
+
 /* ---------------------------------------------------------------- training images
  * The image half of a training item (lib/data/TrainDataset_LR_v2.py:258-342) from the decoded uint8 pixels of one view: pad, flip,
  * --random_scale resize, crop, torchvision's ColorJitter, --aug_blur, the BICUBIC / NEAREST half-size pair and the float32 step of

@@ -141,6 +141,11 @@ class OptimItem(C.Structure):
                 ("chunk_end", C.c_int), ("reserved", C.c_int)]
 
 
+class TensorRef(C.Structure):
+    """SursTensorRef of include/surs.h: one tensor of a surs_tensors_nonfinite table (chunk_end as in SursOptimItem)."""
+    _fields_ = [("p", C.c_void_p), ("n", C.c_longlong), ("chunk_end", C.c_int), ("reserved", C.c_int)]
+
+
 class OptimHyper(C.Structure):
     """SursOptimHyper of include/surs.h: one step's hyper-parameters, kernel arguments."""
     _fields_ = [("kind", C.c_int), ("first_step", C.c_int)] + [(k, C.c_float) for k in (
@@ -341,6 +346,14 @@ _SIGS = {
     "surs_optim_check": (C.c_int, [_vp, _i, C.POINTER(OptimHyper)]),
     "surs_optim_step": (C.c_int, [_vp, _i, C.POINTER(OptimHyper), _vp]),
     "surs_optim_step_host": (C.c_int, [_vp, _i, C.POINTER(OptimHyper)]),
+    "surs_forward_losses_grad_workspace_bytes": (_sz, []),
+    "surs_forward_losses_grad": (C.c_int, [_vp, _vp, _i, C.c_longlong, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp,
+                                           _vp]),
+    "surs_forward_losses_grad_host": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _f, _vp]),
+    "surs_tensors_nonfinite_check": (C.c_int, [_vp, _i, C.POINTER(C.c_longlong)]),
+    "surs_tensors_nonfinite_workspace_bytes": (_sz, [C.c_longlong]),
+    "surs_tensors_nonfinite": (C.c_int, [_vp, _i, C.c_longlong, _vp, _sz, _vp, _vp]),
+    "surs_tensors_nonfinite_host": (C.c_int, [_vp, _i, C.POINTER(C.c_int)]),
     "surs_image_resample_plan": (C.c_int, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _rsp, _vp, _sz, _sz, C.POINTER(_sz)]),
     "surs_train_image_plan": (C.c_int, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_double), _i,
                                         C.c_double, _tip, _vp, _sz]),

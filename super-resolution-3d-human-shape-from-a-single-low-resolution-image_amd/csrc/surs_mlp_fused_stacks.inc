@@ -165,26 +165,12 @@ extern "C" int surs_query_points_stacks(const float *points, int n, const float 
 //   1  get_error_hr      the same of pred_hr, lab_hr
 //   2  get_errorSR       L1 mean of img_sr - img_hr                           = sum_j |img_sr[j] - img_hr[j]| / K
 //   3  get_error_disp_1  MSE(lab_hr - lab_lr, pred_hr[S-1] - pred_lr[S-1])
-// Stage 1: LOSS_BLOCKS workgroups of LOSS_THREADS threads; thread t of workgroup b takes elements (b LOSS_THREADS + t) + k LOSS_BLOCKS
-// LOSS_THREADS in ascending k - a partition that depends on the sizes only -, float64 sums, then the workgroup's tree over LDS.
-// Stage 2: one workgroup adds the LOSS_BLOCKS partial sums of each term in the same tree.  No atomics: two runs give the same bits.
+// The partition, the float64 tree and the second stage are surs_loss_reduce.h's (shared with surs_forward_losses_grad): a fixed
+// partition, no atomics, two runs give the same bits.
 // ------------------------------------------------------------------------------------------------
+#include "surs_loss_reduce.h"
+
 namespace surs {
-
-constexpr int LOSS_BLOCKS = 256, LOSS_THREADS = 256;
-
-__device__ __forceinline__ void loss_tree(double (&v)[4], double (*sh)[LOSS_THREADS], int tid) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) sh[t][tid] = v[t];
-    __syncthreads();
-    for (int d = LOSS_THREADS / 2; d > 0; d >>= 1) {
-        if (tid < d) {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) sh[t][tid] += sh[t][tid + d];
-        }
-        __syncthreads();
-    }
-}
 
 __global__ __launch_bounds__(LOSS_THREADS) void loss_partial_kernel(const float *__restrict__ pred_lr, const float *__restrict__ pred_hr,
                                                                     int stacks, long long m, const float *__restrict__ lab_lr,
@@ -195,25 +181,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_partial_kernel(const float 
     const int tid = threadIdx.x;
     const long long first = (long long)blockIdx.x * LOSS_THREADS + tid, step = (long long)LOSS_BLOCKS * LOSS_THREADS;
     double v[4] = {0.0, 0.0, 0.0, 0.0};
-    const bool want_lr = pred_lr && lab_lr, want_hr = pred_hr && lab_hr, want_disp = want_lr && want_hr;
-    for (long long i = first; i < m; i += step) {
-        const double ll = want_lr ? (double)lab_lr[i] : 0.0, lh = want_hr ? (double)lab_hr[i] : 0.0;
-        for (int s = 0; s < stacks; ++s) {
-            if (want_lr) {
-                const double d = (double)pred_lr[(size_t)s * m + i] - ll;
-                v[0] += d * d;
-            }
-            if (want_hr) {
-                const double d = (double)pred_hr[(size_t)s * m + i] - lh;
-                v[1] += d * d;
-            }
-        }
-        if (want_disp) {
-            const size_t o = (size_t)(stacks - 1) * m + i;
-            const double d = (lh - ll) - ((double)pred_hr[o] - (double)pred_lr[o]);
-            v[3] += d * d;
-        }
-    }
+    loss_points(v, pred_lr, pred_hr, stacks, m, lab_lr, lab_hr, first, step);
     if (img_sr && img_hr)
         for (long long j = first; j < k; j += step) v[2] += fabs((double)img_sr[j] - (double)img_hr[j]);
     loss_tree(v, sh, tid);
@@ -223,24 +191,8 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_partial_kernel(const float 
 __global__ __launch_bounds__(LOSS_THREADS) void loss_final_kernel(const double *__restrict__ partial, int stacks, long long m, long long k,
                                                                   float w0, float w1, float w2, float w3, float *__restrict__ terms,
                                                                   float *__restrict__ total) {
-    static_assert(LOSS_BLOCKS == LOSS_THREADS, "one partial sum per thread");
     __shared__ double sh[4][LOSS_THREADS];
-    const int tid = threadIdx.x;
-    double v[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) v[t] = partial[tid * 4 + t];
-    loss_tree(v, sh, tid);
-    if (tid == 0) {
-        const double sm = (double)stacks * (double)m;
-        const float e0 = m > 0 ? (float)(sh[0][0] / sm) : 0.0f, e1 = m > 0 ? (float)(sh[1][0] / sm) : 0.0f;
-        const float e2 = k > 0 ? (float)(sh[2][0] / (double)k) : 0.0f, e3 = m > 0 ? (float)(sh[3][0] / (double)m) : 0.0f;
-        terms[0] = e0;
-        terms[1] = e1;
-        terms[2] = e2;
-        terms[3] = e3;
-        // SuRSNet.py:265 in float32, left to right
-        if (total) *total = w0 * e0 + w1 * e1 + w2 * e2 + w3 * e3;
-    }
+    loss_final(partial, stacks, m, k, w0, w1, w2, w3, terms, total, sh);
 }
 
 }  // namespace surs

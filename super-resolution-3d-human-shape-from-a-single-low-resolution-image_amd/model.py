@@ -20,7 +20,7 @@ them.  The hourglass filter (image_filter_lr.*) has a backward too (--norm group
 conv_block_backward(), hourglass_train() / hourglass_backward() (native.hg_backward), stack_tail_train() / stack_tail_backward()
 (native.tail_backward), and as a whole, filter_lr_train() / filter_lr_backward() (native.filter_lr_backward); hg_parameters() are the
 fp32 weights they read, autograd.conv_block, autograd.hourglass, autograd.stack_tail and autograd.filter_lr the Functions over them;
-forward_backward() does not return encoder gradients.
+forward_backward(encoder=True) returns the gradients of all three parameter sets from one taped forward.
 
 Encoder options: --norm group | batch and --scale 1..4 (anything else: ValueError at construction).  --norm batch is nn.BatchNorm2d in
 EVAL mode - y = (x - running_mean) / sqrt(running_var + 1e-5) * weight + bias, always from the running statistics: train() here keeps
@@ -353,15 +353,22 @@ class SuRSNet:
             raise RuntimeError("%s_backward needs a preceding %s_train()%s: the tape of the forward's maps is missing" % (what, what, of))
         return tapes
 
-    def _backward(self, tapes, upstream, need, fn):
+    def _backward(self, tapes, upstream, need, fn, nhwc=False):
         """The per-image backward of one module from `tapes` (one per image).  upstream: per output (its name, its gradient [B,c,h,w] or
         None = zero, its (c, h, w)); need: the workspace's bytes; fn(tape, [image b's NHWC gradient or None per output], grads=,
         accumulate=, workspace=) -> (the input's gradient [h,w,c] or None, grads).  The parameters' gradients are summed by the library in
-        image order: the first image overwrites, the later ones add.  Returns (the input's gradient [B,c,h,w] or None, grads)."""
+        image order: the first image overwrites, the later ones add.  Returns (the input's gradient [B,c,h,w] or None, grads).
+        nhwc=True (forward_backward(encoder=True)'s private route): every gradient is given in the memory the library reads - a
+        contiguous [B,h,w,c] tensor or a list of B [h,w,c] tensors, handed on untouched - and the input's gradient comes back as the
+        list of the B [h,w,c] tensors the library wrote: no copy on either side."""
         dev, B = self._device(), len(tapes)
         gs = []
         for name, g, shape in upstream:
-            if g is not None:
+            if g is not None and nhwc:
+                c, h, w = shape
+                if len(g) != B or any(tuple(t.shape) != (h, w, c) for t in g):
+                    raise ValueError("%s %s against the output's %s in NHWC" % (name, [tuple(t.shape) for t in g][:2], (B, h, w, c)))
+            elif g is not None:
                 if tuple(g.shape) != (B,) + shape:
                     raise ValueError("%s %s against the output's %s" % (name, tuple(g.shape), (B,) + shape))
                 g = g.detach().to(dev, torch.float32).permute(0, 2, 3, 1).contiguous()
@@ -373,14 +380,18 @@ class SuRSNet:
         for b in range(B):
             dx, grads = fn(tapes[b], [None if g is None else g[b] for g in gs], grads=grads, accumulate=b > 0, workspace=self._train_ws)
             dxs.append(dx)
+        if nhwc:
+            return (None if dxs[0] is None else dxs), grads
         return (None if dxs[0] is None else torch.stack(dxs, 0).permute(0, 3, 1, 2)), grads
 
     # ------------------------------------------------------------------ super-resolution gradients
+    _SR_F16 = ("super-resolution gradients: --encoder_precision f16 (net->parts == 1) has no backward: training runs the fp32-grade "
+               "forward")
+
     def _sr_native(self):
         W = self._encoder_weights()
         if W.reduced:
-            raise RuntimeError("super-resolution gradients: --encoder_precision f16 (net->parts == 1) has no backward: training runs "
-                               "the fp32-grade forward")
+            raise RuntimeError(self._SR_F16)
         return encoder._native_net(W).net, W.scale
 
     def _sr_param_set(self):
@@ -423,6 +434,10 @@ class SuRSNet:
         feature_lr through image_filter_lr (the hourglass) is not part of this: whoever owns that network supplies
         grad_feature_lr.  tapes: what an earlier super_res_train() filed in _tapes[SR_TAPES], to go back through THAT forward
         whatever ran since; the model's own entry is neither read nor changed."""
+        return self._super_res_backward(grad_img_SR, grad_feature_lr, grad_feat_hr, tapes)
+
+    def _super_res_backward(self, grad_img_SR, grad_feature_lr, grad_feat_hr, tapes=None, nhwc=False):
+        """super_res_backward; nhwc: _backward's private NHWC route."""
         h, w, tapes = self._kept_tapes(self.SR_TAPES, tapes, "super_res")
         net, scale = self._sr_native()
         params = self._param_set("sr")[0]
@@ -432,7 +447,8 @@ class SuRSNet:
         if all(g is None for _, g, _ in upstream):
             raise ValueError("super_res_backward: no upstream gradient (all three are None)")
         return self._backward(tapes, upstream, native.sr_backward_workspace_bytes(net, h, w),
-                              lambda tape, g, **kw: (None, native.sr_backward(net, params, tape, h, w, *g, scale=scale, **kw)))[1]
+                              lambda tape, g, **kw: (None, native.sr_backward(net, params, tape, h, w, *g, scale=scale, **kw)),
+                              nhwc=nhwc)[1]
 
     # ------------------------------------------------------------------ hourglass gradients
     def _hg_check_norm(self):
@@ -558,6 +574,10 @@ class SuRSNet:
         preceding filter_lr_train(), or from `tapes`: what an earlier one filed in _tapes["filter_lr"].  grad_outs holds one
         [B,hg_dim,h,w] tensor or None (zero) per stack, not all None.  Summed over the batch in image order; the parameters of a stack
         no gradient reaches get zeros."""
+        return self._filter_lr_backward(grad_outs, tapes)
+
+    def _filter_lr_backward(self, grad_outs, tapes=None, nhwc=False):
+        """filter_lr_backward; nhwc: _backward's private NHWC route."""
         self._hg_check_norm()
         S = self.opt.num_stack_lr
         if len(grad_outs) != S:
@@ -569,7 +589,8 @@ class SuRSNet:
         hp = self._param_set("hg")[0]
         return self._backward(tapes, [("grad_outs[%d]" % s, g, (net.l[s].cout, h, w)) for s, g in enumerate(grad_outs)],
                               native.filter_lr_backward_workspace_bytes(net, h, w),
-                              lambda tape, g, **kw: native.filter_lr_backward(net, self.opt.hg_depth, hp.keys, hp.tensors, tape, h, w, g, **kw))
+                              lambda tape, g, **kw: native.filter_lr_backward(net, self.opt.hg_depth, hp.keys, hp.tensors, tape, h, w, g, **kw),
+                              nhwc=nhwc)
 
     def reencode_wide(self):
         """Runs the encoder again on the images of the last super_res() call with every fp32-grade product on three bf16 parts
@@ -1105,17 +1126,37 @@ class SuRSNet:
         return grads
 
     def forward_backward(self, images_lr, images_hr, points_lr, points_hr, calibs, transforms=None, labels_lr=None, labels_hr=None,
-                         features=False):
-        """forward() and the classifiers' gradients of its loss: (res_hr, error, res_lr, grads).  The first three are exactly forward()'s
-        (it is called; error still has no autograd graph), grads is classifier_grads()'s OrderedDict: every mlp_lr.* / mlp_hr.* key in
-        state_dict() order, float32 device tensors of the parameters' shapes.  features=True: (res_hr, error, res_lr, grads,
-        feat_grads) with classifier_grads(features=True)'s feat_grads and feat_grads["img_SR"] = opt.srweight sign(img_SR -
-        images_hr) / numel (torch's L1 backward, 0 at equality) - everything the loss hands back to the encoder.  Out of scope:
-        the parameter gradients of the hourglass (image_filter_lr.*), and this call is NOT extended by those of the super-resolution
-        network (super_res_train() / super_res_backward(), autograd.super_res_features): a gradient that silently lacked the path
-        feature_lr -> filter_lr -> points would be a trap; num_views == 1 and orthogonal projection only."""
+                         features=False, encoder=False):
+        """forward() and the gradients of its loss: (res_hr, error, res_lr, grads).
+
+        encoder=False (the default): the first three are exactly forward()'s (it is called; error still has no autograd graph), grads
+        is classifier_grads()'s OrderedDict: every mlp_lr.* / mlp_hr.* key in state_dict() order, float32 device tensors of the
+        parameters' shapes.  features=True: (res_hr, error, res_lr, grads, feat_grads) with classifier_grads(features=True)'s
+        feat_grads and feat_grads["img_SR"] = opt.srweight sign(img_SR - images_hr) / numel (torch's L1 backward, 0 at equality) -
+        everything the loss hands back to the encoder.
+
+        encoder=True: the FULL gradient, what one iteration of the reference's training loop computes (apps/train_SuRS.py:122-148).
+        grads is one OrderedDict over every key of mlp_parameters(), sr_parameters() and hg_parameters(), in state_dict() order:
+        float32 device tensors of the parameters' shapes, summed over the batch in image order, the same bits on every call - what
+        optim.Optimizer.step() takes.  ONE taped forward, no second one: super_res_train(images_lr) -> filter_lr_train(feature_lr) ->
+        the stacks queries, with the reference's crossing of the label arguments as forward() does them -> the loss with the gradient
+        of its image term (surs_forward_losses_grad) -> classifier_grads(features=True) -> filter_lr_backward(d im_feat_list_lr) ->
+        one super_res_backward(d img_SR, d feature_lr, d im_feat_list_hr[0]).  The gradients between these calls stay in the NHWC
+        memory the library writes and reads: no clone and no layout change of a map.  res_hr, error, res_lr, loss_values, im_SR and
+        im_feat_list_* are forward()'s bit for bit on the same input (the taped forwards run the inference launch lists; the loss keeps
+        surs_forward_losses' partition); in eval mode only the last stack is queried, as forward() does, and the other stacks get zero
+        gradients.  features does not apply (ValueError).  Non-finite FEATURES are not retried on wide operands here - the tapes would
+        no longer be those of the features -: the query raises NonFiniteVolumeError; non-finite GRADIENTS are what
+        Optimizer.step(guard=True) looks for.  Refused, by the checks of the calls above: --norm batch (NotImplementedError: no
+        backward), --encoder_precision f16 (RuntimeError: net->parts == 1 has no backward).
+
+        Either way: num_views == 1 and orthogonal projection only (NotImplementedError)."""
         if self.num_views != 1 or self.projection_mode != "orthogonal":
             raise NotImplementedError(self._GRADS_LIMIT)
+        if encoder:
+            if features:
+                raise ValueError("forward_backward(encoder=True) returns the parameters' gradients; features=True goes with encoder=False")
+            return self._forward_backward_full(images_lr, images_hr, points_lr, points_hr, calibs, transforms, labels_lr, labels_hr)
         res_hr, error, res_lr = self.forward(images_lr, images_hr, points_lr, points_hr, calibs, transforms=transforms,
                                              labels_lr=labels_lr, labels_hr=labels_hr)
         if not features:
@@ -1126,3 +1167,46 @@ class SuRSNet:
         scale = torch.full((), float(self.opt.srweight), dtype=torch.float32, device=img_SR.device) / img_SR.numel()
         feat_grads["img_SR"] = torch.sign(img_SR - images_hr.to(img_SR.device, torch.float32)) * scale
         return res_hr, error, res_lr, grads, feat_grads
+
+    def _check_full_gradient(self):
+        """forward_backward(encoder=True)'s refusals, before anything runs: the checks of the calls it is made of."""
+        self._hg_check_norm()
+        if getattr(self.opt, "encoder_precision", "auto") == "f16":
+            raise RuntimeError(self._SR_F16)
+
+    def _forward_backward_full(self, images_lr, images_hr, points_lr, points_hr, calibs, transforms, labels_lr, labels_hr):
+        self._check_full_gradient()
+        if labels_lr is None or labels_hr is None:
+            raise ValueError("forward needs labels_lr and labels_hr (the loss terms are taken against them)")
+        dev = self._device()
+        img_SR, feature_lr, _ = self.super_res_train(images_lr)
+        outs = self.filter_lr_train(feature_lr)
+        S = len(outs)
+        # (forward()'s filter_lr(keep_all=self.training): every stack in training mode, the last one in eval mode)
+        self.im_feat_list_lr = list(outs) if self.training else outs[-1:]
+        self._lr_from = None      # (reencode_wide must not replace these maps: the tapes are theirs)
+        self._query_mr(points_hr, calibs, transforms, labels_hr, lr_only=True)
+        self.query_sr(points_lr, calibs, transforms=transforms, labels=labels_lr)
+        res_hr, res_lr = self.get_preds()
+        if tuple(img_SR.shape) != tuple(images_hr.shape):
+            raise ValueError("get_errorSR: image_SR %s against images_hr %s" % (tuple(img_SR.shape), tuple(images_hr.shape)))
+        self.images_HR = images_hr
+        w = (self.opt.mlp1, self.opt.mlp2, self.opt.srweight, self.opt.dispweight)
+        def nhwc(t):
+            """The [B,h,w,C] tensor behind an NCHW-shaped map of the library: a view, never a copy - the promise of this route."""
+            t = t.permute(0, 2, 3, 1)
+            assert t.is_contiguous(), "a map of the training step is not NHWC in memory: %s, strides %s" % (tuple(t.shape), t.stride())
+            return t
+        self.loss_values, error, d_img = native.forward_losses_grad(
+            self._stacked(self.intermediate_preds_list_lr), self._labels("lr"), self._stacked(self.intermediate_preds_list_hr),
+            self._labels("hr"), nhwc(img_SR), images_hr.detach().to(dev, torch.float32).contiguous(), w)
+        g_mlp, fg = self.classifier_grads(features=True)
+        g_lr = [None] * (S - len(fg["lr"])) + [nhwc(t) for t in fg["lr"]]
+        d_feature_lr, g_hg = self._filter_lr_backward(g_lr, nhwc=True)
+        g_sr = self._super_res_backward(d_img, d_feature_lr, nhwc(fg["hr"]), nhwc=True)
+        merged = {}
+        for g in (g_mlp, g_sr, g_hg):
+            merged.update(g)
+        grads = OrderedDict((k, merged[k]) for k in self._sd if k in merged)
+        assert len(grads) == len(merged)
+        return res_hr, error, res_lr, grads

@@ -1158,6 +1158,93 @@ def optim_step_host(tensors, hyper):
     check(lib().surs_optim_step_host(C.cast(optim_items(rows), C.c_void_p), len(rows), C.byref(hyper)))
 
 
+# ------------------------------------------------------------------ training step: the loss head and the non-finite guard
+
+def forward_losses_grad(pred_lr, lab_lr, pred_hr, lab_hr, img_sr_nhwc, img_hr, weights, want_grad=True):
+    """surs_forward_losses_grad: forward_losses' (terms, total) - the same bits - from img_sr_nhwc [B,H,W,C], the model's own NHWC
+    memory, and img_hr [B,C,H,W] as the dataset hands it, and d (weights[2] terms[2]) / d img_sr as a new [B,H,W,C] tensor (None with
+    want_grad=False).  Returns (terms, total, d_img_sr).  One launch pair on the current stream, no synchronisation."""
+    dev = img_sr_nhwc.device
+    if pred_lr.dim() != 2 or tuple(pred_lr.shape) != tuple(pred_hr.shape):
+        raise ValueError("predictions must be [S,M] and agree: %s" % ([tuple(pred_lr.shape), tuple(pred_hr.shape)],))
+    S, M = pred_lr.shape
+    pred_lr, pred_hr = _f32c(pred_lr), _f32c(pred_hr)
+    lab_lr, lab_hr = (_f32c(l.to(dev).reshape(-1)) for l in (lab_lr, lab_hr))
+    if lab_lr.numel() != M or lab_hr.numel() != M:
+        raise ValueError("labels must hold one value per point: %d" % M)
+    if img_sr_nhwc.dim() != 4 or img_hr.dim() != 4:
+        raise ValueError("img_sr [B,H,W,C] and img_hr [B,C,H,W] are expected")
+    B, H, W, Cc = img_sr_nhwc.shape
+    if tuple(img_hr.shape) != (B, Cc, H, W):
+        raise ValueError("get_errorSR: image_SR %s against images_hr %s" % ((B, Cc, H, W), tuple(img_hr.shape)))
+    img_sr_nhwc, img_hr = _f32c(img_sr_nhwc), _f32c(img_hr)
+    ws = torch.empty(lib().surs_forward_losses_grad_workspace_bytes() // 8, dtype=torch.float64, device=dev)
+    terms = torch.empty(4, dtype=torch.float32, device=dev)
+    total = torch.empty((), dtype=torch.float32, device=dev)
+    d_img = torch.empty_like(img_sr_nhwc) if want_grad else None
+    wt = (C.c_float * 4)(*[float(v) for v in weights])
+    check(lib().surs_forward_losses_grad(_ptr(pred_lr), _ptr(pred_hr), int(S), int(M), _ptr(lab_lr), _ptr(lab_hr), _ptr(img_sr_nhwc),
+                                         _ptr(img_hr), int(B), int(Cc), int(H), int(W), wt, _ptr(ws), ws.numel() * 8, _ptr(terms),
+                                         _ptr(total), _ptr(d_img), _stream()))
+    return terms, total, d_img
+
+
+def forward_losses_grad_host(img_sr_nhwc, img_hr, w_sr):
+    """surs_forward_losses_grad_host: d_img_sr [B,H,W,C] of contiguous float32 numpy arrays img_sr_nhwc [B,H,W,C], img_hr [B,C,H,W]."""
+    B, H, W, Cc = img_sr_nhwc.shape
+    if img_hr.shape != (B, Cc, H, W) or any(a.dtype != np.float32 or not a.flags.c_contiguous for a in (img_sr_nhwc, img_hr)):
+        raise ValueError("forward_losses_grad_host: contiguous float32 [B,H,W,C] and [B,C,H,W] arrays expected")
+    out = np.empty_like(img_sr_nhwc)
+    check(lib().surs_forward_losses_grad_host(img_sr_nhwc.ctypes.data, img_hr.ctypes.data, B, Cc, H, W, float(w_sr), out.ctypes.data))
+    return out
+
+
+def tensor_refs(rows):
+    """(a host array of SursTensorRef over rows (address, n), chunk_end filled in; its chunk count), checked by the library."""
+    items = (_lib.TensorRef * max(len(rows), 1))()
+    end = 0
+    for it, (p, n) in zip(items, rows):
+        end += lib().surs_optim_chunks(n)
+        it.p, it.n, it.chunk_end = p, n, end
+    total = C.c_longlong(0)
+    check(lib().surs_tensors_nonfinite_check(C.cast(items, C.c_void_p), len(rows), C.byref(total)))
+    return items, total.value
+
+
+def tensors_nonfinite(table, n_items, total_chunks, workspace=None, result=None):
+    """surs_tensors_nonfinite over the DEVICE table `table` (the bytes of tensor_refs' array): a 0-dim int32 device tensor holding the
+    lowest index whose tensor has a NaN or an infinity, or -1.  No synchronisation: reading the result is the caller's."""
+    dev = table.device
+    need = lib().surs_tensors_nonfinite_workspace_bytes(total_chunks)
+    if workspace is None or workspace.numel() * 4 < need:
+        workspace = torch.empty(max(need // 4, 1), dtype=torch.int32, device=dev)
+    if result is None:
+        result = torch.empty((), dtype=torch.int32, device=dev)
+    check(lib().surs_tensors_nonfinite(_ptr(table), n_items, total_chunks, _ptr(workspace), workspace.numel() * 4, _ptr(result), _stream()))
+    return result
+
+
+def tensors_nonfinite_device(tensors):
+    """tensors_nonfinite of a list of contiguous float32 device tensors, table built and uploaded here (tests and tools; the
+    optimiser keeps its table between steps)."""
+    tensors = [_f32c(t) for t in tensors]
+    items, total = tensor_refs([(t.data_ptr(), t.numel()) for t in tensors])
+    dev = tensors[0].device
+    table = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(dev)
+    return tensors_nonfinite(table, len(tensors), total)
+
+
+def tensors_nonfinite_host(arrays):
+    """surs_tensors_nonfinite_host over contiguous float32 numpy arrays: the lowest index with a NaN or an infinity, or -1."""
+    for a in arrays:
+        if a.dtype != np.float32 or not a.flags.c_contiguous:
+            raise ValueError("tensors_nonfinite_host: contiguous float32 arrays expected")
+    items, _ = tensor_refs([(a.ctypes.data, a.size) for a in arrays])
+    res = C.c_int(0)
+    check(lib().surs_tensors_nonfinite_host(C.cast(items, C.c_void_p), len(arrays), C.byref(res)))
+    return res.value
+
+
 def mlp_grad_workspace_bytes(shapes):
     """surs_mlp_grad_workspace_bytes: the device workspace of mlp_grads for this pair - a function of the shapes, not of n."""
     lr, hr = (_shape_struct(*s) for s in shapes)

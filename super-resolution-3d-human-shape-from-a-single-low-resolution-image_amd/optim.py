@@ -5,6 +5,7 @@
     optimizerG.zero_grad()
     res_hr, error, res_lr, grads = netG.forward_backward(...)
     optimizerG.step(grads)                              # one launch over every tensor, then netG.commit()
+    optimizerG.step(grads, guard=True)                  # the same unless a gradient is non-finite: then nothing is touched
 
 Optimizer steps the plain fp32 masters behind mlp_parameters(), sr_parameters() and hg_parameters() - about 330 tensors, 18.4 M values
 at the released options - by ONE launch of surs_optim_step over a device table (native.optim_step; the arithmetic is torch.optim's
@@ -98,6 +99,9 @@ class Optimizer:
         self._seen = set()                 # keys that have been stepped (or loaded): the ones state_dict() lists
         self._sig = self._table = self._n_items = None
         self._keep = None
+        self.skipped = 0                   # steps step(guard=True) refused because a gradient was not finite
+        self.last_skipped_key = None       # the first key (in parameter order) whose gradient was not finite in the last refused step
+        self._guard_sig = self._guard_table = self._guard_ws = self._guard_total = None
 
     # ------------------------------------------------------------------ state
     def _state_names(self, group=None):
@@ -143,13 +147,35 @@ class Optimizer:
             out.append((k, g.detach() if g.is_contiguous() else g.detach().contiguous()))
         return out
 
-    def step(self, grads=None, commit=True):
+    def _nonfinite(self, todo):
+        """The index in `todo` of the first gradient that holds a NaN or an infinity, or -1: native.tensors_nonfinite over a device
+        table of the gradients (rebuilt only when a pointer differs from the previous guarded step's), then the one read of its 4-byte
+        result - a synchronisation with the current stream."""
+        sig = tuple((k, g.data_ptr(), g.numel()) for k, g in todo)
+        if sig != self._guard_sig:
+            items, total = native.tensor_refs([(g.data_ptr(), g.numel()) for _, g in todo])
+            nbytes = C.sizeof(items)
+            host = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+            C.memmove(host.data_ptr(), C.addressof(items), nbytes)
+            self._guard_table = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._guard_table.copy_(host, non_blocking=True)
+            self._guard_ws = torch.empty(max(total, 1), dtype=torch.int32, device=self.device)
+            self._guard_sig, self._guard_total = sig, total
+        return int(native.tensors_nonfinite(self._guard_table, len(todo), self._guard_total, workspace=self._guard_ws).item())
+
+    def step(self, grads=None, commit=True, guard=False):
         """One step of every key that has a gradient, in one launch on the current stream, then net.commit(which) unless commit=False.
         grads: a mapping state-dict key -> device tensor - the OrderedDicts classifier_grads() / forward_backward(),
         super_res_backward() and filter_lr_backward() return, or a merge of them; any shape with the right element count; keys of other
         sets are ignored - or None: the .grad of the Parameters (autograd.point_loss and the other Functions leave them).  A key without
         a gradient is skipped, as torch skips grad is None (see the module docstring for its bias correction).  The device table is
-        rebuilt only when a pointer differs from the previous step's and uploaded from pinned memory without synchronisation."""
+        rebuilt only when a pointer differs from the previous step's and uploaded from pinned memory without synchronisation.
+        guard=True: the gradients about to be applied are first searched for a NaN or an infinity (surs_tensors_nonfinite) and the
+        4-byte answer is read - ONE synchronisation per step, which guard=False does not have.  The fp32-grade forward runs on two f16
+        operand parts: an activation beyond the f16 range gives non-finite features and gradients, and one such step would poison every
+        master.  On a hit nothing is launched: parameters, optimiser state and the step count stay bit for bit as they were, `skipped`
+        counts the step, `last_skipped_key` names the first offending key, and the call returns False; otherwise it returns True after
+        the step guard=False would have taken (the same bits).  Returns None with guard=False, as before."""
         for w in self.which:
             if self.net._masters().get(w) is not self._owners[w]:
                 raise RuntimeError("Optimizer.step: the net's %r masters were replaced (load_state_dict() / to()): make a new Optimizer "
@@ -158,6 +184,12 @@ class Optimizer:
         todo = self._gradients(grads)
         if not todo:
             return None
+        if guard:
+            hit = self._nonfinite(todo)
+            if hit >= 0:
+                self.skipped += 1
+                self.last_skipped_key = todo[hit][0]
+                return False
         names = self._state_names()
         sig = (names,) + tuple((k, g.data_ptr()) for k, g in todo)
         if sig != self._sig:
@@ -179,7 +211,7 @@ class Optimizer:
         self._seen.update(k for k, _ in todo)
         if commit:
             self.net.commit(self.which)
-        return None
+        return True if guard else None
 
     # ------------------------------------------------------------------ torch.optim's state_dict
     def state_dict(self):

@@ -48,18 +48,21 @@ _BOOL_FLAGS = ["no_residual", "residual", "no_gen_mesh", "debug", "random_multiv
                "pin_memory", "no_num_eval", "skip_hourglass", "use_tanh", "random_flip", "random_trans",
                "random_scale", "val_test_error", "val_train_error", "gen_test_mesh", "gen_train_mesh",
                "all_mesh", "with_color", "both_color", "change_weights"]
+# read by the training driver (apps/train_SuRS.py, optim.from_options, train_util.adjust_learning_rate)
+_TRAIN_LOOP = [
+    ("batch_size", int, 2), ("learning_rate", float, 1e-3), ("num_epoch", int, 100), ("freq_plot", int, 10), ("freq_save", int, 50),
+    ("freq_save_ply", int, 100), ("resume_epoch", int, -1), ("continue_train", int, -1), ("gamma", float, 0.1), ("optimizer", str, "ADAM"),
+    ("momentum", float, 0.9), ("beta1", float, 0.9), ("beta2", float, 0.999), ("epsilon", float, 1e-8), ("weight_decay", float, 0),
+    ("num_gen_mesh_test", int, 1), ("checkpoints_path", str, "./checkpoints"),
+]
 # accepted for command-line compatibility, never read by this package
 _IGNORED = [
-    ("gpu_ids", str, "0"), ("num_threads", int, 1), ("batch_size", int, 2), ("learning_rate", float, 1e-3),
-    ("learning_rateC", float, 1e-3), ("num_epoch", int, 100), ("freq_plot", int, 10), ("freq_save", int, 50),
-    ("freq_save_ply", int, 100), ("resume_epoch", int, -1), ("continue_train", int, -1),
+    ("gpu_ids", str, "0"), ("num_threads", int, 1), ("learning_rateC", float, 1e-3),
     ("test_folder_path", str, None), ("norm_color", str, "instance"), ("num_hourglass", int, 2),
     ("hg_down", str, "ave_pool"), ("hourglass_dim", int, 256), ("mlp_norm", str, "group"),
-    ("scale_pifu", float, 0.01), ("gamma", float, 0.1), ("color_loss_type", str, "l1"), ("losses", str, "l1"),
-    ("disp_error", int, 1), ("n_train", int, 300), ("n_val", int, 60), ("optimizer", str, "ADAM"),
-    ("momentum", float, 0.9), ("beta1", float, 0.9), ("beta2", float, 0.999), ("epsilon", float, 1e-8),
-    ("ams", float, False), ("weight_decay", float, 0), ("num_gen_mesh_test", int, 1), ("n_colors", int, 3),
-    ("checkpoints_path", str, "./checkpoints"), ("load_netC_checkpoint_path", str, None),
+    ("scale_pifu", float, 0.01), ("color_loss_type", str, "l1"), ("losses", str, "l1"),
+    ("disp_error", int, 1), ("n_train", int, 300), ("n_val", int, 60),
+    ("ams", float, False), ("n_colors", int, 3), ("load_netC_checkpoint_path", str, None),
     ("load_checkpoint_path", str, None), ("single", str, ""), ("mask_path", str, None), ("img_path", str, None),
     ("aug_alstd", float, 0.0),
 ]
@@ -84,6 +87,7 @@ _NATIVE = [
     ("no_octree", None, False),      # dense sweep (the parity target)
     ("synthetic", None, False),      # synthetic image + PRNG weights instead of dataroot / checkpoint
     ("pipeline", None, False),       # eval driver: subjects as a pipeline (train_util.gen_mesh_pipelined) instead of one by one
+    ("seed", int, 0),                # training driver: the dataset's samples, the loader's shuffle and the augmentations' host generators
 ]
 
 
@@ -94,7 +98,7 @@ class BaseOptions:
         self.initialized = False
 
     def initialize(self, parser):
-        for name, typ, default in _PATH_FLAGS + _IGNORED + _TRAIN_DATA + _LOSS_WEIGHTS:
+        for name, typ, default in _PATH_FLAGS + _TRAIN_LOOP + _IGNORED + _TRAIN_DATA + _LOSS_WEIGHTS:
             parser.add_argument("--" + name, type=typ, default=default)
         for name, typ, default in _LIST_FLAGS:
             parser.add_argument("--" + name, type=typ, nargs="+", default=list(default))

@@ -149,3 +149,22 @@ def adjust_learning_rate(optimizer, epoch, lr, schedule, gamma):
     for group in optimizer.param_groups:
         group["lr"] = lr
     return lr
+
+
+def reshape_multiview_tensors(image_tensor_hr, image_tensor_lr, calib_tensor):
+    """The loader's [B, num_views, ...] tensors flattened to [B num_views, ...], as /root/reference/lib/train_util.py:14-38 does and in
+    its argument order: (image_tensor_hr [B V,C,H,W], image_tensor_lr [B V,C,h,w], calib_tensor [B V,4,4]) - views, no copies."""
+    flat = lambda t: t.view((t.shape[0] * t.shape[1],) + tuple(t.shape[2:]))
+    if image_tensor_hr.dim() != 5 or image_tensor_lr.dim() != 5 or calib_tensor.dim() != 4:
+        raise ValueError("reshape_multiview_tensors: [B,V,C,H,W] images and [B,V,4,4] calibrations are expected, not %s, %s, %s" % (
+            tuple(image_tensor_hr.shape), tuple(image_tensor_lr.shape), tuple(calib_tensor.shape)))
+    return flat(image_tensor_hr), flat(image_tensor_lr), flat(calib_tensor)
+
+
+def reshape_sample_tensor(sample_tensor, num_views):
+    """sample_tensor [B,3,N] repeated once per view, view-minor: [B num_views,3,N] (/root/reference/lib/train_util.py:41-51); the
+    tensor itself for one view."""
+    if num_views == 1:
+        return sample_tensor
+    B, c, n = sample_tensor.shape
+    return sample_tensor.unsqueeze(1).repeat(1, num_views, 1, 1).view(B * num_views, c, n)
