@@ -1120,6 +1120,43 @@ int surs_optim_step(const SursOptimItem *items, int n_items, const SursOptimHype
  * refuses.  What the kernel is held against bit for bit, and torch.optim without a device; not a path of the product. */
 int surs_optim_step_host(const SursOptimItem *items, int n_items, const SursOptimHyper *h);
 
+/* The data-parallel step: R ranks have all-gathered their gradient slabs into one buffer, and the gradient of element i of an item
+ * is read as g[i + r * rank_stride], r = 0 .. num_ranks - 1 (g points into rank 0's row).  The value handed to the unchanged
+ * per-kind update is
+ *     ((g_0 + g_1) + ... + g_{R-1}) * scale
+ * - fp32 sums LEFT TO RIGHT IN RANK ORDER, starting from g_0 (not from zero: -0 stays -0), then ONE fp32 product with scale, skipped
+ * when scale == 1.0f.  It is formed in registers in the pass that applies it and never written: no float atomics, no library
+ * reduction whose order depends on a backend or a ring, and every rank computes the same bits from the same bytes.  Otherwise
+ * surs_optim_step: its chunking, its grid, its 16-byte path (which here also needs rank_stride % 4 == 0; scalar access otherwise),
+ * its refusals, and additionally SURS_E_INVALID for num_ranks outside 1 .. 64, rank_stride < 0 and a NaN scale.  num_ranks == 1 with
+ * scale == 1.0f gives surs_optim_step's bits.  Non-finite gradients of any rank propagate (see surs_tensors_nonfinite for the guard:
+ * run over the gathered buffer as num_ranks refs of one row each, the lowest index is the lowest offending rank). */
+int surs_optim_step_ranks(const SursOptimItem *items, int n_items, const SursOptimHyper *h, int num_ranks, long long rank_stride,
+                          float scale, void *stream);
+/* The same loop on the HOST (host table, host pointers), after surs_optim_check and the checks above: what the kernel is held
+ * against bit for bit. */
+int surs_optim_step_ranks_host(const SursOptimItem *items, int n_items, const SursOptimHyper *h, int num_ranks, long long rank_stride,
+                               float scale);
+
+/* One tensor of a surs_tensors_pack table: n floats copied from src to dst (device pointers; host pointers for the host twin). */
+typedef struct SursPackItem {
+    const float *src;
+    float *dst;
+    long long n;         /* elements; 0 is legal and costs nothing */
+    int chunk_end;       /* the inclusive prefix sum of surs_optim_chunks(n) over the table, as in SursOptimItem */
+    int reserved;
+} SursPackItem;
+
+/* Checks a HOST copy of a table: SURS_E_INVALID for n < 0, a null src or dst of an item with n > 0, or a chunk_end that is not the
+ * prefix sum.  Ranges must not overlap (not checked). */
+int surs_tensors_pack_check(const SursPackItem *items, int n_items);
+/* ONE launch on `stream` copies every item of the DEVICE table: how a rank's gradient tensors reach its send slab.  The optimiser
+ * step's chunking and grid; 16-byte access where src and dst are both 16-byte aligned at the chunk, scalar otherwise and for the
+ * n % 4 tail.  A copy: no sums, so no order to state.  n_items == 0 does nothing. */
+int surs_tensors_pack(const SursPackItem *items, int n_items, void *stream);
+/* The same copy on the HOST, after surs_tensors_pack_check: nothing is written when it refuses. */
+int surs_tensors_pack_host(const SursPackItem *items, int n_items);
+
 /* ---------------------------------------------------------------- training step
  * What one iteration of the reference's training loop (apps/train_SuRS.py:122-148) needs besides the taped forwards, their backwards
  * and the optimiser step: the loss with the gradient of its image term, and a guard against non-finite gradients

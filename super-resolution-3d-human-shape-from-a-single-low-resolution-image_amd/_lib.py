@@ -141,6 +141,11 @@ class OptimItem(C.Structure):
                 ("chunk_end", C.c_int), ("reserved", C.c_int)]
 
 
+class PackItem(C.Structure):
+    """SursPackItem of include/surs.h: one tensor of a surs_tensors_pack table (chunk_end as in SursOptimItem)."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("n", C.c_longlong), ("chunk_end", C.c_int), ("reserved", C.c_int)]
+
+
 class TensorRef(C.Structure):
     """SursTensorRef of include/surs.h: one tensor of a surs_tensors_nonfinite table (chunk_end as in SursOptimItem)."""
     _fields_ = [("p", C.c_void_p), ("n", C.c_longlong), ("chunk_end", C.c_int), ("reserved", C.c_int)]
@@ -346,6 +351,11 @@ _SIGS = {
     "surs_optim_check": (C.c_int, [_vp, _i, C.POINTER(OptimHyper)]),
     "surs_optim_step": (C.c_int, [_vp, _i, C.POINTER(OptimHyper), _vp]),
     "surs_optim_step_host": (C.c_int, [_vp, _i, C.POINTER(OptimHyper)]),
+    "surs_optim_step_ranks": (C.c_int, [_vp, _i, C.POINTER(OptimHyper), _i, C.c_longlong, _f, _vp]),
+    "surs_optim_step_ranks_host": (C.c_int, [_vp, _i, C.POINTER(OptimHyper), _i, C.c_longlong, _f]),
+    "surs_tensors_pack_check": (C.c_int, [_vp, _i]),
+    "surs_tensors_pack": (C.c_int, [_vp, _i, _vp]),
+    "surs_tensors_pack_host": (C.c_int, [_vp, _i]),
     "surs_forward_losses_grad_workspace_bytes": (_sz, []),
     "surs_forward_losses_grad": (C.c_int, [_vp, _vp, _i, C.c_longlong, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp,
                                            _vp]),

@@ -75,6 +75,32 @@ SURS_HD inline void ou_update(float &p, float g, float &s0, float &s1, float &s2
     else ou_rmsprop(p, g, s0, h);
 }
 
+// The gradient a data-parallel step applies (surs_optim_step_ranks): rank r's value lies r * stride values of T behind rank 0's, and
+// the result is ((g_0 + g_1) + ... + g_{R-1}) * scale - fp32 sums left to right STARTING FROM g_0 (0 + g_0 would turn a -0 into +0),
+// then one fp32 product, skipped at scale == 1 - so that R == 1, scale == 1 returns g_0's bits untouched.  T is float, or the
+// kernel's four-float vector (the same sums per component); P the pointer's value type (an address-space-qualified one on the
+// device).  The loads of OU_RANK_UNROLL ranks are issued before the first of their adds: independent loads in flight, where one
+// load per add would pay a memory latency per rank.  The order of the adds does not depend on the unroll.
+constexpr int OU_RANK_UNROLL = 8;
+constexpr int OU_MAX_RANKS = 64;
+
+template <typename T, typename P>
+SURS_HD inline T ou_rank_sum(const P *g, long long stride, int R, float scale) {
+    T v[OU_RANK_UNROLL];
+    T acc = g[0];
+    for (int r0 = 0; r0 < R; r0 += OU_RANK_UNROLL) {
+        const int c = R - r0 < OU_RANK_UNROLL ? R - r0 : OU_RANK_UNROLL;
+#pragma unroll
+        for (int j = 0; j < OU_RANK_UNROLL; ++j)
+            if (j < c && r0 + j > 0) v[j] = g[(long long)(r0 + j) * stride];
+#pragma unroll
+        for (int j = 0; j < OU_RANK_UNROLL; ++j)
+            if (j < c && r0 + j > 0) acc = acc + v[j];
+    }
+    if (scale != 1.0f) acc = acc * scale;
+    return acc;
+}
+
 // elements per workgroup visit: 256 lanes x 4 floats x 4 rounds
 constexpr int OU_CHUNK = 4096;
 SURS_HD inline int ou_chunks(long long n) { return n <= 0 ? 0 : (int)((n + OU_CHUNK - 1) / OU_CHUNK); }

@@ -790,3 +790,178 @@ def assemble_slab_meshes(res, counts, top_ids, fixup, R, dev, dst=0, group=None,
                 ex.send(res[f][1], dst)
     ex.start().wait()
     return out if rank == dst else None
+
+
+# ------------------------------------------------------------------ data-parallel training
+def shard_indices(n_batches, rank, world, seed=0, shuffle=True):
+    """The batches rank `rank` of `world` takes out of n_batches: every rank forms the SAME permutation (numpy's default_rng(seed);
+    the identity with shuffle=False), drops the tail that does not fill a round of `world`, and takes positions rank, rank + world,
+    ... of the rest - disjoint shards of n_batches // world batches each, so that every rank takes the same number of steps and no
+    rank waits in a collective for a peer that has run out of data."""
+    n_batches, rank, world = int(n_batches), int(rank), int(world)
+    if world < 1 or not 0 <= rank < world or n_batches < 0:
+        raise ValueError("shard_indices: rank %d of %d, %d batches" % (rank, world, n_batches))
+    order = np.random.default_rng(int(seed)).permutation(n_batches) if shuffle else np.arange(n_batches)
+    return [int(i) for i in order[:n_batches // world * world][rank::world]]
+
+
+class TrainGroup:
+    """TrainGroup(net, optimizer, group=None): R processes train ONE model, each on its own batches (one node, one GPU per rank).
+
+        stepped = tg.step(grads, guard=True)      # instead of optimizer.step(grads, guard=True)
+
+    step() packs this rank's gradients into one flat slab (ONE launch of surs_tensors_pack; every key at the optimiser's own
+    16-byte-aligned offset, Optimizer._offset; every key that has a gradient takes the copy - no backward entry writes into the slab
+    directly), all-gathers the R slabs (all_gather_into_tensor: RCCL on device buffers, gloo staged through the host like the slab
+    exchange above), and calls optimizer.step(ranks=(gathered, R)): one launch forms ((g_0 + g_1) + ... + g_{R-1}) * fp32(1 / R) per
+    element in rank order and applies the update in the same pass.  No library all-reduce, whose order depends on the backend and
+    its ring: every rank computes the same bits from the same bytes, so the replicas cannot drift, and the result is a function of
+    (R, the gradients) alone - the same over gloo and over RCCL.  Keys without a gradient leave zeros in the slab: it is zeroed once,
+    and afterwards only the keys that had a gradient in the previous step and have none now are cleared.  The mean of the ranks'
+    gradients is the gradient of the mean of their losses: the effective batch is R times --batch_size, at the user's learning rate.
+
+    guard=True: the gathered buffer is searched as R tensors (surs_tensors_nonfinite); on a hit EVERY rank returns False - the same
+    answer from the same bytes, without another collective - nothing is launched, parameters, state and step count stay bit for bit,
+    optimizer.skipped counts it and optimizer.last_skipped_rank names the lowest offending rank.  fail() is what a rank calls whose
+    forward raised (non-finite features): it joins the same collective with a slab of NaN, so that the peers skip instead of hanging.
+    One rank, or no process group: no collective at all, and the plain step's bits.
+
+    Not here: overlapping the exchange with the backward (bucketing), sharded optimiser state, more than one node, a reduce-scatter
+    variant (the all-gather moves (R - 1) G bytes into each rank against 2 (R - 1) / R G of a ring all-reduce; INTEGRATION.md
+    "Data-parallel training")."""
+
+    def __init__(self, net, optimizer, group=None):
+        self.net, self.optimizer, self.group = net, optimizer, group
+        self.world, self.rank = _world(group)
+        dev, total = optimizer.device, optimizer._total
+        self._send = torch.zeros(total, dtype=torch.float32, device=dev)
+        self._gathered = self._send.view(1, total) if self.world == 1 else torch.empty((self.world, total), dtype=torch.float32, device=dev)
+        self._host = None                  # gloo: pinned staging buffers (send, gathered)
+        self._had = set()                  # the keys whose gradients the slab holds
+        self._sig = self._table = self._n_items = None
+        self._keep = None
+
+    # -------------------------------------------------------------- pack and gather
+    def _pack(self, grads):
+        from . import native
+        import ctypes as C
+        o = self.optimizer
+        todo = o._gradients(grads)
+        now = set(k for k, _ in todo)
+        for k in self._had - now:
+            self._send[o._offset[k]:o._offset[k] + o._masters[k].numel()].zero_()
+        self._had = now
+        if todo:
+            sig = tuple((k, g.data_ptr()) for k, g in todo)
+            if sig != self._sig:
+                items = native.pack_items([(g.data_ptr(), self._send.data_ptr() + 4 * o._offset[k], g.numel()) for k, g in todo])
+                nbytes = C.sizeof(items)
+                host = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+                C.memmove(host.data_ptr(), C.addressof(items), nbytes)
+                self._table = torch.empty(nbytes, dtype=torch.uint8, device=o.device)
+                self._table.copy_(host, non_blocking=True)
+                self._sig, self._n_items = sig, len(todo)
+            self._keep = [g for _, g in todo]
+            native.tensors_pack(self._table, self._n_items)
+        return todo
+
+    def _gather(self):
+        if self.world == 1:
+            return
+        if _host_staged(self._send, self.group):
+            if self._host is None:
+                self._host = (torch.empty(self._send.shape, dtype=torch.float32).pin_memory(),
+                              torch.empty(self._gathered.shape, dtype=torch.float32).pin_memory())
+            h_in, h_out = self._host
+            h_in.copy_(self._send)         # synchronises: the pack has finished
+            dist.all_gather_into_tensor(h_out.view(-1), h_in, group=self.group)   # (gloo takes the concatenated 1-D form only)
+            self._gathered.copy_(h_out, non_blocking=True)
+        else:
+            dist.all_gather_into_tensor(self._gathered.view(-1), self._send, group=self.group)
+
+    def step(self, grads, guard=True):
+        """See the class.  Returns what optimizer.step returns: True / False with guard, None without."""
+        todo = self._pack(grads)
+        self._gather()
+        return self.optimizer.step({k: True for k, _ in todo}, guard=guard, ranks=(self._gathered, self.world))
+
+    def fail(self):
+        """This rank has no gradients to offer (its forward raised): join the step's collective with a slab of NaN.  Every rank's
+        guard then names this rank (or a lower one that failed too) and skips; returns False.  The peers must step with guard=True."""
+        self._send.fill_(float("nan"))
+        self._gather()
+        stepped = self.optimizer.step(None, guard=True, ranks=(self._gathered, self.world))
+        self._send.zero_()
+        self._had = set()
+        return stepped
+
+    # -------------------------------------------------------------- replicas
+    def _bcast(self, t, src):
+        if self.world == 1:
+            return
+        if _host_staged(t, self.group):
+            h = t.cpu()
+            dist.broadcast(h, _global_rank(self.group, src), group=self.group)
+            if self.rank != src:
+                t.copy_(h)
+        else:
+            dist.broadcast(t, _global_rank(self.group, src), group=self.group)
+
+    def broadcast_state(self, src=0):
+        """Masters and optimiser state (its slabs, step count and stepped keys) of rank `src` to every rank, then net.commit(): how
+        the replicas are made equal at the start of a run and after a resume."""
+        o = self.optimizer
+        if self.world > 1:
+            masters = list(o._masters.values())
+            flat = torch.cat([m.detach().reshape(-1) for m in masters])
+            self._bcast(flat, src)
+            if self.rank != src:
+                at = 0
+                for m in masters:
+                    m.detach().copy_(flat[at:at + m.numel()].view(m.shape))
+                    at += m.numel()
+            meta = [(o._t, sorted(o._seen), o.kind, [dict(g) for g in o.param_groups])]
+            dist.broadcast_object_list(meta, _global_rank(self.group, src), group=_host_group(self.group))
+            t, seen, kind, groups = meta[0]
+            if kind != o.kind:
+                raise ValueError("TrainGroup.broadcast_state: rank %d runs %s, this rank %s" % (src, kind, o.kind))
+            o._t, o._seen, o.param_groups = int(t), set(seen), groups
+            for n in o._state_names():
+                self._bcast(o._slab(n), src)
+            o._sig = None
+        self.net.commit(o.which)
+
+    def replicas_digest(self):
+        """[world] Python ints: per rank an int64 checksum of the bits of every master (position-weighted sums of the int32 bit
+        patterns, wrapping, combined over the keys in order), all-gathered."""
+        o = self.optimizer
+        sums = []
+        for m in o._masters.values():
+            bits = m.detach().reshape(-1).view(torch.int32).to(torch.int64)
+            sums.append((bits * torch.arange(1, bits.numel() + 1, dtype=torch.int64, device=bits.device)).sum())
+        d = 0
+        for s in torch.stack(sums).cpu().tolist():
+            d = (d * 1000003 + s) % (1 << 62)
+        if self.world == 1:
+            return [d]
+        hg = _host_group(self.group)
+        on = o.device if dist.get_backend(hg) != "gloo" else torch.device("cpu")
+        mine = torch.tensor([d], dtype=torch.int64, device=on)
+        out = [torch.empty_like(mine) for _ in range(self.world)]
+        dist.all_gather(out, mine, group=hg)
+        return [int(t.item()) for t in out]
+
+    def assert_replicas_equal(self):
+        """RuntimeError naming the first rank whose masters differ from rank 0's (replicas_digest)."""
+        d = self.replicas_digest()
+        for r, v in enumerate(d):
+            if v != d[0]:
+                raise RuntimeError("TrainGroup: the masters of rank %d differ from rank 0's (digests %d, %d): the replicas have drifted"
+                                   % (r, v, d[0]))
+        return d[0]
+
+    def mean_over_ranks(self, value):
+        """The mean of one float per rank (one tiny all_gather); a NaN on any rank gives NaN."""
+        if self.world == 1:
+            return float(value)
+        return float(all_gather_rows([value], self.optimizer.device, self.group)[:, 0].mean())

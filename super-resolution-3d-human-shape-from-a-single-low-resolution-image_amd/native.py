@@ -1158,6 +1158,56 @@ def optim_step_host(tensors, hyper):
     check(lib().surs_optim_step_host(C.cast(optim_items(rows), C.c_void_p), len(rows), C.byref(hyper)))
 
 
+def optim_step_ranks(table, n_items, hyper, num_ranks, rank_stride, scale):
+    """surs_optim_step_ranks: optim_step with the gradient of element i of an item read as g[i + r * rank_stride], r = 0 .. num_ranks - 1
+    (g points into row 0 of a gathered [num_ranks, rank_stride] buffer), summed in fp32 left to right from g_0 and multiplied once by
+    the fp32 `scale` (skipped at 1.0) - in the pass that applies it; the sum is never written.  One launch on the current stream."""
+    check(lib().surs_optim_step_ranks(_ptr(table), n_items, C.byref(hyper), int(num_ranks), int(rank_stride), float(scale), _stream()))
+
+
+def optim_step_ranks_host(tensors, hyper, num_ranks, rank_stride, scale):
+    """surs_optim_step_ranks_host over rows (p, g, s0, s1, s2) as optim_step_host takes them, except that g is a VIEW into row 0 of a
+    contiguous float32 [num_ranks, rank_stride] numpy array (p.size elements of it): the rows behind it are read through the stride."""
+    rows = []
+    for r in tensors:
+        p = r[0]
+        for a in r:
+            if a is not None and (a.dtype != np.float32 or not a.flags.c_contiguous):
+                raise ValueError("optim_step_ranks_host: contiguous float32 arrays expected")
+        for a in r[1:]:
+            if a is not None and a.size != p.size:
+                raise ValueError("optim_step_ranks_host: a tensor of %d elements against a parameter of %d" % (a.size, p.size))
+        rows.append(tuple(a.ctypes.data if a is not None else None for a in r) + (p.size,))
+    check(lib().surs_optim_step_ranks_host(C.cast(optim_items(rows), C.c_void_p), len(rows), C.byref(hyper), int(num_ranks),
+                                           int(rank_stride), float(scale)))
+
+
+def pack_items(rows):
+    """A host array of SursPackItem over rows (src, dst, n) of raw addresses, chunk_end filled in, checked by the library."""
+    items = (_lib.PackItem * max(len(rows), 1))()
+    end = 0
+    for it, (src, dst, n) in zip(items, rows):
+        end += lib().surs_optim_chunks(n)
+        it.src, it.dst, it.n, it.chunk_end = src, dst, n, end
+    check(lib().surs_tensors_pack_check(C.cast(items, C.c_void_p), len(rows)))
+    return items
+
+
+def tensors_pack(table, n_items):
+    """surs_tensors_pack: every item of the DEVICE table `table` (the bytes of pack_items' array) copied by one launch on the current
+    stream."""
+    check(lib().surs_tensors_pack(_ptr(table), n_items, _stream()))
+
+
+def tensors_pack_host(pairs):
+    """surs_tensors_pack_host over (src, dst) pairs of contiguous float32 numpy arrays of equal size."""
+    for s, d in pairs:
+        if any(a.dtype != np.float32 or not a.flags.c_contiguous for a in (s, d)) or s.size != d.size:
+            raise ValueError("tensors_pack_host: contiguous float32 arrays of equal size expected")
+    rows = [(s.ctypes.data, d.ctypes.data, s.size) for s, d in pairs]
+    check(lib().surs_tensors_pack_host(C.cast(pack_items(rows), C.c_void_p), len(rows)))
+
+
 # ------------------------------------------------------------------ training step: the loss head and the non-finite guard
 
 def forward_losses_grad(pred_lr, lab_lr, pred_hr, lab_hr, img_sr_nhwc, img_hr, weights, want_grad=True):

@@ -101,6 +101,7 @@ class Optimizer:
         self._keep = None
         self.skipped = 0                   # steps step(guard=True) refused because a gradient was not finite
         self.last_skipped_key = None       # the first key (in parameter order) whose gradient was not finite in the last refused step
+        self.last_skipped_rank = None      # step(ranks=..., guard=True): the lowest rank whose gathered slab was not finite
         self._guard_sig = self._guard_table = self._guard_ws = self._guard_total = None
 
     # ------------------------------------------------------------------ state
@@ -163,7 +164,55 @@ class Optimizer:
             self._guard_sig, self._guard_total = sig, total
         return int(native.tensors_nonfinite(self._guard_table, len(todo), self._guard_total, workspace=self._guard_ws).item())
 
-    def step(self, grads=None, commit=True, guard=False):
+    def _step_ranks(self, grads, ranks, commit, guard, hyper):
+        """step(ranks=(gathered, R)): see step()."""
+        gathered, R = ranks
+        R = int(R)
+        if (not torch.is_tensor(gathered) or gathered.dtype != torch.float32 or gathered.device != self.device
+                or tuple(gathered.shape) != (R, self._total) or not gathered.is_contiguous() or gathered.data_ptr() % 16):
+            raise ValueError("Optimizer.step(ranks=): a contiguous 16-byte-aligned float32 [%d, %d] tensor on %s is expected, got %s" % (
+                R, self._total, self.device, "%s %s" % (tuple(gathered.shape), gathered.dtype) if torch.is_tensor(gathered)
+                else type(gathered).__name__))
+        keys = self._keys if grads is None else [k for k in self._keys if k in grads and grads[k] is not None]
+        if not keys:
+            return None
+        if guard:
+            sig = ("ranks", gathered.data_ptr(), R)
+            if sig != self._guard_sig:
+                items, total = native.tensor_refs([(gathered.data_ptr() + 4 * r * self._total, self._total) for r in range(R)])
+                self._guard_table = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(self.device)
+                self._guard_ws = torch.empty(max(total, 1), dtype=torch.int32, device=self.device)
+                self._guard_sig, self._guard_total = sig, total
+            hit = int(native.tensors_nonfinite(self._guard_table, R, self._guard_total, workspace=self._guard_ws).item())
+            if hit >= 0:
+                self.skipped += 1
+                self.last_skipped_rank, self.last_skipped_key = hit, None
+                return False
+        names = self._state_names()
+        sig = ("ranks", names, gathered.data_ptr(), R, tuple(keys) if grads is not None else None)
+        if sig != self._sig:
+            rows = []
+            for k in keys:
+                s = [self._slice(n, k).data_ptr() for n in names] + [None] * (3 - len(names))
+                rows.append((self._masters[k].data_ptr(), gathered.data_ptr() + 4 * self._offset[k], s[0], s[1], s[2],
+                             self._masters[k].numel()))
+            items = native.optim_items(rows)
+            native.optim_check(items, len(rows), hyper)
+            nbytes = C.sizeof(items)
+            host = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
+            C.memmove(host.data_ptr(), C.addressof(items), nbytes)
+            self._table = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._table.copy_(host, non_blocking=True)
+            self._sig, self._n_items = sig, len(rows)
+        self._keep = [gathered]
+        native.optim_step_ranks(self._table, self._n_items, hyper, R, self._total, C.c_float(1.0 / R).value)
+        self._t += 1
+        self._seen.update(keys)
+        if commit:
+            self.net.commit(self.which)
+        return True if guard else None
+
+    def step(self, grads=None, commit=True, guard=False, ranks=None):
         """One step of every key that has a gradient, in one launch on the current stream, then net.commit(which) unless commit=False.
         grads: a mapping state-dict key -> device tensor - the OrderedDicts classifier_grads() / forward_backward(),
         super_res_backward() and filter_lr_backward() return, or a merge of them; any shape with the right element count; keys of other
@@ -175,12 +224,21 @@ class Optimizer:
         operand parts: an activation beyond the f16 range gives non-finite features and gradients, and one such step would poison every
         master.  On a hit nothing is launched: parameters, optimiser state and the step count stay bit for bit as they were, `skipped`
         counts the step, `last_skipped_key` names the first offending key, and the call returns False; otherwise it returns True after
-        the step guard=False would have taken (the same bits).  Returns None with guard=False, as before."""
+        the step guard=False would have taken (the same bits).  Returns None with guard=False, as before.
+        ranks=(gathered, R): the data-parallel step (dist.TrainGroup makes the buffer).  gathered is a contiguous float32 [R, total]
+        device tensor, row r the gradient slab of rank r with key k at this optimiser's own offset _offset[k] (zeros where a rank had
+        no gradient); the table's g points into row 0 and ONE launch of surs_optim_step_ranks applies ((g_0 + g_1) + ... + g_{R-1}) *
+        fp32(1 / R) - sums in rank order, never written.  grads then only NAMES the keys to step (a mapping; None: every key) - the
+        keys any rank had a gradient for, which in a data-parallel run is every rank's own set.  guard=True searches the R rows
+        (surs_tensors_nonfinite over R refs): on a hit nothing is launched, `skipped` counts it and `last_skipped_rank` is the lowest
+        offending rank - the same answer on every rank, from the same bytes.  R = 1 gives the plain step's bits."""
         for w in self.which:
             if self.net._masters().get(w) is not self._owners[w]:
                 raise RuntimeError("Optimizer.step: the net's %r masters were replaced (load_state_dict() / to()): make a new Optimizer "
                                    "and load_state_dict() this one's state_dict()" % w)
         hyper = self._hyper()
+        if ranks is not None:
+            return self._step_ranks(grads, ranks, commit, guard, hyper)
         todo = self._gradients(grads)
         if not todo:
             return None

@@ -88,6 +88,12 @@ _NATIVE = [
     ("synthetic", None, False),      # synthetic image + PRNG weights instead of dataroot / checkpoint
     ("pipeline", None, False),       # eval driver: subjects as a pipeline (train_util.gen_mesh_pipelined) instead of one by one
     ("seed", int, 0),                # training driver: the dataset's samples, the loader's shuffle and the augmentations' host generators
+    # training driver, data-parallel (dist.TrainGroup): everything by flag, nothing from the environment
+    ("world_size", int, 1),          # processes training one model, one GPU each (rank r on GPU r % device_count); 1 = today's run
+    ("rank", int, -1),               # this process's rank; -1 with --world_size N > 1: start the N ranks as child processes and wait
+    ("dist_backend", str, "nccl"),   # nccl (RCCL, device buffers) | gloo (host staging: ranks that share one GPU, tests)
+    ("dist_url", str, "tcp://127.0.0.1:29533"),   # init_process_group's init_method
+    ("dist_timeout", float, 600.0),  # seconds a collective waits for a peer before the run ends with an error
 ]
 
 

@@ -17,6 +17,15 @@ Every measurement runs in a process of its own, ROUNDS times, the children alter
 line per child and a summary (min / median / max over the rounds).
 
     python tools/gpu_train_step_time.py [--rounds 5] [--out FILE] [--parent-lib FILE] [--children full autograd ...]
+
+--world N times the DATA-PARALLEL step instead (dist.TrainGroup; INTEGRATION.md "Data-parallel training"): N processes, rank r on GPU
+r % device_count - RCCL when every rank has a GPU of its own, else gloo ranks sharing a GPU, which says nothing about xGMI and is
+reported as such (`backend`) -, every rank at the options above on its own seeded batch.  Per rank: steps per second of
+forward_backward + TrainGroup.step(guard=True) with the host running ahead, and, from a second loop with a synchronise on either side
+of TrainGroup.step, the share of a step spent in pack + all-gather + fused step.  One JSON line (rank 0) per round with the slowest
+rank's figures.
+
+    python tools/gpu_train_step_time.py --world 8 [--rounds 5] [--out FILE]
 """
 import argparse
 import json
@@ -42,6 +51,112 @@ def _use_parent_lib(path):
     for name in [k for k in _lib._SIGS if not hasattr(old, k)]:
         del _lib._SIGS[name]
     _lib.EXPORTS[:] = sorted(_lib._SIGS)
+
+
+def _training_inputs(opt, dev, seed=0):
+    import numpy as np
+    import torch
+    import common
+    from surs_amd import prng, weights
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
+    s = 100 * seed
+    return dict(images_lr=up(np.concatenate([weights.synthetic_image(H, seed=s + 1 + b) for b in range(B)], 0)),
+                images_hr=up(prng.uniform("img_hr", s + 7, (B, 3, 2 * H, 2 * H), -1.0, 1.0)),
+                points_hr=up(np.stack([weights.synthetic_points(N, seed=s + 30 + b) for b in range(B)])),
+                points_lr=up(np.stack([weights.synthetic_points(N, seed=s + 40 + b) for b in range(B)])),
+                calibs=up(np.stack([common.CALIB] * B)),
+                labels_hr=up(prng.uniform("lab_hr", s + 1, (B, 1, N), 0.0, 1.0) > 0.5),
+                labels_lr=up(prng.uniform("lab_lr", s + 1, (B, 1, N), 0.0, 1.0) > 0.5))
+
+
+def dp_worker(rank, world, port, backend):
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import datetime
+    import torch
+    import torch.distributed as tdist
+    from surs_amd import dist as sdist, model, optim, options, weights
+    dev = torch.device("cuda:%d" % (rank % torch.cuda.device_count()))
+    torch.cuda.set_device(dev)
+    tdist.init_process_group(backend, init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=world,
+                             timeout=datetime.timedelta(seconds=240))
+    opt = options.BaseOptions().parse(["--residual", "--loadSize", "512", "--batch_size", str(B), "--num_sample_inout", str(N)])
+    net = model.SuRSNet(opt).to(device=dev)
+    net.load_state_dict(weights.synthetic_state_dict(opt, seed=0))
+    net.train()
+    x = _training_inputs(opt, dev, seed=rank)
+    o = optim.Optimizer(net, "ADAM", lr=1e-5)
+    tg = sdist.TrainGroup(net, o)
+    tg.broadcast_state(0)
+    sync = torch.cuda.synchronize
+
+    def grads():
+        return net.forward_backward(x["images_lr"], x["images_hr"], x["points_lr"], x["points_hr"], x["calibs"], labels_lr=x["labels_lr"],
+                                    labels_hr=x["labels_hr"], encoder=True)[3]
+    for _ in range(WARMUP):
+        tg.step(grads(), guard=True)
+    sync()
+    tdist.barrier()
+    t = time.perf_counter()
+    for _ in range(STEPS):
+        tg.step(grads(), guard=True)
+    sync()
+    ms = (time.perf_counter() - t) / STEPS * 1e3
+    exchange = 0.0
+    t = time.perf_counter()
+    for _ in range(STEPS):
+        g = grads()
+        sync()
+        t0 = time.perf_counter()
+        tg.step(g, guard=True)
+        sync()
+        exchange += time.perf_counter() - t0
+    split_ms = (time.perf_counter() - t) / STEPS * 1e3
+    tg.assert_replicas_equal()
+    rows = sdist.all_gather_rows([ms, exchange / STEPS * 1e3, split_ms], dev)
+    if rank == 0:
+        slow = rows[rows[:, 0].argmax()]
+        print(json.dumps(dict(child="dp", world=world, backend=backend, gpus=torch.cuda.device_count(), ms=float(slow[0]),
+                              steps_per_s=1e3 / float(slow[0]), items_per_s=1e3 / float(slow[0]) * B * world,
+                              exchange_ms=float(rows[:, 1].max()), exchange_share=float(rows[:, 1].max() / slow[2]),
+                              gradient_bytes=4 * o._total, skipped=o.skipped)), flush=True)
+    tdist.destroy_process_group()
+
+
+def main_dp(args):
+    """--world N: this process only starts the ranks (it never touches a GPU) and prints their lines."""
+    import socket
+    results = []
+    for r in range(args.rounds):
+        s = socket.socket()
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+        s.close()
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-world", str(args.world), "--port", str(port)],
+                           capture_output=True, text=True, timeout=900)
+        if p.returncode != 0:   # nothing more is started on the device after a failure
+            sys.stderr.write(p.stdout[-2000:] + p.stderr[-4000:])
+            raise SystemExit("data-parallel child failed (%d)" % p.returncode)
+        line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
+        print(line, flush=True)
+        results.append(json.loads(line))
+    med = lambda k: sorted(d[k] for d in results)[len(results) // 2]
+    text = json.dumps(dict(rounds=args.rounds, steps=STEPS, batch_per_rank=B, image=H, points=N, world=args.world, backend=results[0]["backend"],
+                           gpus=results[0]["gpus"], gradient_bytes=results[0]["gradient_bytes"],
+                           summary={k: dict(min=min(d[k] for d in results), median=med(k), max=max(d[k] for d in results))
+                                    for k in ("ms", "steps_per_s", "items_per_s", "exchange_ms", "exchange_share")}), indent=1)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+def child_world(args):
+    import torch
+    import torch.multiprocessing as mp
+    world = args.child_world
+    backend = "nccl" if torch.cuda.device_count() >= world else "gloo"
+    mp.spawn(dp_worker, args=(world, args.port, backend), nprocs=world, join=True)
 
 
 def child(args):
@@ -139,7 +254,14 @@ def main():
     ap.add_argument("--parent-lib", help="another build of libsurs_hip.so for bench_parent and optim_parent")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out")
+    ap.add_argument("--world", type=int, help="time the data-parallel step on this many ranks instead")
+    ap.add_argument("--child-world", type=int)
+    ap.add_argument("--port", type=int)
     args = ap.parse_args()
+    if args.child_world:
+        return child_world(args)
+    if args.world:
+        return main_dp(args)
     if args.child:
         return child(args)
     children = args.children or list(CHILDREN + (PARENT_CHILDREN if args.parent_lib else ()))
