@@ -1023,6 +1023,75 @@ int surs_mesh_shade_normals_host(const float *verts, int nv, const int32_t *face
                                  const float *vertex_normals, const float *normal_matrix, const int32_t *face, const float *bary, int w,
                                  int h, float *out);
 
+/* ---------------------------------------------------------------- mesh PRT
+ * Per-vertex precomputed radiance transfer: what a textured scan needs before its training views can be lit and rendered
+ * (surs_amd/render.py, apps/render_data.py).  The reference's renderer (lib/renderer, OpenGL) reads such vectors from a ray-traced
+ * preprocessing step it does not ship; this is that step, by brute force over all faces, stated independently:
+ *   prt[v][i] = (4 pi / D) sum_k V(v, d_k) max(0, n_v . d_k) Y_i(d_k),     k = 0 .. D - 1 in index order, one fp32 accumulator each,
+ * a term with n . d_k <= 0 skipped, the scale 12.566371f / D applied once at the end.  Y_0..8: the real spherical harmonics of bands
+ * 0 - 2 in the order l (l + 1) + m: 0.282095; 0.488603 (y, z, x); 1.092548 xy, 1.092548 yz, 0.315392 (3 z^2 - 1), 1.092548 xz,
+ * 0.546274 (x^2 - y^2).  V = 0 where the ray from v + offset n along d_k hits a triangle at t > 0 - Moeller-Trumbore, edges inclusive
+ * (u >= 0, v >= 0, u + v <= 1), a triangle that lists v as a corner (by INDEX) skipped, a zero-area or non-finite triangle hitting
+ * nothing -, else 1.  A vertex with a non-finite position or normal gets 0.  A mesh as in "training samples" (indices clamped to
+ * [0, nv)); normals [nv, 3] unit vectors, dirs [D, 3] unit vectors (an argument: render.prt_directions makes the default set), prt
+ * [nv, 9].  The arithmetic is csrc/surs_mesh_prt.h, one for host and device: the same arguments give the same bits, and a vertex's
+ * bits depend neither on nv, nor on its place in the array, nor on the workspace.
+ * The faces stream through LDS SURS_MESH_PRT_CHUNK at a time; the workspace holds one bit per (vertex, direction) pair,
+ * surs_mesh_prt_workspace_bytes(nv, D) (0 for nv or D < 1 or more than 2^31 - 512 pairs), whatever the number of faces.
+ * SURS_E_INVALID, before anything is launched or written: a NULL array, nv < 1, nf < 1, D < 1, more than 2^31 - 512 pairs, an offset
+ * that is negative or not finite, a workspace that is too small.
+ * surs_mesh_prt_host is the same header looped on the HOST (all pointers host pointers): the kernels' bits, no device; visible
+ * (nullable) [nv, D] gets 1 where a pair contributed (n . d > 0 and nothing hit), else 0.
+ * surs_mesh_prt_counted is surs_mesh_prt - the same bits - that also writes wave_tests [ceil(nv D / 64)] uint32 (device, not NULL):
+ * the number of triangles each wave of 64 rays looked at before it left the face loop; 64 times their sum is the number of ray -
+ * triangle tests executed (tools/gpu_render_time.py). */
+#define SURS_MESH_PRT_CHUNK 512
+size_t surs_mesh_prt_workspace_bytes(int nv, int D);
+int surs_mesh_prt_counted(const float *verts, int nv, const int32_t *faces, int nf, const float *normals, const float *dirs, int D,
+                          float offset, float *prt, void *workspace, size_t workspace_bytes, uint32_t *wave_tests, void *stream);
+int surs_mesh_prt(const float *verts, int nv, const int32_t *faces, int nf, const float *normals, const float *dirs, int D, float offset,
+                  float *prt, void *workspace, size_t workspace_bytes, void *stream);
+int surs_mesh_prt_host(const float *verts, int nv, const int32_t *faces, int nf, const float *normals, const float *dirs, int D,
+                       float offset, float *prt, uint8_t *visible);
+
+/* ---------------------------------------------------------------- mesh shading
+ * The colour of a rastered view: texture, spherical-harmonic lighting, gamma, and the box resolve that stands in for multisampling.
+ * The arithmetic is csrc/surs_mesh_shade.h, one for host and device, and calls no math library (its log2 / exp2 are short fp32
+ * polynomials): the same arguments give the same bits on both sides.
+ *
+ * surs_texture_pyramid: tex [h, w, 3] uint8, row 0 the TOP of the image -> levels, surs_texture_pyramid_floats(w, h) floats: level 0
+ * (tex / 255) and three further levels, each the 2 x 2 mean of the one above, packed one after the other.  w and h multiples of 8 in
+ * [8, 16384], else SURS_E_INVALID (and 0 floats).
+ *
+ * surs_mesh_shade_prt: face [h, w] and bary [h, w, 2] as surs_mesh_raster wrote them for (verts, faces, view, w, h) -> rgba [h, w, 4]
+ * fp32.  Corners are the raster's (ascending vertex index); faces_uv [nf, 3] is given in the FACE's own corner order and permuted
+ * inside the call.  Per covered pixel: uv = the barycentric blend of the corners' uvs [nuv, 2]; albedo = a trilinear lookup in
+ * `pyramid` (tw x th; bilinear within a level, clamp to edge, texel centres at (i + 1/2) / size, v = 0 the LAST row), the level
+ * lambda = clamp(1/2 log2(A_tex / A_pix), 0, 3) constant per face (A_tex: its uv area in level-0 texels, A_pix: its projected area in
+ * pixels); s_c = sum_i p_i light[i][c] by fma in ascending i; rgb_c = clamp(albedo_c max(s_c, 0)^(1/2.2), 0, 1), a = 1; background
+ * (0, 0, 0, 0).  pyramid NULL: albedo 1 (faces_uv, uvs not read).  p is the barycentric blend of prt [nv, 9] (light [9, 3] then in
+ * prt's frame, the mesh's), or - prt NULL - A_l Y_i(n) of the blended vertex normals [nv, 3] turned by normal_matrix[9] (row-major
+ * 3 x 3) and normalised, A = (pi, 2 pi / 3, pi / 4): the unshadowed limit of surs_mesh_prt (light then in the frame the matrix
+ * turns into).  SURS_E_INVALID: a NULL array that is read, nv or nf < 1, w or h outside [1, 8192], a texture size as above.
+ * The _host twin also writes shading [h, w, 3] (nullable): s_c before the gamma.
+ *
+ * surs_image_resolve: rgba [h m, w m, 4] -> rgb [h, w, 3] and mask [h, w] (nullable) uint8: the mean of a pixel's m x m sub-samples,
+ * added in row-major order in fp32, times 255, rounded to nearest (ties to even); mask from the alpha channel.  m in [1, 8], w m and
+ * h m in [1, 8192]. */
+size_t surs_texture_pyramid_floats(int w, int h);
+int surs_texture_pyramid(const uint8_t *tex, int w, int h, float *levels, void *stream);
+int surs_texture_pyramid_host(const uint8_t *tex, int w, int h, float *levels);
+int surs_mesh_shade_prt(const int32_t *face, const float *bary, const float *verts, int nv, const int32_t *faces, int nf,
+                        const float *view, const int32_t *faces_uv, const float *uvs, int nuv, const float *prt, const float *normals,
+                        const float *normal_matrix, const float *light, const float *pyramid, int tw, int th, int w, int h, float *rgba,
+                        void *stream);
+int surs_mesh_shade_prt_host(const int32_t *face, const float *bary, const float *verts, int nv, const int32_t *faces, int nf,
+                             const float *view, const int32_t *faces_uv, const float *uvs, int nuv, const float *prt,
+                             const float *normals, const float *normal_matrix, const float *light, const float *pyramid, int tw, int th,
+                             int w, int h, float *rgba, float *shading);
+int surs_image_resolve(const float *rgba, int w, int h, int m, uint8_t *rgb, uint8_t *mask, void *stream);
+int surs_image_resolve_host(const float *rgba, int w, int h, int m, uint8_t *rgb, uint8_t *mask);
+
 /* ---------------------------------------------------------------- device repack
  * The packed images the forward reads (surs_conv_pack_weights*, the blobs of surs_mlp_pack / surs_mlp_pack_generic) rebuilt ON THE
  * DEVICE from the plain fp32 parameters an optimiser has just stepped: the bytes the host packers give for the same values, without

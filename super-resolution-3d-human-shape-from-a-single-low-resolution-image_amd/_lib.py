@@ -340,6 +340,18 @@ _SIGS = {
     "surs_mesh_shade_normals": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "surs_mesh_raster_host": (C.c_int, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "surs_mesh_shade_normals_host": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "surs_mesh_prt_workspace_bytes": (_sz, [_i, _i]),
+    "surs_mesh_prt": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp, _i, _f, _vp, _vp, _sz, _vp]),
+    "surs_mesh_prt_counted": (C.c_int, [_vp, _i, _vp, _i, _vp, _vp, _i, _f, _vp, _vp, _sz, _vp, _vp]),
+    "surs_mesh_prt_host":(C.c_int, [_vp, _i, _vp, _i, _vp, _vp, _i, _f, _vp, _vp]),
+    "surs_texture_pyramid_floats": (_sz, [_i, _i]),
+    "surs_texture_pyramid": (C.c_int, [_vp, _i, _i, _vp, _vp]),
+    "surs_texture_pyramid_host": (C.c_int, [_vp, _i, _i, _vp]),
+    "surs_mesh_shade_prt": (C.c_int, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "surs_mesh_shade_prt_host": (C.c_int, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp,
+                                           _vp]),
+    "surs_image_resolve": (C.c_int, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "surs_image_resolve_host": (C.c_int, [_vp, _i, _i, _i, _vp, _vp]),
     "surs_conv_repack_tiles": (C.c_int, [_i, _i, _i]),
     "surs_conv_repack": (C.c_int, [_vp, _i, _vp]),
     "surs_conv1x1_merge": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
@@ -381,6 +393,7 @@ _SIGS = {
     "surs_image_hsv_host": (C.c_int, [_vp, C.c_longlong, _i, _vp]),
 }
 MESH_FACES_PER_PART, SAMPLE_SELECT_CHUNK = 4096, 1024     # SURS_MESH_FACES_PER_PART, SURS_SAMPLE_SELECT_CHUNK of include/surs.h
+MESH_PRT_CHUNK = 512     # SURS_MESH_PRT_CHUNK of include/surs.h
 EXPORTS = sorted(_SIGS)
 
 

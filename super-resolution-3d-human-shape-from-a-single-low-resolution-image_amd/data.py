@@ -218,6 +218,26 @@ class SyntheticDataset:
                 "img_LR": torch.from_numpy(self._w.synthetic_image(self.size, seed=1 + i)), "calib": torch.from_numpy(calib[None])}
 
 
+def param_calib(param, load_size):
+    """(calib, extrinsic) float32 [4,4] of a PARAM dict as TrainDataset.get_render forms them without augmentation (phase 'test'):
+    the same expressions in the same order, for whoever WRITES a dataroot (render.view_param) - tests/test_render_host.py holds the
+    two to each other bit for bit."""
+    ortho_ratio, scale, center, R = param.get("ortho_ratio"), param.get("scale"), param.get("center"), param.get("R")
+    half = float(load_size // 2)
+    translate = -np.matmul(R, center).reshape(3, 1)
+    extrinsic = np.concatenate([R, translate], axis=1)
+    extrinsic = np.concatenate([extrinsic, np.array([0, 0, 0, 1]).reshape(1, 4)], 0)
+    scale_intrinsic = np.identity(4)
+    scale_intrinsic[0, 0] = scale / ortho_ratio
+    scale_intrinsic[1, 1] = -scale / ortho_ratio
+    scale_intrinsic[2, 2] = scale / ortho_ratio
+    uv_intrinsic = np.identity(4)
+    uv_intrinsic[0, 0] = uv_intrinsic[1, 1] = uv_intrinsic[2, 2] = 1.0 / half
+    trans_intrinsic = np.identity(4)
+    intrinsic = np.matmul(trans_intrinsic, np.matmul(uv_intrinsic, scale_intrinsic))
+    return np.matmul(intrinsic, extrinsic).astype(np.float32), extrinsic.astype(np.float32)
+
+
 class TrainDataset:
     """The item contract of the reference's TrainDataset_LR_v2 (lib/data/TrainDataset_LR_v2.py):
 

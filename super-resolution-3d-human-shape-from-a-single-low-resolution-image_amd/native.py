@@ -2673,6 +2673,196 @@ def normal_map_host(verts, faces, view, size, vertex_normals=None):
     return out, face >= 0
 
 
+# ------------------------------------------------------------------ mesh PRT, mesh shading (include/surs.h)
+
+def _np(a, dtype, shape_tail, what):
+    a = np.ascontiguousarray(np.asarray(a, dtype))
+    if a.ndim != len(shape_tail) + 1 or a.shape[1:] != tuple(shape_tail):
+        raise ValueError("%s: [n, %s] expected, not %s" % (what, ", ".join(str(s) for s in shape_tail), a.shape))
+    return a
+
+
+def _dev_f32(a, dev, shape, what):
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float32)))
+    t = t.to(device=dev, dtype=torch.float32).contiguous()
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError("%s: %s expected, not %s" % (what, tuple(shape), tuple(t.shape)))
+    return t
+
+
+def mesh_prt(mesh, normals, dirs, offset, workspace=None, want_tests=False):
+    """surs_mesh_prt: the mesh's per-vertex transfer vectors, float32 [nv, 9] on the device, for unit vertex normals [nv, 3] and unit
+    directions [D, 3] (tensors or arrays); the rays start `offset` along the normal.  Once per subject.  want_tests: through
+    surs_mesh_prt_counted, also the number of ray - triangle tests executed (an int: one read of the device)."""
+    dev = mesh.verts.device
+    n = _dev_f32(normals, dev, (mesh.nv, 3), "normals")
+    d = dirs if isinstance(dirs, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(dirs, np.float32)))
+    d = d.to(device=dev, dtype=torch.float32).contiguous()
+    if d.dim() != 2 or d.shape[1] != 3 or d.shape[0] < 1:
+        raise ValueError("dirs: [D, 3] expected, not %s" % (tuple(d.shape),))
+    D = d.shape[0]
+    nbytes = lib().surs_mesh_prt_workspace_bytes(mesh.nv, D)
+    ws = workspace if workspace is not None else torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    prt = torch.empty((mesh.nv, 9), dtype=torch.float32, device=dev)
+    if want_tests:
+        waves = torch.zeros((mesh.nv * D + 63) // 64, dtype=torch.int32, device=dev)
+        check(lib().surs_mesh_prt_counted(_ptr(mesh.verts), mesh.nv, _ptr(mesh.faces), mesh.nf, _ptr(n), _ptr(d), D, float(offset),
+                                          _ptr(prt), _ptr(ws), ws.numel() * ws.element_size(), _ptr(waves), _stream()))
+        return prt, 64 * int(waves.to(torch.int64).sum())
+    check(lib().surs_mesh_prt(_ptr(mesh.verts), mesh.nv, _ptr(mesh.faces), mesh.nf, _ptr(n), _ptr(d), D, float(offset), _ptr(prt),
+                              _ptr(ws), ws.numel() * ws.element_size(), _stream()))
+    return prt
+
+
+def mesh_prt_host(verts, faces, normals, dirs, offset, want_visible=False):
+    """surs_mesh_prt_host on numpy arrays, on the HOST: float32 [nv, 9], the kernels' bits; with want_visible also uint8 [nv, D], 1
+    where the pair contributed (n . d > 0 and no triangle hit)."""
+    v, f = _host_mesh(verts, faces)
+    n = np.ascontiguousarray(np.asarray(normals, np.float32))
+    d = _np(dirs, np.float32, (3,), "dirs")
+    if n.shape != (len(v), 3):
+        raise ValueError("normals: [%d, 3] expected, not %s" % (len(v), n.shape))
+    prt = np.empty((len(v), 9), np.float32)
+    vis = np.empty((len(v), len(d)), np.uint8) if want_visible else None
+    check(lib().surs_mesh_prt_host(v.ctypes.data, len(v), f.ctypes.data, len(f), n.ctypes.data, d.ctypes.data, len(d), float(offset),
+                                   prt.ctypes.data, vis.ctypes.data if want_visible else None))
+    return (prt, vis) if want_visible else prt
+
+
+class Texture:
+    """A texture's packed pyramid (surs_texture_pyramid): `.levels` float32 - a device tensor, or a numpy array with host=True -, and
+    `.w`, `.h` of level 0.  level(l) is a [h >> l, w >> l, 3] view."""
+
+    def __init__(self, levels, w, h):
+        self.levels, self.w, self.h = levels, w, h
+
+    def level(self, l):
+        off = sum(3 * (self.w >> i) * (self.h >> i) for i in range(l))
+        return self.levels[off:off + 3 * (self.w >> l) * (self.h >> l)].reshape(self.h >> l, self.w >> l, 3)
+
+
+def texture_pyramid(tex, host=False, device=None):
+    """tex uint8 [h, w, 3] (row 0 the top of the image; array or tensor) -> Texture."""
+    if isinstance(tex, torch.Tensor) and not host:
+        t = tex.to(device=device or tex.device).contiguous()
+        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
+            raise ValueError("texture: uint8 [h, w, 3] expected")
+    else:
+        t = np.ascontiguousarray(tex.cpu().numpy() if isinstance(tex, torch.Tensor) else np.asarray(tex))
+        if t.dtype != np.uint8 or t.ndim != 3 or t.shape[2] != 3:
+            raise ValueError("texture: uint8 [h, w, 3] expected, not %s %s" % (t.dtype, t.shape))
+        if not host:
+            t = torch.from_numpy(t).to(device or require_gpu())
+    h, w = int(t.shape[0]), int(t.shape[1])
+    n = lib().surs_texture_pyramid_floats(w, h)
+    if host:
+        levels = np.empty(max(n, 1), np.float32)
+        check(lib().surs_texture_pyramid_host(t.ctypes.data, w, h, levels.ctypes.data))
+    else:
+        levels = torch.empty(max(n, 1), dtype=torch.float32, device=t.device)
+        check(lib().surs_texture_pyramid(_ptr(t), w, h, _ptr(levels), _stream()))
+    return Texture(levels[:n], w, h)
+
+
+def mesh_shade_prt(mesh, view, face, bary, light, prt=None, normals=None, normal_matrix=None, texture=None, faces_uv=None, uvs=None):
+    """surs_mesh_shade_prt on the device: face int32 [h, w] and bary [h, w, 2] of mesh_raster(mesh, view, (h, w), want_bary=True) ->
+    rgba float32 [h, w, 4].  light [9, 3]: in the mesh's frame with prt [nv, 9]; without, normals [nv, 3] and normal_matrix [3, 3] give
+    the analytic transfer and light is in the frame the matrix turns into.  texture: a device Texture with faces_uv int32 [nf, 3] (the
+    faces' own corner order) and uvs [nuv, 2]; None: albedo 1."""
+    dev = mesh.verts.device
+    h, w = int(face.shape[0]), int(face.shape[1])
+    assert face.dtype == torch.int32 and face.is_contiguous() and bary.dtype == torch.float32 and bary.is_contiguous()
+    assert tuple(bary.shape) == (h, w, 2)
+    m = _view12(view)
+    li = np.ascontiguousarray(np.asarray(light, np.float64).astype(np.float32))
+    if li.shape != (9, 3):
+        raise ValueError("light: [9, 3] expected, not %s" % (li.shape,))
+    p = _dev_f32(prt, dev, (mesh.nv, 9), "prt") if prt is not None else None
+    n = nm = None
+    if p is None:
+        if normals is None or normal_matrix is None:
+            raise ValueError("without prt the vertex normals and the normal matrix are needed")
+        n = _dev_f32(normals, dev, (mesh.nv, 3), "normals")
+        nm = np.ascontiguousarray(np.asarray(normal_matrix, np.float64).astype(np.float32).reshape(3, 3))
+    fu = uv = pyr = None
+    tw = th = nuv = 0
+    if texture is not None:
+        fu = faces_uv if isinstance(faces_uv, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(faces_uv, np.int32)))
+        fu = fu.to(device=dev, dtype=torch.int32).contiguous()
+        if tuple(fu.shape) != (mesh.nf, 3):
+            raise ValueError("faces_uv: [%d, 3] expected, not %s" % (mesh.nf, tuple(fu.shape)))
+        uv = uvs if isinstance(uvs, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(uvs, np.float32)))
+        uv = uv.to(device=dev, dtype=torch.float32).contiguous()
+        if uv.dim() != 2 or uv.shape[1] != 2 or uv.shape[0] < 1:
+            raise ValueError("uvs: [nuv, 2] expected, not %s" % (tuple(uv.shape),))
+        nuv, pyr, tw, th = uv.shape[0], texture.levels, texture.w, texture.h
+    rgba = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
+    check(lib().surs_mesh_shade_prt(_ptr(face), _ptr(bary), _ptr(mesh.verts), mesh.nv, _ptr(mesh.faces), mesh.nf, m.ctypes.data, _ptr(fu),
+                                    _ptr(uv), nuv, _ptr(p), _ptr(n), nm.ctypes.data if nm is not None else None, li.ctypes.data,
+                                    _ptr(pyr), tw, th, w, h, _ptr(rgba), _stream()))
+    return rgba
+
+
+def mesh_shade_prt_host(verts, faces, view, face, bary, light, prt=None, normals=None, normal_matrix=None, texture=None, faces_uv=None,
+                        uvs=None, want_shading=False):
+    """mesh_shade_prt on numpy arrays, on the HOST (texture: a host Texture): rgba float32 [h, w, 4], the kernel's bits; with
+    want_shading also float32 [h, w, 3], the shading before the gamma."""
+    v, f = _host_mesh(verts, faces)
+    face = np.ascontiguousarray(np.asarray(face, np.int32))
+    h, w = face.shape
+    bary = np.ascontiguousarray(np.asarray(bary, np.float32)).reshape(h, w, 2)
+    m = _view12(view)
+    li = np.ascontiguousarray(np.asarray(light, np.float64).astype(np.float32))
+    if li.shape != (9, 3):
+        raise ValueError("light: [9, 3] expected, not %s" % (li.shape,))
+    p = n = nm = fu = uv = pyr = None
+    if prt is not None:
+        p = np.ascontiguousarray(np.asarray(prt, np.float32))
+        if p.shape != (len(v), 9):
+            raise ValueError("prt: [%d, 9] expected, not %s" % (len(v), p.shape))
+    else:
+        if normals is None or normal_matrix is None:
+            raise ValueError("without prt the vertex normals and the normal matrix are needed")
+        n = np.ascontiguousarray(np.asarray(normals, np.float32))
+        if n.shape != (len(v), 3):
+            raise ValueError("normals: [%d, 3] expected, not %s" % (len(v), n.shape))
+        nm = np.ascontiguousarray(np.asarray(normal_matrix, np.float64).astype(np.float32).reshape(3, 3))
+    tw = th = nuv = 0
+    if texture is not None:
+        fu = np.ascontiguousarray(np.asarray(faces_uv, np.int32))
+        if fu.shape != (len(f), 3):
+            raise ValueError("faces_uv: [%d, 3] expected, not %s" % (len(f), fu.shape))
+        uv = _np(uvs, np.float32, (2,), "uvs")
+        nuv, pyr, tw, th = len(uv), np.ascontiguousarray(texture.levels), texture.w, texture.h
+    rgba = np.empty((h, w, 4), np.float32)
+    shading = np.empty((h, w, 3), np.float32) if want_shading else None
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    check(lib().surs_mesh_shade_prt_host(face.ctypes.data, bary.ctypes.data, v.ctypes.data, len(v), f.ctypes.data, len(f), m.ctypes.data,
+                                         ptr(fu), ptr(uv), nuv, ptr(p), ptr(n), ptr(nm), li.ctypes.data, ptr(pyr), tw, th, w, h,
+                                         rgba.ctypes.data, ptr(shading)))
+    return (rgba, shading) if want_shading else rgba
+
+
+def image_resolve(rgba, m, host=False):
+    """surs_image_resolve: rgba float32 [h m, w m, 4] -> (rgb uint8 [h, w, 3], mask uint8 [h, w]), the mean of each pixel's m x m
+    sub-samples in bytes.  A device tensor, or - host - a numpy array through the host twin."""
+    m = int(m)
+    H, W = int(rgba.shape[0]), int(rgba.shape[1])
+    if m < 1 or H % m or W % m or tuple(rgba.shape[2:]) != (4,):
+        raise ValueError("image_resolve: rgba [h m, w m, 4] expected at m = %d, not %s" % (m, tuple(rgba.shape)))
+    h, w = H // m, W // m
+    if host:
+        a = np.ascontiguousarray(np.asarray(rgba, np.float32))
+        rgb, mask = np.empty((h, w, 3), np.uint8), np.empty((h, w), np.uint8)
+        check(lib().surs_image_resolve_host(a.ctypes.data, w, h, m, rgb.ctypes.data, mask.ctypes.data))
+        return rgb, mask
+    assert rgba.dtype == torch.float32 and rgba.is_contiguous()
+    rgb = torch.empty((h, w, 3), dtype=torch.uint8, device=rgba.device)
+    mask = torch.empty((h, w), dtype=torch.uint8, device=rgba.device)
+    check(lib().surs_image_resolve(_ptr(rgba), w, h, m, _ptr(rgb), _ptr(mask), _stream()))
+    return rgb, mask
+
+
 # ------------------------------------------------------------------ training images
 
 class ImagePlan:
